@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- calibration iterations/s of the network-wise calibration hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--global-batch 16]
 
@@ -18,7 +18,13 @@ Scaling modes:
   --global-batch G   strong: the global batch is fixed (configs[3]: G = 16), per-GPU batch = G/N; value = global-batch-G
                      iterations/s.
 
-Prints ONE JSON line (rank 0) with
+A plain run sets up, warms up, times the K steps once and prints ONE JSON line (rank 0): `metric`, `value`, `unit`,
+`ms_per_step` (milliseconds per timed step), `higher_is_better`, `dtype` and the configuration; no timed step is
+profiled.  --dump-outputs DIR also writes what the timed path computed in its last step (the rounding variables
+`alpha` and the weight scales `delta` of every quantised layer, float32) as DIR/<layer>.<tensor>.npy.
+
+--full adds everything else the line used to carry (the HIP-event profiling of the headline run, its repeats, the
+secondary workloads and the CPU oracle); the line then also holds
   `roofline`      dominant kernel of the timed (default-precision, bf16x3) run, HIP-event timed inside every 10th timed step (the 6th, 16th, ...); the
                   bound (mfma | hbm) is chosen per kernel from its arithmetic intensity against the ridge of its matrix pipe;
   `repeats`       it/s of `--repeats` independent timed runs of the same K steps (`value` = the first);
@@ -178,6 +184,13 @@ def main():
     ap.add_argument("--workload", choices=("hnerv", "nerv", "uvg12m"), default="hnerv",
                     help="hnerv = the headline config (default); nerv = NeRV-3M + Hadamard (BASELINE configs[2]); uvg12m = HNeRV UVG "
                          "960x1920 ~12M (BASELINE configs[4] shape) as the headline line of this run; neither has a cpu baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also profile the headline run (roofline, per-kernel tables), repeat it (--repeats) and measure the "
+                         "secondary objects (fp32, phase1, nerv, trained, uvg, psnr, cpu_baseline; each has its --no-* switch); "
+                         "off by default: a plain run times the K steps once and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline run computed in its last step (alpha and delta of "
+                         "every quantised layer, float32) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -201,7 +214,7 @@ def main():
             dist.init_process_group(backend)
 
     from neuroquant_amd import ops
-    from neuroquant_amd.quantization import QuantModel, model_reconstruction
+    from neuroquant_amd.quantization import QuantModel, QuantModule, model_reconstruction
     from neuroquant_amd.utils import CacheLoader, FrameCache, synthetic_frames
 
     strong = args.global_batch > 0
@@ -214,6 +227,8 @@ def main():
         B = 2                   # frames per GPU per iteration (BASELINE configs[1])
         gB = B * world
     K, W = args.steps, args.warmup
+    # HIP events inside the timed steps (the roofline object): --full only; those steps run eagerly instead of replaying
+    profile = args.full and not os.environ.get("NQ_BENCH_NOPROF")
     n_frames = max(args.frames // gB * gB, gB)
     # ---- workloads, resident in HBM (built on first use) ----
     wl_box = {}
@@ -241,12 +256,17 @@ def main():
                 wl_box[key] = FrameCache(synthetic_frames(n, hw[0], hw[1], seed=903, device=dev))
             cache = wl_box[key]
             model = build_model(workload=name).to(dev)
+            # the encoder is set-up, not the timed path: PyTorch's own convolutions, not MIOpen's, whose choice of solution
+            # follows the tuning database in the home directory (the inputs would differ in the last bits between a first
+            # run and a later one)
+            miopen, torch.backends.cudnn.enabled = torch.backends.cudnn.enabled, False
             with torch.no_grad():
                 if name == "nerv":
                     emb = model.encode(torch.arange(n, device=dev).float() / n)
                 else:
                     emb = torch.cat([model.encode(cache.batch(torch.arange(i, min(i + 4, n), device=dev)))
                                      for i in range(0, n, 4)])
+            torch.backends.cudnn.enabled = miopen
             del model
             wl = dict(arch="nerv" if name == "nerv" else "hnerv", hadamard=name == "nerv", cache=cache, n=n, emb=emb,
                       make=lambda: build_model(workload=name).to(dev))
@@ -258,9 +278,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_run(precision, K, W, workload=args.workload, phase1=False):
+    def timed_run(precision, K, W, workload=args.workload, phase1=False, keep_outputs=False):
         """Fresh QuantModel on the seeded weights; W untimed + K timed phase-2 iterations under `precision` (phase1: the
-        same count of PHASE-1 iterations -- scales learned through the UAQ fake-quant, reference calib_model.py:119-165)."""
+        same count of PHASE-1 iterations -- scales learned through the UAQ fake-quant, reference calib_model.py:119-165).
+        keep_outputs: the result also holds `outputs`, {name: host float32 tensor} of what the last step left in the model."""
         wl = workload_of(workload)
         nerv, arch, cache, emb = wl["hadamard"], wl["arch"], wl["cache"], wl["emb"]
         ops.set_conv_precision(precision)
@@ -290,7 +311,7 @@ def main():
                 gc.collect()
                 gc.disable()
                 sync()
-                if not os.environ.get("NQ_BENCH_NOPROF"):
+                if profile:
                     ops.profile_start()
                     ops.profile_sample(phase == 0)
                 t["t0"] = time.perf_counter()
@@ -301,7 +322,7 @@ def main():
                 sync()
                 t["t1"] = time.perf_counter()
                 gc.enable()
-                t["prof"] = ops.profile_stop() if not os.environ.get("NQ_BENCH_NOPROF") else {}
+                t["prof"] = ops.profile_stop() if profile else {}
 
         # iters = 20 * len(loader): int(0.05 * iters / len) = 1 phase-1 epoch of W+K+1 iterations, cut after W+K by max_steps
         model_reconstruction(qnn, cali_data=emb, gt=loader, arch=arch, batch_size=gB,
@@ -321,20 +342,32 @@ def main():
         if use_dist:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         prof_steps = len([d for d in range(W, steps_total) if (d - W) % PROF_EVERY == phase])
+        outputs = None
+        if keep_outputs:
+            outputs = {}
+            for name, m in model.named_modules():
+                if isinstance(m, QuantModule):
+                    outputs[f"{name}.weight_alpha"] = m.weight_quantizer.alpha.detach().float().cpu()
+                    outputs[f"{name}.bias_alpha"] = m.bias_quantizer.alpha.detach().float().cpu()
+                    outputs[f"{name}.weight_delta"] = m.weight_quantizer.delta.detach().float().cpu()
         del qnn, model
         torch.cuda.empty_cache()
         return dict(elapsed=float(tmax.item()), t_enq=t["t_enq"] - t["t0"], prof=t["prof"], avg_bits=avg_bits,
-                    prof_steps=prof_steps)
+                    prof_steps=prof_steps, outputs=outputs)
 
     nerv = args.workload == "nerv"
-    main_run = timed_run(args.precision, K, W)
+    main_run = timed_run(args.precision, K, W, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if main_run["outputs"] is not None:
+        dump_outputs(args.dump_outputs, main_run.pop("outputs"))
     # the same K timed steps again (fresh model, same warm-up): the spread the 47 ms timed region has on this box goes into
     # the line (`repeats`); `value` stays the first, contract run
-    more_runs = [timed_run(args.precision, K, W) for _ in range(max(args.repeats - 1, 0))]
+    more_runs = [timed_run(args.precision, K, W) for _ in range(max(args.repeats - 1, 0) if args.full else 0)]
     # the secondary objects (exact fp32, phase 1, NeRV) describe the single-GPU kernels: N = 1 only -- at N > 1 the line is
     # the data-parallel headline and its repeats, nothing else rides on the collectives
     if world > 1:
         args.no_fp32 = args.no_phase1 = args.no_nerv = args.no_trained = args.no_uvg = True
+    if not args.full:   # a plain run: the headline line only
+        args.no_fp32 = args.no_phase1 = args.no_nerv = args.no_trained = args.no_uvg = args.no_cpu_baseline = True
     fp32_run = None
     if not args.no_fp32:
         Kf = max(1, min(K, args.fp32_steps))
@@ -363,6 +396,28 @@ def main():
 
     elapsed = main_run["elapsed"]
     per_step_units = 1 if strong else world     # strong: one global-batch iteration per step; weak: `world` B=2-equivalents
+    value = K * per_step_units / elapsed
+    line = {
+        "metric": "calibration iters/sec (HNeRV Bunny 1280x640, 21k iters) + final PSNR vs ref",
+        "value": round(value, 3),
+        "unit": (f"it/s (global batch {gB} frames per iteration, sharded over the GPUs)" if strong
+                 else "it/s (B=2 frames per iteration-equivalent, summed over GPUs)"),
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(elapsed / K * 1e3, 3),
+        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+        "dtype": ("f32 operands split into bf16 hi+lo, 3 BF16 MFMAs per product, fp32 accumulate (bf16x3); fp32 MFMA on small layers"
+                  if args.precision == "bf16x3" else "f32 (exact fp32-input MFMA, --precision fp32)"),
+        "data": "synthetic",
+        "config": {"workload": {"nerv": "NeRV Bunny_1280x640_3M + Hadamard", "hnerv": "HNeRV Bunny_1280x640_3M",
+                                "uvg12m": "HNeRV UVG 960x1920 ~12M (tools/hnerv_uvg_12m.yaml)"}[args.workload]
+                   + ", channel_wise, bits 6 5 4 5 5 6 6, phase-2 (AdaRound) iteration",
+                   "per_gpu_batch": B, "global_batch": gB, "frames": workload_of(args.workload)["n"], "avg_bits": main_run["avg_bits"],
+                   "parallelism": f"dp{world}"},
+    }
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
     if os.environ.get("NQ_BENCH_NOPROF"):   # throughput only (measures the cost of the event records themselves)
         print(json.dumps({"value": round(K * per_step_units / elapsed, 3), "ms_per_step": round(elapsed / K * 1e3, 3),
                           "note": "no profiling"}))
@@ -449,22 +504,7 @@ def main():
     if world == 1 and not args.no_cpu_baseline and args.workload == "hnerv":
         psnr, cpu = psnr_and_cpu_baseline(dev)
 
-    value = K * per_step_units / elapsed
-    out = {
-        "metric": "calibration iters/sec (HNeRV Bunny 1280x640, 21k iters) + final PSNR vs ref",
-        "value": round(value, 3),
-        "unit": (f"it/s (global batch {gB} frames per iteration, sharded over the GPUs)" if strong
-                 else "it/s (B=2 frames per iteration-equivalent, summed over GPUs)"),
-        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(elapsed / K * 1e3, 3),
-        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-        "dtype": ("f32 operands split into bf16 hi+lo, 3 BF16 MFMAs per product, fp32 accumulate (bf16x3); fp32 MFMA on small layers"
-                  if args.precision == "bf16x3" else "f32 (exact fp32-input MFMA, --precision fp32)"),
-        "data": "synthetic",
-        "config": {"workload": {"nerv": "NeRV Bunny_1280x640_3M + Hadamard", "hnerv": "HNeRV Bunny_1280x640_3M",
-                                "uvg12m": "HNeRV UVG 960x1920 ~12M (tools/hnerv_uvg_12m.yaml)"}[args.workload]
-                   + ", channel_wise, bits 6 5 4 5 5 6 6, phase-2 (AdaRound) iteration",
-                   "per_gpu_batch": B, "global_batch": gB, "frames": workload_of(args.workload)["n"], "avg_bits": main_run["avg_bits"],
-                   "parallelism": f"dp{world}"},
+    out = dict(line, **{
         "roofline": roofline,
         "repeats": {"values": [round(K * per_step_units / r["elapsed"], 3) for r in [main_run] + more_runs],
                     "note": "it/s of independent timed runs of the same K steps on this box; `value` is the first"},
@@ -478,10 +518,21 @@ def main():
         "uvg": uvg_obj,
         "psnr": psnr,
         "cpu_baseline": cpu,
-    }
+    })
     print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, limit=64 * 10 ** 6):
+    """{name: host float32 tensor} -> out_dir/<name>.npy, whole arrays (the largest workload, UVG-12M, dumps ~48 MB)."""
+    import numpy as np
+    total = sum(a.numel() * 4 for a in arrays.values())
+    if total > limit:
+        raise SystemExit(f"--dump-outputs: {total / 1e6:.1f} MB of outputs exceed the {limit / 1e6:.0f} MB limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy().astype(np.float32))
 
 
 def omega_sweep_timing(wl, dev, B):

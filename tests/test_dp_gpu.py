@@ -445,7 +445,7 @@ def test_bench_command_at_world_two(extra, want_gb, want_scaling):
     """Rehearsal of the driver's SCALE command before hardware sees it: `bench.py --gpus 2 --steps 4 --warmup 2` as two fresh
     processes under the torchrun environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*), both on this card, process group
     gloo (NQ_DIST_BACKEND; RCCL refuses two ranks on one device).  Both ranks must exit 0, rank 0 alone prints ONE JSON line
-    with the data-parallel headline (n_gpus 2, dp2, the global batch, a roofline object) and the single-GPU secondary
+    with the data-parallel headline (n_gpus 2, dp2, the global batch, a roofline object: --full) and the single-GPU secondary
     objects suppressed."""
     import json
     import subprocess
@@ -458,7 +458,7 @@ def test_bench_command_at_world_two(extra, want_gb, want_scaling):
                    WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         env.pop("NQ_DP_REHEARSAL", None)
         procs.append(subprocess.Popen([sys.executable, bench, "--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1",
-                                       "--frames", "32", "--no-cpu-baseline", *extra], env=env, stdout=subprocess.PIPE,
+                                       "--frames", "32", "--no-cpu-baseline", "--full", *extra], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE))
     outs = []
     for p in procs:

@@ -508,3 +508,36 @@ def test_full_length_calibration_fp32_vs_bf16x3(caplog):
     assert f32["q_opt"] >= f32["q_noopt"] + 1.5 and b3["q_opt"] >= b3["q_noopt"] + 1.5, (f32, b3)
     # the default kernels evaluate the model they calibrated to the same number
     assert abs(b3["q_opt_eval_bf16x3"] - b3["q_opt"]) <= 2e-3
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: ONE JSON line with the headline fields and
+    nothing of --full (no roofline, repeats or secondary objects), K timed steps, and the last step's rounding variables /
+    scales as float32 .npy files (64 MB at most); two fresh processes with the same arguments dump the same arrays."""
+    import json
+    import subprocess
+    bench = os.path.join(ROOT, "bench.py")
+    dumps, lines = [], []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        p = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "3", "--warmup", "4", "--frames", "8",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        js = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(js) == 1, p.stdout[-1000:]
+        lines.append(json.loads(js[0]))
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 4 and line["n_gpus"] == 1 and line["higher_is_better"] is True
+    assert line["value"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-2 * line["value"]
+    assert line["metric"] and line["unit"].startswith("it/s") and line["dtype"]
+    for k in ("roofline", "repeats", "fp32", "phase1", "nerv", "trained", "uvg", "psnr", "cpu_baseline"):
+        assert k not in line, k
+    a, b = dumps
+    # 7 quantised layers of HNeRV-3M: the weight and bias rounding variables and the weight scales of each
+    assert len(a) == 21 and sorted(a) == sorted(b), sorted(a)
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64e6
+    assert sum(x.size for n, x in a.items() if n.endswith(".weight_alpha.npy")) > 2_000_000
+    for n in a:
+        np.testing.assert_array_equal(a[n], b[n], err_msg=n)

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 MODE=${3:-full}         # full | trace (only the per-iteration kernel sequence: one short run)
 PREC=${4:-bf16x3}       # bf16x3 | fp32 (exact fp32-input MFMA convolutions)
-BENCH="python3 $R/bench.py --frames 8 --workload $WL --precision $PREC --no-cpu-baseline --no-fp32 --no-nerv --no-phase1 --no-trained --no-uvg --repeats 1"
+BENCH="python3 $R/bench.py --full --frames 8 --workload $WL --precision $PREC --no-cpu-baseline --no-fp32 --no-nerv --no-phase1 --no-trained --no-uvg --repeats 1"
 if [ "$MODE" = "trace" ]; then
   rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- $BENCH --steps 12 --warmup 5 > $OUT/trace.log 2>&1
   cd $R

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One steady-state calibration iteration as the GPU ran it: kernel by kernel with duration and the idle gap in front of it.
 
-    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --steps 12 --warmup 4 --frames 8 --no-cpu-baseline --no-fp32
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --full --steps 12 --warmup 4 --frames 8 --no-cpu-baseline --no-fp32
     python3 tools/trace_step.py <dir> [out.txt]
 
 An iteration starts at `step_prologue_kernel` (captured iterations, quantization/calib_model.py); the tool prints the LAST
