@@ -392,6 +392,24 @@ NQ_API int nq_head_forward_loss(const float* x, const float* wt, int ld, const f
 /* Per-frame PSNR pieces (utils.py:148-151): sse[f] = sum over one frame of (out-gt)^2, frames of frame_len floats. */
 NQ_API int nq_frame_sse(const float* out, const float* gt, float* sse, int64_t frames, int64_t frame_len, nq_stream_t stream);
 
+/* Per-frame MS-SSIM (utils.py:158-164 -> pytorch_msssim.ms_ssim(X, Y, data_range=1, size_average=False); evaluated beside
+ * the PSNR at calibrate_network.py:109-137): out / gt (frames, C, H, W) fp32 in [0, 1] -> msssim (frames).  Five scales; per
+ * scale an 11-tap Gaussian window (sigma 1.5, float32 taps), separable, valid, along H then along W, of x, y, xx, yy, xy;
+ * cs = mean((2 s12 + C2) / (s1 + s2 + C2)), ssim = mean((2 m1 m2 + C1) / (m1^2 + m2^2 + C1) * cs_map), C1 = 0.01^2, C2 = 0.03^2;
+ * between scales avg_pool2d(2, 2, padding (h % 2, w % 2)) with divisor 4; result = mean over channels of
+ * prod_s relu(cs_s or ssim_5) ^ (0.0448, 0.2856, 0.3001, 0.2363, 0.1333).  One launch per scale (it also writes the pooled
+ * images of the next one) + one finishing launch that adds the per-workgroup partial sums in a fixed order: no atomics,
+ * bit-identical from call to call and independent of the other frames of the call.  Variances are taken about a
+ * per-workgroup pivot, so the last bits differ from a literal fp32 evaluation; parity with the pip package's last bits
+ * is not pinned (the package is not available where this library is built and tested: the yardstick is a float64
+ * restatement of the definition, tests/msssim_ref.py).  ws: nq_ms_ssim_ws_floats(frames, C, H, W) floats (the pooled
+ * pyramids of both images + the partial sums; 0 for arguments nq_ms_ssim rejects).  NQ_ERR_INVALID for null pointers,
+ * non-positive sizes and min(H, W) <= 160 (the package's assert), all checked before the device is touched;
+ * NQ_ERR_UNSUPPORTED for frames * C > 65535. */
+NQ_API int64_t nq_ms_ssim_ws_floats(int64_t frames, int C, int H, int W);
+NQ_API int nq_ms_ssim(const float* out, const float* gt, float* msssim, float* ws, int64_t frames, int C, int H, int W,
+               nq_stream_t stream);
+
 /* Frame gather: dst[i] = float(src_u8[idx[i]]) / 255 for frames of frame_len bytes (videosets/datasets.py:19-24);
  * idx is a device int64 array of n entries. */
 NQ_API int nq_gather_frames_u8(const uint8_t* src, const int64_t* idx, float* dst, int64_t n, int64_t frame_len,

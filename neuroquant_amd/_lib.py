@@ -148,6 +148,8 @@ def _load():
     sig("nq_channel_sum", I, P, P, P, I, I, L, P)
     sig("nq_l2_loss_tanh_head", I, P, P, P, P, P, P, P, P, I, I, L, L, F, P)
     sig("nq_frame_sse", I, P, P, P, L, L, P)
+    sig("nq_ms_ssim_ws_floats", L, L, I, I, I)
+    sig("nq_ms_ssim", I, P, P, P, P, L, I, I, I, P)
     sig("nq_gather_frames_u8", I, P, P, P, L, L, P)
     sig("nq_adaround_fwht_multi", I, POINTER(FqFwhtSeg), I, P)
     sig("nq_fwht_adaround_adam_multi", I, POINTER(FqFwhtSeg), I, F, F, F, F, F, F, P, P)
@@ -167,7 +169,7 @@ EXPORTS = (
     "nq_conv_wgrad3_supported", "nq_conv_wgrad3_ws_floats", "nq_conv_wgrad3_plan", "nq_conv_wgrad3", "nq_conv_wgrad3_swapped",
     "nq_conv_wgrad3_slabs", "nq_conv_wgrad3_swapped_slabs", "nq_conv_wgrad_slabs", "nq_wgrad_reduce_multi",
     "nq_conv_wgrad_ws_floats", "nq_conv_wgrad", "nq_ps_gelu_backward", "nq_tanh_out_backward", "nq_l2_loss",
-    "nq_channel_sum", "nq_l2_loss_tanh_head", "nq_frame_sse", "nq_gather_frames_u8",
+    "nq_channel_sum", "nq_l2_loss_tanh_head", "nq_frame_sse", "nq_ms_ssim_ws_floats", "nq_ms_ssim", "nq_gather_frames_u8",
     "nq_act_dd", "nq_pixel_shuffle", "nq_bias_add", "nq_conv3_split_io", "nq_conv_split_out", "nq_split_words",
     "nq_conv_wgrad3_split_io", "nq_conv_wgrad3_fmt", "nq_conv_wgrad3_slabs_fmt", "nq_head_forward_loss_ws_floats", "nq_head_forward_loss",
     "nq_adaround_fwht_multi", "nq_fwht_adaround_adam_multi", "nq_weight_layouts_all",

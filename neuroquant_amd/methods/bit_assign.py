@@ -38,9 +38,9 @@ import torch.nn as nn
 from ..models import HNeRV, NeRV
 from ..models._decode import _fused_stack
 from ..quantization import QuantModel
-from ..utils import FrameCache, RoundTensor, data_split, get_config, setup_logger
+from ..utils import FrameCache, data_split, get_config, setup_logger
 from .. import ops
-from .calibrate_network import evaluate, load_frames
+from .calibrate_network import evaluate, load_frames, report_line
 
 # toy example (bit_assign.py:26-35)
 hnerv_candidate = {
@@ -225,7 +225,7 @@ def assign(args, cfg):
 
     logging.info('=======================Full-precision model========================')
     res, embedding_list = evaluate(model, cache, args, cfg)
-    logging.info(f'FP: best_pred_seen_psnr: {RoundTensor(res[0], 2)} | best_pred_unseen_psnr: {RoundTensor(res[1], 2)}')
+    logging.info(report_line('FP', args))
     cali_data = torch.cat(embedding_list, dim=0)
 
     if args.candidates:

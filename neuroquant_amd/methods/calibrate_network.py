@@ -3,8 +3,8 @@
 Same flags, same sequence (FP eval -> QuantModel -> set_bitwidth -> lazy scale init -> eval quant off / on ->
 model_reconstruction -> final eval -> torch.save), with the reference's PNG DataLoader replaced by a GPU-resident
 uint8 frame cache (frames are decoded ONCE; the reference re-decodes every frame every epoch in 4 worker processes,
-which alone caps it at ~55 it/s) and PSNR computed by the HIP reduction kernel.  MS-SSIM is not
-computed (third-party pytorch_msssim, out of scope).
+which alone caps it at ~55 it/s) and PSNR and MS-SSIM computed by HIP kernels (ops.frame_psnr, ops.ms_ssim:
+the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package is not pinned, see ops.ms_ssim).
 
     python -m neuroquant_amd.methods.calibrate_network --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny \
         --ckpt epoch300.pth --batch_size 2 --channel_wise --init max --iters_w 21000 --weight 0.01 --b_start 20 \
@@ -100,13 +100,20 @@ def load_frames(args, cfg, device):
     return out.to(device)
 
 
+METRIC_NAMES = ['pred_seen_psnr', 'pred_seen_ssim', 'pred_unseen_psnr', 'pred_unseen_ssim']   # reference args.metric_names
+
+
 @torch.no_grad()
 def evaluate(model, cache: FrameCache, args, cfg):
-    """Per-frame decode + PSNR (reference calibrate_network.py:82-145); returns ([seen_psnr, unseen_psnr], embeddings)."""
+    """Per-frame decode + PSNR + MS-SSIM (reference calibrate_network.py:82-145); returns ([seen_psnr, unseen_psnr],
+    embeddings) and leaves all four means on args.eval_metrics, keyed by METRIC_NAMES (as the reference leaves args.fps).
+    Frames too small for five scales (min(H, W) <= 160) are evaluated for PSNR only: MS-SSIM is logged as n/a and stored
+    as NaN."""
     model.eval()
     n = len(cache)
     dev = cache.frames.device
-    psnr, embeds, dec_times = [], [], []
+    with_ssim = min(cache.frames.shape[-2:]) > 160
+    psnr, ssim, embeds, dec_times = [], [], [], []
     for i in range(n):
         idx = torch.tensor([i], device=dev)
         img = cache.batch(idx)
@@ -115,17 +122,30 @@ def evaluate(model, cache: FrameCache, args, cfg):
         embeds.append(embed_list[0])
         dec_times.append(dec_time)
         psnr.append(ops.frame_psnr(out, img))
+        if with_ssim:
+            ssim.append(ops.ms_ssim(out, img))
         if i % args.print_freq == 0 or i == n - 1:
-            logging.info('[{}], Eval at Step [{}/{}], FPS {}, PSNR {}'.format(
+            logging.info('[{}], Eval at Step [{}/{}], FPS {}, PSNR {}, MS-SSIM {}'.format(
                 datetime.now().strftime("%Y/%m/%d %H:%M:%S"), i + 1, n,
                 round(cfg.get('batch_size', 1) / (sum(dec_times) / len(dec_times)), 1),
-                RoundTensor(torch.cat(psnr).mean().cpu(), 2)))
+                RoundTensor(torch.cat(psnr).mean().cpu(), 2),
+                RoundTensor(torch.cat(ssim).mean().cpu(), 4) if with_ssim else 'n/a'))
     psnr = torch.cat(psnr).cpu()
+    ssim = torch.cat(ssim).cpu() if with_ssim else torch.full((n,), float('nan'))
     seen = [i for i in range(n) if i not in args.val_ind_list]
-    res = [psnr[seen].mean() if seen else torch.zeros(()),
-           psnr[args.val_ind_list].mean() if args.val_ind_list else torch.zeros(())]
+    unseen = list(args.val_ind_list)
+    res = [psnr[seen].mean() if seen else torch.zeros(()), psnr[unseen].mean() if unseen else torch.zeros(())]
+    args.eval_metrics = dict(zip(METRIC_NAMES, [res[0], ssim[seen].mean() if seen else torch.zeros(()),
+                                                res[1], ssim[unseen].mean() if unseen else torch.zeros(())]))
     model.train()
     return res, embeds
+
+
+def report_line(tag, args):
+    """'<tag>: best_pred_seen_psnr: .. | best_pred_seen_ssim: .. | best_pred_unseen_psnr: .. | best_pred_unseen_ssim: ..' from the
+    metrics the last evaluate() left on args (the reference's print_str, calibrate_network.py:212-217)."""
+    return (tag + ': ' if tag else '') + ' | '.join(
+        f'best_{k}: {RoundTensor(v, 4 if k.endswith("ssim") else 2)}' for k, v in args.eval_metrics.items())
 
 
 def calibrate(args, cfg):
@@ -158,8 +178,8 @@ def calibrate(args, cfg):
         logging.info('no --ckpt: random-initialised weights (throughput runs only)')
     model.to(device)
 
-    def report(tag, res):
-        logging.info(f'{tag}: best_pred_seen_psnr: {RoundTensor(res[0], 2)} | best_pred_unseen_psnr: {RoundTensor(res[1], 2)}')
+    def report(tag, res):   # res: evaluate()'s return value, whose four metrics are on args.eval_metrics
+        logging.info(report_line(tag, args))
 
     logging.info('=======================Full-precision model========================')
     res, embedding_list = evaluate(model, cache, args, cfg)

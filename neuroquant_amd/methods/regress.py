@@ -3,7 +3,8 @@
 Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss, per-epoch
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
-from the GPU-resident cache; the ConvNeXt encoder and Adam stay in PyTorch.  MS-SSIM / tensorboard are not produced.
+from the GPU-resident cache; the ConvNeXt encoder and Adam stay in PyTorch.  Evaluations report PSNR and MS-SSIM
+(ops.ms_ssim); tensorboard is not produced.
 
     python -m neuroquant_amd.methods.regress --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny
 """
@@ -20,7 +21,7 @@ import torch
 from ..models import HNeRV, NeRV
 from ..utils import CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger
 from .. import ops
-from .calibrate_network import evaluate, load_frames, seed_all
+from .calibrate_network import evaluate, load_frames, report_line, seed_all
 
 
 def parse_args(argv):
@@ -78,7 +79,7 @@ def train(args, cfg):
         model.load_state_dict(torch.load(args.weight, map_location='cpu'), strict=False)
     if args.eval_only:
         res, _ = evaluate(model, cache, args, cfg)
-        logging.info(f'best_pred_seen_psnr: {RoundTensor(res[0], 2)}')
+        logging.info(report_line('', args))
         return res
     optimizer = torch.optim.Adam(model.parameters(), weight_decay=0.)
     args.lr = cfg['learning_rate']
@@ -101,7 +102,8 @@ def train(args, cfg):
                     RoundTensor(torch.cat(psnrs).mean().cpu(), 2)))
         if (epoch + 1) % cfg.get('eval_freq', 30) == 0 or (cfg['epoch'] - epoch) in [1, 3, 5]:
             res, _ = evaluate(model, cache, args, cfg)
-            logging.info(f'Eval at epoch {epoch + 1}: pred_seen_psnr: {RoundTensor(res[0], 2)}')
+            logging.info(f'Eval at epoch {epoch + 1}: pred_seen_psnr: {RoundTensor(res[0], 2)} | pred_seen_ssim: '
+                         f'{RoundTensor(args.eval_metrics["pred_seen_ssim"], 4)}')
         torch.save(model.state_dict(), '{}/model_latest.pth'.format(args.outf))
         if (epoch + 1) % cfg['epoch'] == 0:
             torch.save(model.state_dict(), f'{args.outf}/epoch{epoch + 1}.pth')

@@ -1697,6 +1697,29 @@ def frame_psnr(out, gt):
     return -10 * torch.log10(sse / flen + 1e-9)
 
 
+def ms_ssim(out, gt):
+    """per-frame MS-SSIM of (F, C, H, W) images in [0, 1] -> (F,) fp32 (reference utils.py:158-164:
+    pytorch_msssim.ms_ssim(out, gt, data_range=1, size_average=False)): five scales, 11-tap Gaussian window (sigma 1.5),
+    valid filtering, 2x2 average pooling between scales, weights (0.0448, 0.2856, 0.3001, 0.2363, 0.1333); the definition is
+    spelled out at nq_ms_ssim in include/nq_hip.h.  One HIP launch per scale + a fixed-order finishing launch on the
+    current stream: bit-identical from call to call, a frame's value does not depend on the other frames of the call.
+    Not differentiable (inputs are detached).  ValueError when min(H, W) <= 160 (the package's assert).
+
+    Parity with the pip package's last bits is NOT pinned: pytorch_msssim is not available where this project is built
+    and tested; the tests hold this op to a float64 restatement of the definition (tests/msssim_ref.py)."""
+    out, gt = _dev(out.detach(), "out"), _dev(gt.detach(), "gt")
+    if out.dim() != 4 or out.shape != gt.shape:
+        raise RuntimeError(f"neuroquant_amd: ms_ssim takes two (F, C, H, W) tensors of one shape, got {tuple(out.shape)} and "
+                           f"{tuple(gt.shape)}")
+    F_, C, H, W = out.shape
+    if min(H, W) <= 160:
+        raise ValueError(f"ms_ssim: the smaller side of the image must exceed (11 - 1) * 2**4 = 160, got {H} x {W}")
+    res = torch.empty(F_, device=out.device, dtype=torch.float32)
+    ws = torch.empty(_q("nq_ms_ssim_ws_floats", F_, C, H, W), device=out.device, dtype=torch.float32)
+    L.check(L.lib().nq_ms_ssim(_p(out), _p(gt), _p(res), _p(ws), F_, C, H, W, _stream()), "ms_ssim")
+    return res
+
+
 def gather_frames_u8(frames_u8: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """float frames[idx] / 255 from a GPU-resident uint8 cache (reference videosets/datasets.py:19-24)."""
     if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or not frames_u8.is_contiguous():

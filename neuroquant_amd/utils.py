@@ -1,6 +1,6 @@
 """Host-side helpers around the hot loop: GPU-resident frame cache + batch loader (replaces the reference's
-PNG-decoding DataLoader, videosets/datasets.py + calibrate_network.py:153-165), PSNR (utils.py:148-155), data split
-(utils.py:42-53), config loading, synthetic Bunny-shaped frames for benchmarking, data-parallel helpers."""
+PNG-decoding DataLoader, videosets/datasets.py + calibrate_network.py:153-165), PSNR and MS-SSIM (utils.py:148-164),
+data split (utils.py:42-53), config loading, synthetic Bunny-shaped frames for benchmarking, data-parallel helpers."""
 import logging
 import math
 import os
@@ -55,6 +55,16 @@ def psnr_fn_single(output, gt):
 
 def psnr_fn_batch(output_list, gt):
     return torch.stack([psnr_fn_single(o, gt) for o in output_list], 0).cpu()
+
+
+def msssim_fn_single(output, gt):
+    """per-frame MS-SSIM (reference utils.py:158-160: ms_ssim(output, gt, data_range=1, size_average=False)) on the HIP
+    kernels of ops.ms_ssim; last-bit parity with the pip package pytorch_msssim is not pinned (see ops.ms_ssim)."""
+    return ops.ms_ssim(output.float().detach(), gt.detach()).cpu()
+
+
+def msssim_fn_batch(output_list, gt):
+    return torch.stack([msssim_fn_single(o.detach(), gt.detach()) for o in output_list], 0).cpu()
 
 
 def synthetic_frames(n, h, w, seed=903, device='cuda'):
