@@ -173,7 +173,8 @@ __global__ __launch_bounds__(TPB) void gather_u8_kernel(const uint8_t* __restric
   const uint8_t* s = src + idx[f] * frame_len;
   float* d = dst + f * frame_len;
   int64_t i = ((int64_t)blockIdx.x * TPB + threadIdx.x) * 4;
-  if (i + 3 < frame_len && ((reinterpret_cast<uintptr_t>(s + i) & 3) == 0)) {
+  // both vector accesses need their alignment: with a frame length that is no multiple of 4 neither s + i nor d + i has it
+  if (i + 3 < frame_len && ((reinterpret_cast<uintptr_t>(s + i) & 3) == 0) && ((reinterpret_cast<uintptr_t>(d + i) & 15) == 0)) {
     uchar4 v = *reinterpret_cast<const uchar4*>(s + i);
     float4 o = make_float4((float)v.x / 255.f, (float)v.y / 255.f, (float)v.z / 255.f, (float)v.w / 255.f);
     *reinterpret_cast<float4*>(d + i) = o;
