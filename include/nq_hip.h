@@ -313,7 +313,8 @@ NQ_API int nq_conv_wgrad3_fmt(const float* x, const float* dy, float* dw, float*
  * by exchanged operand roles: R[ci][(co,tap)] = sum_p x[ci][p] * dy[co][p+tap] is the weight gradient of the convolution
  * dy -> x-channels and dW[co][ci][tap] = R[ci][co][k*k-1-tap]; the big tensor x is then the un-shifted GEMM operand read
  * exactly once.  ws: nq_conv_wgrad3_ws_floats(B, Cout, H, W, Cin, k) floats (the exchanged problem).  No bias gradient
- * (use nq_channel_sum on dy). */
+ * (use nq_channel_sum on dy).  NQ_ERR_UNSUPPORTED where that size is the 4-float token of the few-pixel kernel (which has
+ * no exchanged form): a real slab workspace is never that small, so `ws_floats > 4` is the host-side predicate. */
 NQ_API int nq_conv_wgrad3_swapped(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout, int k,
                            nq_stream_t stream);
 
@@ -343,6 +344,7 @@ NQ_API int nq_conv_wgrad3_slabs(const float* x, const float* dy, float* dw, floa
                          int k, nq_wgr_seg* seg, nq_stream_t stream);
 NQ_API int nq_conv_wgrad3_slabs_fmt(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
                              int Cout, int k, nq_wgr_seg* seg, int fmt, nq_stream_t stream);   /* fmt: nq_conv_wgrad3_fmt */
+/* (NQ_ERR_UNSUPPORTED for the same shapes as nq_conv_wgrad3_swapped: a 4-float nq_conv_wgrad3_ws_floats of the exchanged problem) */
 NQ_API int nq_conv_wgrad3_swapped_slabs(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout,
                                  int k, nq_wgr_seg* seg, nq_stream_t stream);
 NQ_API int nq_conv_wgrad_slabs(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,

@@ -314,7 +314,10 @@ inline Wg3Plan plan_wgrad3(int B, int Cin, int H, int W, int Cout, int k) {
     // 160 x 320 stayed on one-row segments for it, 44.2 us; 12 -> two rows 42.3; 6 -> four rows 41.3; HNeRV dec3 84.0 -> 80.9)
     static const int minseg = [] { const char* e = std::getenv("NQ_WGRAD3_MINSEG"); return e ? atoi(e) : 6; }();
     if (!wgrad3_ss1() && ns_pc >= 1) {
-      if (H % 4 == 0 && segs_x * (H / 4) * B / ns_pc >= minseg) sy = 4;
+      // (k = 3, 80 x 384 tile: the four-row image is 2 x 82032 bytes of LDS, 224 more than a workgroup can have; two rows
+      // fit.  launch_wgrad3p in conv_wgrad3_impl.h does not build that kernel and static_asserts that it is the only one)
+      const bool sy4_fits = !(k == 3 && p.mi == 5 && p.ni == 6);
+      if (sy4_fits && H % 4 == 0 && segs_x * (H / 4) * B / ns_pc >= minseg) sy = 4;
       else if (H % 2 == 0 && segs_x * (H / 2) * B / ns_pc >= minseg) sy = 2;
     }
     const int nseg_pc = segs_x * (H / sy) * B;
@@ -722,6 +725,9 @@ static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* d
     if (seg) *seg = nq_wgr_seg{nullptr, nullptr, dw, db, Cout, Cin * k * k, 0, 0, 0, 0, 1};
     return nq_conv_wgrad_flat3(x, dy, dw, db, B, Cin, H, W, Cout, k, nq_s(stream));
   }
+  // Role-swapped entries (here Cin / Cout are those of the EXCHANGED problem): the few-pixel kernel has no transposing
+  // store, and nq_conv_wgrad3_ws_floats sizes a 4-float token for its shapes -- the slabs below would not fit.  Refused.
+  if (swap_kk != 0 && nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
   Wg3Plan p = plan_wgrad3(B, Cin, H, W, Cout, k);
   float* slab = ws;
   float* slab_db = ws + (int64_t)p.nsplit * p.co_pad * p.n_pad;

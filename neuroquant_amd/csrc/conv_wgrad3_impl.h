@@ -162,8 +162,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float* __restrict__ dyp = a.dy + (int64_t)b * Cout * HW + (int64_t)y * W + x0;
     const float* __restrict__ xp = a.x + (int64_t)b * Cin * HW + (int64_t)y * W + x0;
     const bool seg_full = (x0 + SEG <= W);
-    if (y >= PAD && y + PAD < H && x0 >= PAD && x0 + SEG + PAD <= W) {
-      // interior segment (the common case): every halo element exists -> no per-element tests, no exec-mask branches
+    if (y >= PAD && y + PAD < H && x0 >= PAD && x0 + 4 * Q - PAD <= W) {
+      // interior segment (the common case): every halo element exists -> no per-element tests, no exec-mask branches.
+      // The x rows are loaded as Q whole quads, 4*Q - RW (k = 3: 2) elements more than the halo: all of them must lie in
+      // the row, or the last row of the tensor is read past its end (W % 32 in {1, 2}); such segments take the bounds-checked path below
 #pragma unroll
       for (int i = 0; i < DPT; ++i) {
         const int e = tid + i * 256;
@@ -768,6 +770,12 @@ int launch_wgrad3p(const Wgrad3Args& a_in, hipStream_t st) {
     return v;
   }();
   constexpr int BUF_BYTES = SS * SY * (8 * MT + 4 / (SS * SY)) * 16 + ((CIT * PSXP * 4 + 15) / 16) * 16;   // as in the kernel
+  // A workgroup has 160 KiB of LDS.  One combination does not fit: k = 3, 80 x 384 tile, four-row segments (2 x 82032 bytes);
+  // its kernel is not built, and plan_wgrad3 (conv3.hip) gives such layers two-row segments.
+  if constexpr (2 * BUF_BYTES > 160 * 1024) {
+    static_assert(KS == 3 && MI == 5 && NI == 6 && SS == 1 && SY == 4, "a weight-gradient tile no longer fits the LDS: keep plan_wgrad3 off it");
+    return NQ_ERR_UNSUPPORTED;
+  } else {
   size_t lds = (size_t)2 * BUF_BYTES;
   if (a_in.H % SY != 0) return NQ_ERR_UNSUPPORTED;
   Wgrad3Args a = a_in;
@@ -777,6 +785,7 @@ int launch_wgrad3p(const Wgrad3Args& a_in, hipStream_t st) {
   if (int rc = nq_lds_optin<&conv_wgrad3p_kernel<MI, NI, SS, SY>>(lds)) return rc;
   hipLaunchKernelGGL((conv_wgrad3p_kernel<MI, NI, SS, SY>), grid, dim3(512), lds, st, a);
   return nq_launch_status();
+  }
 }
 
 

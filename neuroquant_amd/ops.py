@@ -745,6 +745,15 @@ def channel_sum(x):
     return out
 
 
+def conv_wgrad_swapped3_supported(B, cin, H, W, cout, k):
+    """True when conv_wgrad_swapped3 serves this (cin -> cout) layer: a head with <= 4 output channels whose exchanged problem
+    (cout -> cin) the tiled bf16x3 kernels take.  Exchanged shapes that nq_conv_wgrad3_supported accepts for the few-pixel
+    kernel are NOT served (that kernel has no exchanged form): nq_conv_wgrad3_ws_floats answers its 4-float token for them,
+    which no slab workspace is as small as."""
+    return (cout <= 4 and cin > 4 and cout * k * k <= 64 and conv_wgrad3_supported(B, cout, H, W, cin, k)
+            and _q("nq_conv_wgrad3_ws_floats", B, cout, H, W, cin, k) > 4)
+
+
 def conv_wgrad_swapped3(x, dy, cout, k, want_db, out=None, defer=None):
     """Weight gradient of a conv with very few OUTPUT channels (the 3-channel head) by swapping operand roles:
     R[ci][(co,kh,kw)] = sum_p x[ci][p] * dy[co][p + tap]  is the weight gradient of the conv  dy -> x-channels, and
@@ -881,7 +890,7 @@ def _wgrad_plain(x, gy, k, precision=None):
     cout = gy.shape[1]
     if _use3(precision) and conv_wgrad3_supported(B, cin, H, W, cout, k):
         return conv_wgrad3_raw(x, gy, cout, k, False)[0]
-    if _use3(precision) and cout <= 4 and cin > 4 and cout * k * k <= 64 and conv_wgrad3_supported(B, cout, H, W, cin, k):
+    if _use3(precision) and conv_wgrad_swapped3_supported(B, cin, H, W, cout, k):
         return conv_wgrad_swapped3(x, gy, cout, k, False)[0]
     return conv_wgrad_raw(x, gy, cout, k, False)[0]
 
@@ -1450,8 +1459,7 @@ def _decoder_backward_steps(ctx, g_img):
         if spec.precision == "bf16x3" and not in_gelu and conv_wgrad3_supported(Bx, cin, Hx, Wx, cout, k):
             return conv_wgrad3_raw(x_in, dconv, cout, k, has_b, out=out, defer=pending,
                                    fmt=(1 if x_split else 0) | (2 if g_split else 0))
-        if spec.precision == "bf16x3" and not in_gelu and cout <= 4 and cin > 4 and cout * k * k <= 64 \
-                and conv_wgrad3_supported(Bx, cout, Hx, Wx, cin, k):
+        if spec.precision == "bf16x3" and not in_gelu and conv_wgrad_swapped3_supported(Bx, cin, Hx, Wx, cout, k):
             if l == n - 1 and has_b and head_db is not None:   # bias gradient handed over by l2_loss_head_grad
                 dw, _ = conv_wgrad_swapped3(x_in, dconv, cout, k, False, out=out, defer=pending)
                 if out is not None:
