@@ -188,49 +188,51 @@ def adam_step(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
                                  _stream()), "adam_step")
 
 
+def _ada_segs(items, out_like=None, opt=None, absent=()):
+    """items: [(x, gy, alpha, delta, zp, n_levels, reg_weight, soft)] -> (segments, outputs, temporaries).  An AdaSeg array whose
+    outputs are freshly allocated in the shape of the input named by out_like ("x" | "alpha" | "delta"); or, given opt, an
+    AdaAdamSeg array over opt's moments (updated in place: no outputs, soft is implied).  absent names the inputs the launch
+    does not read ("gy", "alpha"): they become null pointers; every other input must be a device tensor.  The temporaries are
+    the contiguous device tensors the segments point to: the wrapper's local keeps them alive past its launch call."""
+    segs = ((L.AdaSeg if opt is None else L.AdaAdamSeg) * len(items))()
+    outs, keep = [], []
+    for i, (sg, (x, gy, alpha, delta, zp, n_levels, reg_weight, soft)) in enumerate(zip(segs, items)):
+        t = {"x": x, "gy": gy, "alpha": alpha, "delta": delta, "zp": zp}
+        t = {name: None if name in absent else _dev(a, name) for name, a in t.items()}
+        for name, a in t.items():
+            setattr(sg, name, _p(a))
+        sg.rows, sg.row_len, sg.per_row = _rows(t["x"], t["delta"])
+        sg.n_levels, sg.reg_weight = n_levels, float(reg_weight)
+        if opt is None:
+            outs.append(torch.empty_like(t[out_like]))
+            sg.out, sg.soft = _p(outs[-1]), int(bool(soft))
+        else:
+            sg.m, sg.v = _p(opt.m[i]), _p(opt.v[i])
+        keep.append(t)
+    return segs, outs, keep
+
+
 def adaround_forward_multi(items):
     """items: [(x, alpha, delta, zp, n_levels, soft)] -> [fake-quantised tensors], ONE launch for all of them
     (same arithmetic as adaround_forward, bit for bit)."""
-    segs = (L.AdaSeg * len(items))()
-    outs = []
-    for sg, (x, alpha, delta, zp, n_levels, soft) in zip(segs, items):
-        x, alpha, delta, zp = _dev(x), _dev(alpha), _dev(delta), _dev(zp)
-        rows, rl, per_row = _rows(x, delta)
-        y = torch.empty_like(x)
-        outs.append(y)
-        sg.x, sg.gy, sg.alpha, sg.delta, sg.zp, sg.out = _p(x), None, _p(alpha), _p(delta), _p(zp), _p(y)
-        sg.rows, sg.row_len, sg.per_row, sg.n_levels, sg.soft, sg.reg_weight = rows, rl, per_row, n_levels, int(bool(soft)), 0.0
+    segs, outs, keep = _ada_segs([(x, None, alpha, delta, zp, n_levels, 0.0, soft)
+                                  for x, alpha, delta, zp, n_levels, soft in items], "x", absent=("gy",))
     L.check(L.lib().nq_adaround_forward_multi(segs, len(items), _stream()), "adaround_forward_multi")
     return outs
 
 
 def uaq_forward_multi(items):
     """items: [(x, delta, zp, n_levels)] -> [UAQ fake-quantised tensors], ONE launch (same arithmetic as uaq_forward)."""
-    segs = (L.AdaSeg * len(items))()
-    outs = []
-    for sg, (x, delta, zp, n_levels) in zip(segs, items):
-        x, delta, zp = _dev(x), _dev(delta), _dev(zp)
-        rows, rl, per_row = _rows(x, delta)
-        y = torch.empty_like(x)
-        outs.append(y)
-        sg.x, sg.gy, sg.alpha, sg.delta, sg.zp, sg.out = _p(x), None, None, _p(delta), _p(zp), _p(y)
-        sg.rows, sg.row_len, sg.per_row, sg.n_levels, sg.soft, sg.reg_weight = rows, rl, per_row, n_levels, 0, 0.0
+    segs, outs, keep = _ada_segs([(x, None, None, delta, zp, n_levels, 0.0, 0) for x, delta, zp, n_levels in items], "x",
+                                 absent=("gy", "alpha"))
     L.check(L.lib().nq_uaq_forward_multi(segs, len(items), _stream()), "uaq_forward_multi")
     return outs
 
 
 def uaq_backward_multi(items):
     """items: [(x, gy, delta, zp, n_levels)] -> [d(delta)], ONE launch (same arithmetic and summation order as uaq_backward)."""
-    segs = (L.AdaSeg * len(items))()
-    outs, keep = [], []
-    for sg, (x, gy, delta, zp, n_levels) in zip(segs, items):
-        x, gy, delta, zp = _dev(x), _dev(gy), _dev(delta), _dev(zp)
-        rows, rl, per_row = _rows(x, delta)
-        dd = torch.empty_like(delta)
-        outs.append(dd)
-        keep.append((x, gy))
-        sg.x, sg.gy, sg.alpha, sg.delta, sg.zp, sg.out = _p(x), _p(gy), None, _p(delta), _p(zp), _p(dd)
-        sg.rows, sg.row_len, sg.per_row, sg.n_levels, sg.soft, sg.reg_weight = rows, rl, per_row, n_levels, 0, 0.0
+    segs, outs, keep = _ada_segs([(x, gy, None, delta, zp, n_levels, 0.0, 0) for x, gy, delta, zp, n_levels in items], "delta",
+                                 absent=("alpha",))
     L.check(L.lib().nq_uaq_backward_multi(segs, len(items), _stream()), "uaq_backward_multi")
     return outs
 
@@ -256,15 +258,7 @@ def adaround_backward_multi(items, reg_b=0.0, dyn=None):
     """items: [(x, gy, alpha, delta, zp, n_levels, reg_weight)] -> [d(alpha)] (+ regulariser gradient where
     reg_weight != 0), ONE launch.  dyn (device floats {reg_b, gate, ...} of the current step) replaces the host reg_b and
     gates reg_weight (captured iterations; same arithmetic)."""
-    segs = (L.AdaSeg * len(items))()
-    outs = []
-    for sg, (x, gy, alpha, delta, zp, n_levels, reg_weight) in zip(segs, items):
-        x, gy, alpha, delta, zp = _dev(x), _dev(gy), _dev(alpha), _dev(delta), _dev(zp)
-        rows, rl, per_row = _rows(x, delta)
-        da = torch.empty_like(alpha)
-        outs.append(da)
-        sg.x, sg.gy, sg.alpha, sg.delta, sg.zp, sg.out = _p(x), _p(gy), _p(alpha), _p(delta), _p(zp), _p(da)
-        sg.rows, sg.row_len, sg.per_row, sg.n_levels, sg.soft, sg.reg_weight = rows, rl, per_row, n_levels, 1, float(reg_weight)
+    segs, outs, keep = _ada_segs([tuple(it) + (1,) for it in items], "alpha")
     if dyn is not None:
         L.check(L.lib().nq_adaround_backward_multi_dyn(segs, len(items), _p(dyn), _stream()), "adaround_backward_multi_dyn")
     else:
@@ -278,16 +272,9 @@ def adaround_adam_multi(items, opt, reg_b=0.0, dyn=None, beta1=0.9, beta2=0.999,
     followed by opt.step (tested); d(alpha) itself is not materialised."""
     assert len(items) == len(opt.params)
     opt.t += 1
-    segs = (L.AdaAdamSeg * len(items))()
-    keep = []
-    for i, (sg, (x, gy, alpha, delta, zp, n_levels, reg_weight)) in enumerate(zip(segs, items)):
-        x, gy, alpha, delta, zp = _dev(x), _dev(gy), _dev(alpha), _dev(delta), _dev(zp)
-        if alpha.data_ptr() != opt.params[i].data_ptr():
-            raise RuntimeError("adaround_adam_multi: items must be in the optimiser's parameter order")
-        rows, rl, per_row = _rows(x, delta)
-        keep.append((x, gy))
-        sg.x, sg.gy, sg.alpha, sg.delta, sg.zp, sg.m, sg.v = _p(x), _p(gy), _p(alpha), _p(delta), _p(zp), _p(opt.m[i]), _p(opt.v[i])
-        sg.rows, sg.row_len, sg.per_row, sg.n_levels, sg.reg_weight = rows, rl, per_row, n_levels, float(reg_weight)
+    segs, _, keep = _ada_segs([tuple(it) + (1,) for it in items], opt=opt)
+    if any(t["alpha"].data_ptr() != p.data_ptr() for t, p in zip(keep, opt.params)):
+        raise RuntimeError("adaround_adam_multi: items must be in the optimiser's parameter order")
     step_size, bc2_sqrt = opt.scalars(opt.t, beta1, beta2)
     L.check(L.lib().nq_adaround_adam_multi(segs, len(items), float(reg_b), step_size, beta1, beta2, eps, bc2_sqrt, _p(dyn),
                                            _stream()), "adaround_adam_multi")
@@ -526,24 +513,12 @@ def conv_operand_dims(cin, cout, k):
     return kr.value, ld.value
 
 
-def weight_layouts(w, need_bwd):
-    """-> (wt_fwd, dims_fwd, wt_bwd | None, dims_bwd | None) GEMM operands of an OIHW weight."""
-    w = _dev(w)
-    cout, cin, k, _ = w.shape
-    kf, lf = conv_operand_dims(cin, cout, k)
-    wt = torch.empty(kf * lf, device=w.device, dtype=torch.float32)
-    wb, kb, lb = None, 0, 0
-    if need_bwd:
-        kb, lb = conv_operand_dims(cout, cin, k)
-        wb = torch.empty(kb * lb, device=w.device, dtype=torch.float32)
-    L.check(L.lib().nq_weight_layouts(_p(w), _p(wt), _p(wb), cout, cin, k, kf, lf, kb, lb, _stream()), "weight_layouts")
-    return wt, (kf, lf), wb, (kb, lb)
-
-
-def weight_layouts_multi(items):
-    """items: [(w, need_fwd, need_bwd)] -> [(wt_fwd | None, dims_fwd, wt_bwd | None, dims_bwd)] as weight_layouts, ONE launch."""
+def _wl_segs(items):
+    """items: [(w, need_fwd, need_bwd)] -> (WLSeg array, [(wt_fwd | None, dims_fwd, wt_bwd | None, dims_bwd)], temporaries): the
+    fp32 GEMM operand buffers of OIHW weights, allocated, and the segments that fill them.  The temporaries (the contiguous
+    weights the segments point to) stay alive in the wrapper's local past its launch call."""
     segs = (L.WLSeg * len(items))()
-    outs = []
+    outs, keep = [], []
     for sg, (w, need_fwd, need_bwd) in zip(segs, items):
         w = _dev(w)
         cout, cin, k, _ = w.shape
@@ -558,6 +533,36 @@ def weight_layouts_multi(items):
         sg.w, sg.wt_fwd, sg.wt_bwd, sg.Cout, sg.Cin, sg.k = _p(w), _p(wt), _p(wb), cout, cin, k
         sg.krows_fwd, sg.ld_fwd, sg.krows_bwd, sg.ld_bwd = kf, lf, kb, lb
         outs.append((wt, (kf, lf), wb, (kb, lb)))
+        keep.append(w)
+    return segs, outs, keep
+
+
+def _wl3_segs(items):
+    """items: [(w, transposed)] -> (WL3Seg array, [operand buffers], temporaries): as _wl_segs for the pre-split (bf16 hi / lo)
+    operands of the bf16x3 kernels; transposed -> operand of the data gradient."""
+    segs = (L.WL3Seg * len(items))()
+    outs, keep = [], []
+    for sg, (w, transposed) in zip(segs, items):
+        w = _dev(w)
+        cw_out, cw_in, k, _ = w.shape
+        cin, cout = (cw_out, cw_in) if transposed else (cw_in, cw_out)
+        outs.append(torch.empty(_q("nq_conv3_weight_bytes", cin, cout, k), device=w.device, dtype=torch.uint8))
+        sg.w, sg.wt3, sg.Cin, sg.Cout, sg.k, sg.transposed = _p(w), _p(outs[-1]), cin, cout, k, int(bool(transposed))
+        keep.append(w)
+    return segs, outs, keep
+
+
+def weight_layouts(w, need_bwd):
+    """-> (wt_fwd, dims_fwd, wt_bwd | None, dims_bwd | None) GEMM operands of an OIHW weight."""
+    (sg,), (out,), (w,) = _wl_segs([(w, True, need_bwd)])
+    L.check(L.lib().nq_weight_layouts(_p(w), _p(out[0]), _p(out[2]), sg.Cout, sg.Cin, sg.k, sg.krows_fwd, sg.ld_fwd, sg.krows_bwd,
+                                      sg.ld_bwd, _stream()), "weight_layouts")
+    return out
+
+
+def weight_layouts_multi(items):
+    """items: [(w, need_fwd, need_bwd)] -> [(wt_fwd | None, dims_fwd, wt_bwd | None, dims_bwd)] as weight_layouts, ONE launch."""
+    segs, outs, keep = _wl_segs(items)
     if items:
         L.check(L.lib().nq_weight_layouts_multi(segs, len(items), _stream()), "weight_layouts_multi")
     return outs
@@ -567,40 +572,16 @@ def weight_layouts_all(items3, items_f):
     """weight_layout3_multi(items3) and weight_layouts_multi(items_f) in ONE launch (nq_weight_layouts_all; same bytes)."""
     if not items3 or not items_f or os.environ.get("NQ_LAYOUTS_ALL", "1") == "0":
         return weight_layout3_multi(items3), weight_layouts_multi(items_f)
-    segs3 = (L.WL3Seg * len(items3))()
-    outs3 = []
-    for sg, (w, transposed) in zip(segs3, items3):
-        w = _dev(w)
-        cw_out, cw_in, k, _ = w.shape
-        cin, cout = (cw_out, cw_in) if transposed else (cw_in, cw_out)
-        buf = torch.empty(_q("nq_conv3_weight_bytes", cin, cout, k), device=w.device, dtype=torch.uint8)
-        outs3.append(buf)
-        sg.w, sg.wt3, sg.Cin, sg.Cout, sg.k, sg.transposed = _p(w), _p(buf), cin, cout, k, int(bool(transposed))
-    segsf = (L.WLSeg * len(items_f))()
-    outsf = []
-    for sg, (w, need_fwd, need_bwd) in zip(segsf, items_f):
-        w = _dev(w)
-        cout, cin, k, _ = w.shape
-        wt = wb = None
-        kf = lf = kb = lb = 0
-        if need_fwd:
-            kf, lf = conv_operand_dims(cin, cout, k)
-            wt = torch.empty(kf * lf, device=w.device, dtype=torch.float32)
-        if need_bwd:
-            kb, lb = conv_operand_dims(cout, cin, k)
-            wb = torch.empty(kb * lb, device=w.device, dtype=torch.float32)
-        sg.w, sg.wt_fwd, sg.wt_bwd, sg.Cout, sg.Cin, sg.k = _p(w), _p(wt), _p(wb), cout, cin, k
-        sg.krows_fwd, sg.ld_fwd, sg.krows_bwd, sg.ld_bwd = kf, lf, kb, lb
-        outsf.append((wt, (kf, lf), wb, (kb, lb)))
+    segs3, outs3, keep3 = _wl3_segs(items3)
+    segsf, outsf, keepf = _wl_segs(items_f)
     L.check(L.lib().nq_weight_layouts_all(segs3, len(items3), segsf, len(items_f), _stream()), "weight_layouts_all")
     return outs3, outsf
 
 
-def conv_forward_raw(x, wt, dims, bias, cout, k, epilogue, r, in_gelu=False, zprev=None, fmt=0):
-    """One nq_conv_forward launch.  Returns (y, z): z = shuffled pre-activation for the PixelShuffle epilogues
-    (y is None for EPI_PS), y = un-shuffled gradient for EPI_DGRAD_GELU.  fmt = EPI_Y_SPLIT: y as split {hi | lo} words
-    (conv_split_out says where)."""
-    B, cin, H, W = x.shape
+def _conv_outputs(x, cout, epilogue, r):
+    """(y, z) of a convolution launch on x with this epilogue, allocated: z = shuffled pre-activation of the PixelShuffle
+    epilogues (y is None for EPI_PS), y = un-shuffled gradient for EPI_DGRAD_GELU."""
+    B, _, H, W = x.shape
     y = z = None
     if epilogue in (EPI_PS_GELU, EPI_PS):
         z = torch.empty((B, cout // (r * r), H * r, W * r), device=x.device, dtype=torch.float32)
@@ -610,12 +591,19 @@ def conv_forward_raw(x, wt, dims, bias, cout, k, epilogue, r, in_gelu=False, zpr
         y = torch.empty((B, cout * r * r, H // r, W // r), device=x.device, dtype=torch.float32)
     else:
         y = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32)
+    return y, z
+
+
+def conv_forward_raw(x, wt, dims, bias, cout, k, epilogue, r, zprev=None, fmt=0):
+    """One nq_conv_forward launch.  Returns (y, z) as _conv_outputs describes them.  fmt = EPI_Y_SPLIT: y as split {hi | lo}
+    words (conv_split_out says where).  The kernels' GELU-on-load option is not offered here (nothing uses it)."""
+    B, cin, H, W = x.shape
+    y, z = _conv_outputs(x, cout, epilogue, r)
     nws = _q("nq_conv_forward_ws_floats", B, cin, H, W, cout, k)
     ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws else None
     _timed(("conv_igemm", k, cin, cout, H, W, B, epilogue),
            lambda: L.check(L.lib().nq_conv_forward(_p(x), _p(wt), _p(bias), _p(y), _p(z), _p(ws), B, cin, H, W, cout, k,
-                                                   dims[0], dims[1], r, epilogue | fmt, 1 if in_gelu else 0, _p(zprev),
-                                                   _stream()), "conv_forward"))
+                                                   dims[0], dims[1], r, epilogue | fmt, 0, _p(zprev), _stream()), "conv_forward"))
     return y, z
 
 
@@ -648,25 +636,14 @@ def split_words(x):
 
 def weight_layout3(w, transposed=False):
     """pre-split (bf16 hi/lo) operand of the bf16x3 conv kernels; transposed=True -> operand of the data gradient."""
-    w = _dev(w)
-    cw_out, cw_in, k, _ = w.shape
-    cin, cout = (cw_out, cw_in) if transposed else (cw_in, cw_out)
-    buf = torch.empty(_q("nq_conv3_weight_bytes", cin, cout, k), device=w.device, dtype=torch.uint8)
-    L.check(L.lib().nq_weight_layout3(_p(w), _p(buf), cin, cout, k, 1 if transposed else 0, _stream()), "weight_layout3")
+    (sg,), (buf,), (w,) = _wl3_segs([(w, transposed)])
+    L.check(L.lib().nq_weight_layout3(_p(w), _p(buf), sg.Cin, sg.Cout, sg.k, sg.transposed, _stream()), "weight_layout3")
     return buf
 
 
 def weight_layout3_multi(items):
     """items: [(w, transposed)] -> [operand buffers], ONE launch (same bytes as weight_layout3 per item)."""
-    segs = (L.WL3Seg * len(items))()
-    outs = []
-    for sg, (w, transposed) in zip(segs, items):
-        w = _dev(w)
-        cw_out, cw_in, k, _ = w.shape
-        cin, cout = (cw_out, cw_in) if transposed else (cw_in, cw_out)
-        buf = torch.empty(_q("nq_conv3_weight_bytes", cin, cout, k), device=w.device, dtype=torch.uint8)
-        outs.append(buf)
-        sg.w, sg.wt3, sg.Cin, sg.Cout, sg.k, sg.transposed = _p(w), _p(buf), cin, cout, k, int(bool(transposed))
+    segs, outs, keep = _wl3_segs(items)
     if items:
         L.check(L.lib().nq_weight_layout3_multi(segs, len(items), _stream()), "weight_layout3_multi")
     return outs
@@ -676,15 +653,7 @@ def conv3_forward_raw(x, wt3, bias, cout, k, epilogue, r, zprev=None, fmt=0):
     """bf16x3 counterpart of conv_forward_raw (same outputs).  fmt: EPI_X_SPLIT (x holds split words) | EPI_Y_SPLIT (y is
     written as split words), where conv3_split_io allows."""
     B, cin, H, W = x.shape
-    y = z = None
-    if epilogue in (EPI_PS_GELU, EPI_PS):
-        z = torch.empty((B, cout // (r * r), H * r, W * r), device=x.device, dtype=torch.float32)
-        if epilogue == EPI_PS_GELU:
-            y = torch.empty_like(z)
-    elif epilogue == EPI_DGRAD_GELU:
-        y = torch.empty((B, cout * r * r, H // r, W // r), device=x.device, dtype=torch.float32)
-    else:
-        y = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32)
+    y, z = _conv_outputs(x, cout, epilogue, r)
     nws = _q("nq_conv_forward3_ws_floats", B, cin, H, W, cout, k)
     ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws else None
     _timed(("conv_igemm3", k, cin, cout, H, W, B, epilogue),
@@ -783,7 +752,8 @@ def conv_wgrad_swapped3(x, dy, cout, k, want_db, out=None, defer=None):
     return dw, db
 
 
-def conv_wgrad_raw(x, dy, cout, k, want_db, x_gelu=False, out=None, defer=None):
+def conv_wgrad_raw(x, dy, cout, k, want_db, out=None, defer=None):
+    """fp32 weight (and bias) gradient; out / defer as conv_wgrad3_raw.  The kernels' GELU-on-load option is passed as 0."""
     B, cin, H, W = x.shape
     ws = torch.empty(_q("nq_conv_wgrad_ws_floats", B, cin, H, W, cout, k), device=x.device, dtype=torch.float32)
     dw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32) if out is None else out[0]
@@ -792,12 +762,12 @@ def conv_wgrad_raw(x, dy, cout, k, want_db, x_gelu=False, out=None, defer=None):
         seg = L.WgrSeg()
         _timed(("conv_wgrad", k, cin, cout, H, W, B, 0),
                lambda: L.check(L.lib().nq_conv_wgrad_slabs(_p(x), _p(dy), _p(dw), _p(db), _p(ws), B, cin, H, W, cout, k,
-                                                           1 if x_gelu else 0, ctypes.byref(seg), _stream()), "conv_wgrad_slabs"))
+                                                           0, ctypes.byref(seg), _stream()), "conv_wgrad_slabs"))
         defer.add(seg, ws, dw, db)
         return dw, db
     _timed(("conv_wgrad", k, cin, cout, H, W, B, 0),
            lambda: L.check(L.lib().nq_conv_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(ws), B, cin, H, W, cout, k,
-                                                 1 if x_gelu else 0, _stream()), "conv_wgrad"))
+                                                 0, _stream()), "conv_wgrad"))
     return dw, db
 
 
@@ -1256,8 +1226,88 @@ def _side_stream(device):
     return _SIDE_STREAMS[key]
 
 
+class LayerPlan:
+    """Everything the three launches of one decoder layer need, decided by plan_decoder from shapes alone.  Routes are
+    "bf16x3" | "fp32", the weight gradient's also "swapped3", the data gradient's None where no launch happens (layer 0
+    unless the embedding is trained).  H, W: the layer's INPUT size.  `dgrad` is the launch that turns this layer's
+    conv-output gradient into the one of the layer below (layer 0: into d(embedding)), on this layer's transposed weight.
+    The weight operands follow from the routes: the pre-split operand / its transposed form where fwd / dgrad is "bf16x3",
+    the fp32 forward / backward operand where it is "fp32"."""
+    __slots__ = ("k", "r", "act", "cin", "cout", "has_bias", "H", "W", "epi", "fwd", "dgrad", "wgrad", "x_split", "g_split",
+                 "fwd_fmt", "dgrad_epi", "dgrad_r", "dgrad_fmt", "wgrad_fmt")
+
+
+def plan_decoder(spec, wshapes, has_bias, B, H, W, want_emb_grad):
+    """The launch plan of one decoder forward + backward: one LayerPlan per layer.  wshapes: [(cout, cin)], has_bias: [bool]
+    per layer; B, H, W: the embedding's batch and spatial size.  A pure host function: no tensors, no GPU, only the library's
+    memoised shape queries; spec.precision and NQ_SPLIT_IO are read at call time.
+
+    _DecoderStackFn.forward calls it once per forward and stores the result on the node; the backward pass routes by that
+    stored plan and asks the library nothing.  So a spec.precision edited between a node's forward and its backward does
+    not re-route that node's weight gradients (nothing does that)."""
+    n = len(spec.layers)
+    use3 = spec.precision == "bf16x3"
+    plan = []
+    fio, bio, wio = [0] * n, [0] * n, [0] * n   # split {hi | lo} word capabilities: forward / data gradient / weight gradient
+    for l, (k, r, act) in enumerate(spec.layers):
+        p = LayerPlan()
+        p.k, p.r, p.act, (p.cout, p.cin), p.has_bias, p.H, p.W = k, r, act, wshapes[l], bool(has_bias[l]), H, W
+        cout, cin = p.cout, p.cin
+        if l == n - 1:
+            p.epi = EPI_TANH if spec.tanh_out else EPI_PLAIN
+        else:
+            p.epi = EPI_PS_GELU if act else EPI_PS if r > 1 else EPI_PLAIN
+        p.fwd = "bf16x3" if use3 and conv3_supported(B, cin, H, W, cout, k) else "fp32"
+        # layer 0's data gradient is only needed when the embedding itself is trained (FP32 trainer: the ConvNeXt encoder
+        # sits below it, reference regress.py:259-266), and then stays on the fp32 kernel
+        if l == 0:
+            p.dgrad = "fp32" if want_emb_grad else None
+        else:
+            p.dgrad = "bf16x3" if use3 and conv3_supported(B, cout, H, W, cin, k) else "fp32"
+        if use3 and conv_wgrad3_supported(B, cin, H, W, cout, k):
+            p.wgrad = "bf16x3"
+        elif use3 and conv_wgrad_swapped3_supported(B, cin, H, W, cout, k):
+            p.wgrad = "swapped3"
+        else:
+            p.wgrad = "fp32"
+        if p.fwd == "bf16x3":
+            fio[l] = conv3_split_io(B, cin, H, W, cout, k)
+        if p.dgrad == "bf16x3":
+            bio[l] = conv3_split_io(B, cout, H, W, cin, k)
+        if p.wgrad == "bf16x3":
+            wio[l] = conv_wgrad3_split_io(B, cin, H, W, cout, k)
+        below_act = l > 0 and spec.layers[l - 1][2]
+        p.dgrad_epi, p.dgrad_r = (EPI_DGRAD_GELU, spec.layers[l - 1][1]) if below_act else (EPI_PLAIN, 1)
+        # the head's data gradient (streaming vector kernel) can write split words
+        if l == n - 1 and l > 0 and p.dgrad == "fp32" and below_act \
+                and conv_split_out(B, cout, H, W, cin, k, p.dgrad_r, EPI_DGRAD_GELU):
+            bio[l] = EPI_Y_SPLIT
+        plan.append(p)
+        if l == 0:
+            H, W = H * spec.fc_hw[0], W * spec.fc_hw[1]
+        H, W = H * r, W * r
+    # Which tensors travel as split {hi | lo} words (NQ_SPLIT_IO=0: none): the input x_l of layer l (l >= 2: written by the
+    # GELU epilogue of layer l - 1, read by layer l's forward patch staging and by its weight gradient) and the conv-output
+    # gradient g_l (written by the data gradient of layer l + 1, read by layer l's weight gradient and data gradient) --
+    # where EVERY kernel on both sides takes / writes that form.  Same values in the matrix pipe: identical results.
+    split_on = use3 and os.environ.get("NQ_SPLIT_IO", "1") != "0"
+    for l, p in enumerate(plan):
+        below_act = l > 0 and plan[l - 1].act
+        p.x_split = bool(split_on and l >= 2 and below_act and (fio[l - 1] & EPI_Y_SPLIT) and (fio[l] & EPI_X_SPLIT)
+                         and (wio[l] & 1))
+        p.g_split = bool(split_on and 1 <= l < n - 1 and (bio[l + 1] & EPI_Y_SPLIT) and (bio[l] & EPI_X_SPLIT) and (wio[l] & 2)
+                         and below_act and not (l == 1 and spec.fc_hw != (1, 1)))
+    # the fmt words of the launches: a side is split only where a bf16x3 kernel reads it (x_split / g_split imply that route)
+    for l, p in enumerate(plan):
+        p.fwd_fmt = (EPI_X_SPLIT if p.x_split else 0) | (EPI_Y_SPLIT if l + 1 < n and plan[l + 1].x_split else 0)
+        p.dgrad_fmt = (EPI_X_SPLIT if p.g_split else 0) | (EPI_Y_SPLIT if l > 0 and plan[l - 1].g_split else 0)
+        p.wgrad_fmt = (1 if p.x_split else 0) | (2 if p.g_split else 0)
+    return plan
+
+
 class _DecoderStackFn(Function):
-    """Whole decoder (reference HNeRV.py:49-71 / NeRV.py:44-65) as ONE autograd node with an explicit schedule.
+    """Whole decoder (reference HNeRV.py:49-71 / NeRV.py:44-65) as ONE autograd node with an explicit schedule, the
+    LayerPlans of plan_decoder.
 
     Every block's conv epilogue writes a = gelu(PixelShuffle(conv+bias)) and d = gelu'(...) from one erf (EPI_PS_GELU);
     the data-gradient kernel of the layer above multiplies by d and un-shuffles in its epilogue (EPI_DGRAD_GELU).  So
@@ -1268,101 +1318,40 @@ class _DecoderStackFn(Function):
     def forward(ctx, emb, spec, *wb):
         x = _dev(emb, "embedding")
         n = len(spec.layers)
-        saved_in, saved_z, metas = [], [], []
-        in_gelu = False      # (kept in the metas for the generic kernels' GELU-on-load option; unused by this schedule)
+        Ws = [_dev(w, "weight") for w in wb[0::2]]
+        bs = [_dev(b, "bias") if b is not None else None for b in wb[1::2]]
+        plan = plan_decoder(spec, [tuple(W.shape[:2]) for W in Ws], [b is not None for b in bs], x.shape[0], x.shape[2],
+                            x.shape[3], ctx.needs_input_grad[0])
+        # every weight operand of the node, pre-split (bf16x3 routes) and fp32 (the others), is built by ONE launch before
+        # the first convolution
+        keys3 = [(l, t) for l, p in enumerate(plan) for t, route in ((False, p.fwd), (True, p.dgrad)) if route == "bf16x3"]
+        keys32 = [l for l, p in enumerate(plan) if "fp32" in (p.fwd, p.dgrad)]
+        ops3, ops32 = weight_layouts_all([(Ws[l], t) for l, t in keys3],
+                                         [(Ws[l], plan[l].fwd == "fp32", plan[l].dgrad == "fp32") for l in keys32])
+        ops3, ops32 = dict(zip(keys3, ops3)), dict(zip(keys32, ops32))
+        saved_in, saved_z = [], []
+        ctx.wbk, ctx.dims_b, ctx.w3t = [None] * n, [None] * n, [None] * n   # the data gradients' operands, per layer
         zprev = None         # gelu'(pre-activation) behind x, saved by the producing epilogue
-        # pre-pass over the static shapes: which layers run on the bf16x3 kernels (forward / data gradient); all their
-        # pre-split operands are then built by ONE launch before the first convolution
-        Bx, Hx, Wx = x.shape[0], x.shape[2], x.shape[3]
-        plan, items = [], []
-        fio, bio, wio = [0] * n, [0] * n, [0] * n   # split {hi | lo} word capabilities: forward / data gradient / weight gradient
-        for l, (k, r, act) in enumerate(spec.layers):
-            W = _dev(wb[2 * l], "weight")
-            cout, cin = W.shape[0], W.shape[1]
-            use3 = spec.precision == "bf16x3" and conv3_supported(Bx, cin, Hx, Wx, cout, k)
-            use3_bwd = spec.precision == "bf16x3" and l > 0 and conv3_supported(Bx, cout, Hx, Wx, cin, k)
-            plan.append((use3, use3_bwd, len(items) if use3 else -1, len(items) + int(use3) if use3_bwd else -1))
-            if use3:
-                items.append((W, False))
-                fio[l] = conv3_split_io(Bx, cin, Hx, Wx, cout, k)
-            if use3_bwd:
-                items.append((W, True))
-                bio[l] = conv3_split_io(Bx, cout, Hx, Wx, cin, k)
-            if spec.precision == "bf16x3" and conv_wgrad3_supported(Bx, cin, Hx, Wx, cout, k):
-                wio[l] = conv_wgrad3_split_io(Bx, cin, Hx, Wx, cout, k)
-            if l == n - 1 and l > 0 and not use3_bwd:   # the head's data gradient (streaming vector kernel) can write split words
-                kp, rp, actp = spec.layers[l - 1]
-                if actp and conv_split_out(Bx, cout, Hx, Wx, cin, k, rp, EPI_DGRAD_GELU):
-                    bio[l] = EPI_Y_SPLIT
-            if l == 0:
-                Hx, Wx = Hx * spec.fc_hw[0], Wx * spec.fc_hw[1]
-            Hx, Wx = Hx * r, Wx * r
-        # Which tensors travel as split {hi | lo} words (round 4; NQ_SPLIT_IO=0: none): the input x_l of layer l (l >= 2: written by
-        # the GELU epilogue of layer l - 1, read by layer l's forward patch staging and by its weight gradient) and the conv-output
-        # gradient g_l (written by the data gradient of layer l + 1, read by layer l's weight gradient and data gradient) --
-        # where EVERY kernel on both sides takes / writes that form.  Same values in the matrix pipe: identical results.
-        split_on = spec.precision == "bf16x3" and os.environ.get("NQ_SPLIT_IO", "1") != "0"
-        xsp, gsp = [False] * n, [False] * n
-        if split_on:
-            for l in range(2, n):
-                xsp[l] = bool(spec.layers[l - 1][2] and (fio[l - 1] & EPI_Y_SPLIT) and (fio[l] & EPI_X_SPLIT) and (wio[l] & 1))
-            for l in range(1, n - 1):
-                gsp[l] = bool((bio[l + 1] & EPI_Y_SPLIT) and (bio[l] & EPI_X_SPLIT) and (wio[l] & 2) and spec.layers[l - 1][2]
-                              and not (l == 1 and spec.fc_hw != (1, 1)))
-        # the fp32 operands (layers / directions that stay on the fp32 kernels) come from the SAME launch (round 4).
-        # layer 0's data-gradient operand is only needed when the embedding itself is trained (FP32 trainer: the
-        # ConvNeXt encoder sits below it, reference regress.py:259-266)
-        need_bs = [(l > 0 and not plan[l][1]) or (l == 0 and ctx.needs_input_grad[0]) for l in range(n)]
-        fp32_items = [(_dev(wb[2 * l], "weight"), not plan[l][0], need_bs[l]) for l in range(n)
-                      if (not plan[l][0]) or need_bs[l]]
-        operands, fp32_list = weight_layouts_all(items, fp32_items)
-        fp32_ops = iter(fp32_list)
-        for l, (k, r, act) in enumerate(spec.layers):
-            W = _dev(wb[2 * l], "weight")
-            b = _dev(wb[2 * l + 1], "bias") if wb[2 * l + 1] is not None else None
-            cout, cin = W.shape[0], W.shape[1]
-            use3, use3_bwd, i_f, i_b = plan[l]
-            need_b = need_bs[l]
-            wt = dims = wbk = dims_b = None
-            if use3:
-                wt3 = operands[i_f]
-            if (not use3) or need_b:
-                wt, dims, wbk, dims_b = next(fp32_ops)
-                if not need_b:
-                    wbk = dims_b = None
-            last = l == n - 1
-            if last:
-                epi = EPI_TANH if spec.tanh_out else EPI_PLAIN
-            elif act:
-                epi = EPI_PS_GELU
-            elif r > 1:
-                epi = EPI_PS
-            else:
-                epi = EPI_PLAIN
-            fused_loss = None
-            if last and epi == EPI_TANH and not use3 and getattr(_LOSS_TLS, "req", None) is not None:
-                tgt_, cache_, idx_ = _LOSS_TLS.req
-                fused_loss = head_forward_loss_raw(x, wt, dims, b, cout, k, tgt_, cache_, idx_)
+        fused_loss = None
+        for l, p in enumerate(plan):
+            wt, dims, wbk, dims_b = ops32.get(l, (None,) * 4)
+            if p.dgrad == "fp32":
+                ctx.wbk[l], ctx.dims_b[l] = wbk, dims_b
+            ctx.w3t[l] = ops3.get((l, True))
+            if l == n - 1 and p.epi == EPI_TANH and p.fwd == "fp32" and getattr(_LOSS_TLS, "req", None) is not None:
+                fused_loss = head_forward_loss_raw(x, wt, dims, bs[l], p.cout, p.k, *_LOSS_TLS.req)
             if fused_loss is not None:
                 y, z = fused_loss[0], None
-            elif use3:
-                y, z = conv3_forward_raw(x, wt3, b, cout, k, epi, r,
-                                         fmt=(EPI_X_SPLIT if xsp[l] else 0) | (EPI_Y_SPLIT if l + 1 < n and xsp[l + 1] else 0))
+            elif p.fwd == "bf16x3":
+                y, z = conv3_forward_raw(x, ops3[l, False], bs[l], p.cout, p.k, p.epi, p.r, fmt=p.fwd_fmt)
             else:
-                y, z = conv_forward_raw(x, wt, dims, b, cout, k, epi, r, in_gelu=in_gelu)
+                y, z = conv_forward_raw(x, wt, dims, bs[l], p.cout, p.k, p.epi, p.r)
             saved_in.append(x)
             saved_z.append(zprev)
-            metas.append((k, r, act, cout, cin, in_gelu, wbk, dims_b, b is not None, operands[i_b] if use3_bwd else None,
-                          xsp[l], gsp[l]))
-            if epi == EPI_PS_GELU:
-                x, zprev, in_gelu = y, z, False
-            elif epi == EPI_PS:
-                x, zprev, in_gelu = z, None, False
-            else:
-                x, zprev, in_gelu = y, None, False
+            x, zprev = (y, z) if p.epi == EPI_PS_GELU else (z, None) if p.epi == EPI_PS else (y, None)
             if l == 0 and spec.fc_hw != (1, 1):
                 x = _space_from_channels(x, *spec.fc_hw).contiguous()
-        ctx.spec, ctx.metas, ctx.n = spec, metas, n
+        ctx.spec, ctx.plan, ctx.n = spec, plan, n
         ctx.save_for_backward(x, *saved_in, *saved_z)
         # per-node state (reachable from outside as img.grad_fn.<name>): the data-parallel hook installed on this thread
         # when the forward ran, whether backward handed the arena to it, and the hand-over slot of the fused loss tail
@@ -1393,8 +1382,9 @@ def _decoder_backward_steps(ctx, g_img):
     arena is complete and must be exchanged between data-parallel ranks (last = None: the whole arena at once), and
     returns the gradient tuple of _DecoderStackFn.backward.  The autograd node drives it and calls the installed hook at
     every yield; the captured data-parallel iteration (quantization/calib_model.py) drives it stage by stage, with the
-    collectives launched eagerly between three replayed graphs."""
-    spec, metas, n = ctx.spec, ctx.metas, ctx.n
+    collectives launched eagerly between three replayed graphs.  Every route and flag comes from the plan the forward
+    stored (ctx.plan); no support query is made here."""
+    spec, plan, n = ctx.spec, ctx.plan, ctx.n
     saved = ctx.saved_tensors
     img, xs, zs = saved[0], saved[1:1 + n], saved[1 + n:]
     d_emb = None
@@ -1433,14 +1423,12 @@ def _decoder_backward_steps(ctx, g_img):
     arena_hook, arena_two_phase = ctx.nq_arena
     if arena_hook is not None:
         sizes = []
-        for l in range(n):
-            k, r, act, cout, cin = metas[l][:5]
-            sizes += [cout * cin * k * k, cout if metas[l][8] else 0]
+        for p in plan:
+            sizes += [p.cout * p.cin * p.k * p.k, p.cout if p.has_bias else 0]
         arena = torch.empty(sum(sizes), device=g.device, dtype=torch.float32)
         views, off = [], 0
-        for l in range(n):
-            k, r, act, cout, cin = metas[l][:5]
-            wv = arena[off:off + sizes[2 * l]].view(cout, cin, k, k)
+        for l, p in enumerate(plan):
+            wv = arena[off:off + sizes[2 * l]].view(p.cout, p.cin, p.k, p.k)
             off += sizes[2 * l]
             bv = arena[off:off + sizes[2 * l + 1]] if sizes[2 * l + 1] else None
             off += sizes[2 * l + 1]
@@ -1452,43 +1440,38 @@ def _decoder_backward_steps(ctx, g_img):
     pending = PendingReductions() if side is None and os.environ.get("NQ_DEFER_REDUCE", "1") != "0" else None
 
     def wgrad(l, dconv):
-        k, r, act, cout, cin, in_gelu, wbk, dims_b, has_b, W3, x_split, g_split = metas[l]
-        x_in = xs[l]
-        Bx, _, Hx, Wx = x_in.shape
+        p = plan[l]
         out = views[l] if views is not None else None
-        if spec.precision == "bf16x3" and not in_gelu and conv_wgrad3_supported(Bx, cin, Hx, Wx, cout, k):
-            return conv_wgrad3_raw(x_in, dconv, cout, k, has_b, out=out, defer=pending,
-                                   fmt=(1 if x_split else 0) | (2 if g_split else 0))
-        if spec.precision == "bf16x3" and not in_gelu and conv_wgrad_swapped3_supported(Bx, cin, Hx, Wx, cout, k):
-            if l == n - 1 and has_b and head_db is not None:   # bias gradient handed over by l2_loss_head_grad
-                dw, _ = conv_wgrad_swapped3(x_in, dconv, cout, k, False, out=out, defer=pending)
+        if p.wgrad == "bf16x3":
+            return conv_wgrad3_raw(xs[l], dconv, p.cout, p.k, p.has_bias, out=out, defer=pending, fmt=p.wgrad_fmt)
+        if p.wgrad == "swapped3":
+            if l == n - 1 and p.has_bias and head_db is not None:   # bias gradient handed over by l2_loss_head_grad
+                dw, _ = conv_wgrad_swapped3(xs[l], dconv, p.cout, p.k, False, out=out, defer=pending)
                 if out is not None:
                     out[1].copy_(head_db)
                     return dw, out[1]
                 return dw, head_db
-            return conv_wgrad_swapped3(x_in, dconv, cout, k, has_b, out=out, defer=pending)
-        return conv_wgrad_raw(x_in, dconv, cout, k, has_b, x_gelu=in_gelu, out=out, defer=pending)
+            return conv_wgrad_swapped3(xs[l], dconv, p.cout, p.k, p.has_bias, out=out, defer=pending)
+        return conv_wgrad_raw(xs[l], dconv, p.cout, p.k, p.has_bias, out=out, defer=pending)
 
     def dgrad(l, dconv):
         """conv-output gradient of layer l -> conv-output gradient of layer l - 1 (l >= 1)"""
-        k, r, act, cout, cin, in_gelu, wbk, dims_b, has_b, W3, x_split, g_split = metas[l]
-        kp, rp, actp = spec.layers[l - 1]
-        epi_b, r_b, zp = (EPI_DGRAD_GELU, rp, zs[l]) if actp else (EPI_PLAIN, 1, None)
-        if not actp and rp != 1:
+        p = plan[l]
+        if not plan[l - 1].act and plan[l - 1].r != 1:
             raise NotImplementedError("PixelShuffle without activation between decoder layers")
-        out_split = EPI_Y_SPLIT if metas[l - 1][11] else 0   # the gradient this call produces is layer l - 1's g
         # the layer below ends in GELU: d(pre-activation) = dgrad * gelu'(z), stored as ITS conv-output gradient
-        if W3 is not None:   # W3 = pre-built transposed operand
-            d, _ = conv3_forward_raw(dconv, W3, None, cin, k, epi_b, r_b, zprev=zp, fmt=(EPI_X_SPLIT if g_split else 0) | out_split)
+        zp = zs[l] if p.dgrad_epi == EPI_DGRAD_GELU else None
+        if p.dgrad == "bf16x3":
+            d, _ = conv3_forward_raw(dconv, ctx.w3t[l], None, p.cin, p.k, p.dgrad_epi, p.dgrad_r, zprev=zp, fmt=p.dgrad_fmt)
         else:
-            d, _ = conv_forward_raw(dconv, wbk, dims_b, None, cin, k, epi_b, r_b, zprev=zp, fmt=out_split)
-        if not actp and l == 1 and spec.fc_hw != (1, 1):
+            d, _ = conv_forward_raw(dconv, ctx.wbk[l], ctx.dims_b[l], None, p.cin, p.k, p.dgrad_epi, p.dgrad_r, zprev=zp,
+                                    fmt=p.dgrad_fmt)
+        if not plan[l - 1].act and l == 1 and spec.fc_hw != (1, 1):
             d = _channels_from_space(d, *spec.fc_hw).contiguous()
         return d
 
     def emb_grad(dconv):   # d(embedding): plain data gradient through layer 0 (no activation below it)
-        k, r, act, cout, cin, in_gelu, wbk, dims_b, has_b, W3 = metas[0][:10]
-        return conv_forward_raw(dconv, wbk, dims_b, None, cin, k, EPI_PLAIN, 1)[0]
+        return conv_forward_raw(dconv, ctx.wbk[0], ctx.dims_b[0], None, plan[0].cin, plan[0].k, EPI_PLAIN, 1)[0]
 
     if arena is not None and arena_two_phase and n > 1:
         # Data-parallel schedule: the data-gradient chain first, then the weight gradients of the deep layers (most
@@ -1499,9 +1482,9 @@ def _decoder_backward_steps(ctx, g_img):
         dcs[n - 1] = dconv
         for l in range(n - 1, 0, -1):
             dcs[l - 1] = dgrad(l, dcs[l])
-        if ctx.needs_input_grad[0]:
+        if plan[0].dgrad is not None:
             d_emb = emb_grad(dcs[0])
-        flops = [metas[l][3] * metas[l][4] * metas[l][0] ** 2 * xs[l].shape[2] * xs[l].shape[3] for l in range(n)]
+        flops = [p.cout * p.cin * p.k ** 2 * p.H * p.W for p in plan]
         split, late = n - 1, flops[n - 1]
         while split > 1 and late < 0.8 * sum(flops):
             split -= 1
@@ -1535,7 +1518,7 @@ def _decoder_backward_steps(ctx, g_img):
             dw, db = wgrad(l, dconv)
         grads[2 * l], grads[2 * l + 1] = dw, db
         if l == 0:
-            if ctx.needs_input_grad[0]:
+            if plan[0].dgrad is not None:
                 d_emb = emb_grad(dconv)
             break
         dconv = dgrad(l, dconv)
@@ -1548,8 +1531,6 @@ def _decoder_backward_steps(ctx, g_img):
         yield arena, None
         ctx.nq_arena_reduced = True
     return (d_emb, None) + tuple(grads)
-
-
 
 
 class _ManualNode:
