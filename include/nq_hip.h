@@ -40,6 +40,10 @@ typedef void* nq_stream_t; /* hipStream_t */
 #define NQ_ERR_UNSUPPORTED (-2) /* shape outside what the kernels are built for */
 #define NQ_ERR_LAUNCH (-3)      /* HIP reported a launch error */
 
+/* 6.  History: v4 added the fused launches marked "ABI v4" below, v5 the split {hi | lo} word interchange.  v6 only removed:
+ * the *_slabs / *_fmt weight-gradient entries (now the `seg` / `fmt` arguments of nq_conv_wgrad, nq_conv_wgrad3 and
+ * nq_conv_wgrad3_swapped), the GELU-on-load option of the fp32 kernels (in_gelu / x_gelu: nothing used it), and the
+ * "workspace of the exchanged problem > 4 floats" idiom (now nq_conv_wgrad3_swapped_ws_floats / _supported). */
 NQ_API int nq_abi_version(void);
 NQ_API const char* nq_error_string(int code);
 
@@ -258,11 +262,9 @@ NQ_API int nq_conv_operand_dims(int Cin, int Cout, int k, int* krows, int* ld);
 NQ_API int nq_split_words(const float* x, float* y, int64_t n, nq_stream_t stream);
 NQ_API int64_t nq_conv_forward_ws_floats(int B, int Cin, int H, int W, int Cout, int k);
 /* 1 when nq_conv_forward can write y as split words (NQ_EPI_Y_SPLIT) for this call: the streaming data gradient of the head */
-NQ_API int nq_conv_split_out(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int in_gelu, int has_bias);
-/* in_gelu != 0: x holds pre-activations and exact GELU is applied while the input tile is staged. */
+NQ_API int nq_conv_split_out(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int has_bias);
 NQ_API int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y, float* z, float* ws, int B, int Cin, int H,
-                    int W, int Cout, int k, int krows, int ld, int r, int epilogue, int in_gelu, const float* zprev,
-                    nq_stream_t stream);
+                    int W, int Cout, int k, int krows, int ld, int r, int epilogue, const float* zprev, nq_stream_t stream);
 
 /* ---- "bf16x3" variant of nq_conv_forward: fp32-equivalent accuracy on the BF16 matrix pipe ------------------------
  * Every fp32 operand is split into bf16 hi + lo and each product formed as hi*hi + hi*lo + lo*hi with fp32
@@ -294,43 +296,13 @@ NQ_API int nq_weight_layouts_all(const nq_wl3_seg* segs3, int n3, const nq_wl_se
 NQ_API int nq_conv_forward3(const float* x, const void* wt3, const float* bias, float* y, float* z, const float* zprev, float* ws, int B,
                      int Cin, int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream);
 
-/* bf16x3 variant of nq_conv_wgrad (same contract, x_gelu not offered): */
-NQ_API int nq_conv_wgrad3_supported(int B, int Cin, int H, int W, int Cout, int k);
-NQ_API int64_t nq_conv_wgrad3_ws_floats(int B, int Cin, int H, int W, int Cout, int k);
-/* The launch plan nq_conv_wgrad3 will use for this shape (pure host function): MT = 16*mi channels x NT = 64*ni columns per
- * workgroup, nsplit K-splits, pc != 0 -> the 8-wave producer/consumer kernel (32-bit buffer offsets: only for operands
- * below 2 GiB), pc == 0 -> the 4-wave kernel (64-bit pointers). */
-NQ_API int nq_conv_wgrad3_plan(int B, int Cin, int H, int W, int Cout, int k, int* mi, int* ni, int* nsplit, int* pc);
-NQ_API int nq_conv_wgrad3(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                   int k, nq_stream_t stream);
-/* The same with operands as split {hi | lo} words (see NQ_EPI_X_SPLIT): fmt bit 0 -- x, bit 1 -- dy, only the bits
- * nq_conv_wgrad3_split_io returns for the shape (the row-segment producer/consumer kernel).  dw is bit-identical to the float
- * call on the un-split tensors; db sums hi + lo of every dy value (what the matrix pipe sees of it). */
-NQ_API int nq_conv_wgrad3_split_io(int B, int Cin, int H, int W, int Cout, int k);
-NQ_API int nq_conv_wgrad3_fmt(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                       int k, int fmt, nq_stream_t stream);
-/* The same weight gradient dw (Cout,Cin,k,k) for a convolution with very FEW output channels (the 3-channel head, HNeRV.py:42)
- * by exchanged operand roles: R[ci][(co,tap)] = sum_p x[ci][p] * dy[co][p+tap] is the weight gradient of the convolution
- * dy -> x-channels and dW[co][ci][tap] = R[ci][co][k*k-1-tap]; the big tensor x is then the un-shifted GEMM operand read
- * exactly once.  ws: nq_conv_wgrad3_ws_floats(B, Cout, H, W, Cin, k) floats (the exchanged problem).  No bias gradient
- * (use nq_channel_sum on dy).  NQ_ERR_UNSUPPORTED where that size is the 4-float token of the few-pixel kernel (which has
- * no exchanged form): a real slab workspace is never that small, so `ws_floats > 4` is the host-side predicate. */
-NQ_API int nq_conv_wgrad3_swapped(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout, int k,
-                           nq_stream_t stream);
-
-/* Weight + bias gradient of the same convolution: dw (Cout,Cin,k,k), db (Cout) (db may be NULL),
- * from x (B,Cin,H,W) and dy (B,Cout,H,W).  ws: scratch of >= nq_conv_wgrad_ws_floats(...) floats.
- * x_gelu != 0: x holds pre-activations, exact GELU is applied while staging.  Deterministic (fixed split-K order). */
-NQ_API int64_t nq_conv_wgrad_ws_floats(int B, int Cin, int H, int W, int Cout, int k);
-NQ_API int nq_conv_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                  int k, int x_gelu, nq_stream_t stream);
-
-/* Deferred slab reduction (round 3).  The weight-gradient kernels above split K over workgroups into slabs and finish with a
- * fixed-order reduction launch each (five ~10 us launches per HNeRV-3M iteration).  The *_slabs variants run ONLY the
- * split kernel and describe the pending reduction in *seg (slab / dw / db pointers stay owned by the caller until it ran);
- * nq_wgrad_reduce_multi performs up to 16 pending reductions per launch, each with the same summation order as the
- * single-tensor entry point -- results are bit-identical to nq_conv_wgrad3 / nq_conv_wgrad3_swapped / nq_conv_wgrad.
- * seg->nsplit == 0 on return: the kernel wrote dw / db itself (tiny 1x1 problems), nothing is pending. */
+/* Weight + bias gradient of the same convolution: dw (Cout,Cin,k,k), db (Cout) (db may be NULL), from x (B,Cin,H,W) and
+ * dy (B,Cout,H,W).  ws: scratch of >= nq_conv_wgrad_ws_floats(...) floats.  Deterministic (fixed split-K order).
+ * The kernels split K over workgroups into slabs and finish with a fixed-order reduction launch.  seg == NULL: both run.
+ * seg != NULL (deferred reduction): ONLY the split kernel runs and *seg describes the pending reduction (slab / dw / db
+ * pointers stay owned by the caller until it ran); nq_wgrad_reduce_multi performs up to 16 pending reductions per launch,
+ * each with the same summation order -- results are bit-identical to the seg == NULL call.  seg->nsplit == 0 on return:
+ * the kernel wrote dw / db itself (few-pixel problems), nothing is pending.  The three entries below share this contract. */
 typedef struct nq_wgr_seg {
   const float* slab;     /* [nsplit][co_pad][n_pad] */
   const float* slab_db;  /* [nsplit][co_pad] or NULL */
@@ -340,15 +312,37 @@ typedef struct nq_wgr_seg {
   int swap_kk;           /* > 0: role-swapped problem, dw[ci][co][kk-1-tap] = R[co][ci][tap] (nq_conv_wgrad3_swapped) */
   int sg;                /* split groups per output (1, 4 or 16): fixes the summation order */
 } nq_wgr_seg;
-NQ_API int nq_conv_wgrad3_slabs(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                         int k, nq_wgr_seg* seg, nq_stream_t stream);
-NQ_API int nq_conv_wgrad3_slabs_fmt(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
-                             int Cout, int k, nq_wgr_seg* seg, int fmt, nq_stream_t stream);   /* fmt: nq_conv_wgrad3_fmt */
-/* (NQ_ERR_UNSUPPORTED for the same shapes as nq_conv_wgrad3_swapped: a 4-float nq_conv_wgrad3_ws_floats of the exchanged problem) */
-NQ_API int nq_conv_wgrad3_swapped_slabs(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout,
-                                 int k, nq_wgr_seg* seg, nq_stream_t stream);
-NQ_API int nq_conv_wgrad_slabs(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                        int k, int x_gelu, nq_wgr_seg* seg, nq_stream_t stream);
+NQ_API int64_t nq_conv_wgrad_ws_floats(int B, int Cin, int H, int W, int Cout, int k);
+NQ_API int nq_conv_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
+                  int k, nq_wgr_seg* seg, nq_stream_t stream);
+
+/* bf16x3 variant of nq_conv_wgrad, k in {3,5}: */
+NQ_API int nq_conv_wgrad3_supported(int B, int Cin, int H, int W, int Cout, int k);
+NQ_API int64_t nq_conv_wgrad3_ws_floats(int B, int Cin, int H, int W, int Cout, int k);   /* 4 (a token) for few-pixel shapes */
+/* The launch plan nq_conv_wgrad3 will use for this shape (pure host function): MT = 16*mi channels x NT = 64*ni columns per
+ * workgroup, nsplit K-splits, pc != 0 -> the 8-wave producer/consumer kernel (32-bit buffer offsets: only for operands
+ * below 2 GiB), pc == 0 -> the 4-wave kernel (64-bit pointers). */
+NQ_API int nq_conv_wgrad3_plan(int B, int Cin, int H, int W, int Cout, int k, int* mi, int* ni, int* nsplit, int* pc);
+/* fmt != 0: operands as split {hi | lo} words (see NQ_EPI_X_SPLIT): bit 0 -- x, bit 1 -- dy, only the bits
+ * nq_conv_wgrad3_split_io returns for the shape (the row-segment producer/consumer kernel; other bits: NQ_ERR_UNSUPPORTED).
+ * dw is bit-identical to the float call on the un-split tensors; db sums hi + lo of every dy value (what the matrix pipe
+ * sees of it). */
+NQ_API int nq_conv_wgrad3_split_io(int B, int Cin, int H, int W, int Cout, int k);
+NQ_API int nq_conv_wgrad3(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
+                   int k, int fmt, nq_wgr_seg* seg, nq_stream_t stream);
+/* The same weight gradient dw (Cout,Cin,k,k) for a convolution with very FEW output channels (the 3-channel head, HNeRV.py:42)
+ * by exchanged operand roles: R[ci][(co,tap)] = sum_p x[ci][p] * dy[co][p+tap] is the weight gradient of the convolution
+ * dy -> x-channels and dW[co][ci][tap] = R[ci][co][k*k-1-tap]; the big tensor x is then the un-shifted GEMM operand read
+ * exactly once.  No bias gradient (use nq_channel_sum on dy).  All three take the arguments of the ORIGINAL layer:
+ *   nq_conv_wgrad3_swapped_ws_floats : size of ws -- the slabs of the exchanged problem's plan; 0 exactly where the launch is
+ *                                      NQ_ERR_UNSUPPORTED (the few-pixel kernel owns the exchanged shape: no exchanged form)
+ *   nq_conv_wgrad3_swapped_supported : 1 where callers should route here (like nq_conv3_supported, narrower than what the
+ *                                      launch accepts): Cout <= 4 < Cin, Cout*k*k <= 64, the exchanged problem is
+ *                                      nq_conv_wgrad3_supported and the workspace size above is not 0 */
+NQ_API int64_t nq_conv_wgrad3_swapped_ws_floats(int B, int Cin, int H, int W, int Cout, int k);
+NQ_API int nq_conv_wgrad3_swapped_supported(int B, int Cin, int H, int W, int Cout, int k);
+NQ_API int nq_conv_wgrad3_swapped(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout, int k,
+                           nq_wgr_seg* seg, nq_stream_t stream);
 NQ_API int nq_wgrad_reduce_multi(const nq_wgr_seg* segs, int nseg, nq_stream_t stream);
 
 /* Backward of PixelShuffle(r)+GELU: dconv (B,C*r*r,H,W) = unshuffle(da * z), da and z (B,C,H*r,W*r), z = the saved

@@ -14,11 +14,11 @@ int nq_tiny_pw_wgrad(const float* x, const float* dy, float* dw, float* db, int 
 
 extern "C" {
 int nq_conv_igemm_k1(const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int,
-                     int, float*, int, const float*, hipStream_t);
+                     int, float*, const float*, hipStream_t);
 int nq_conv_igemm_k3(const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int,
-                     int, float*, int, const float*, hipStream_t);
+                     int, float*, const float*, hipStream_t);
 int nq_conv_igemm_k5(const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int,
-                     int, float*, int, const float*, hipStream_t);
+                     int, float*, const float*, hipStream_t);
 int nq_conv_splitk_finish(const float*, const float*, float*, float*, const float*, int, int, int, int, int, int, int,
                           hipStream_t);
 int nq_head_supported(int, int);
@@ -26,11 +26,11 @@ int nq_head_forward(const float*, const float*, int, const float*, float*, int, 
 int nq_head_dgrad(const float*, const float*, int, const float*, float*, int, int, int, int, int, int, int, int, hipStream_t);
 int nq_head_dgrad_streams(int, int, int, int, int, int, int, int);
 int nq_conv_wgrad_k1(const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int, int,
-                     int, hipStream_t);
+                     hipStream_t);
 int nq_conv_wgrad_k3(const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int, int,
-                     int, hipStream_t);
+                     hipStream_t);
 int nq_conv_wgrad_k5(const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int, int,
-                     int, hipStream_t);
+                     hipStream_t);
 }
 
 namespace {
@@ -66,11 +66,11 @@ inline int pick_nsplit(int B, int Cin, int H, int W, int Cout, int k) {
   return ns < 1 ? 1 : ns;
 }
 
-inline bool use_head_fwd(int Cout, int k, int epi, int in_gelu) {
-  return nq_head_supported(Cout, k) && (epi == NQ_EPI_PLAIN || epi == NQ_EPI_TANH) && !in_gelu;
+inline bool use_head_fwd(int Cout, int k, int epi) {
+  return nq_head_supported(Cout, k) && (epi == NQ_EPI_PLAIN || epi == NQ_EPI_TANH);
 }
-inline bool use_head_dgrad(int Cin, int k, int epi, int in_gelu, const float* bias) {
-  return nq_head_supported(Cin, k) && (epi == NQ_EPI_PLAIN || epi == NQ_EPI_DGRAD_GELU) && !in_gelu && !bias;
+inline bool use_head_dgrad(int Cin, int k, int epi, bool has_bias) {
+  return nq_head_supported(Cin, k) && (epi == NQ_EPI_PLAIN || epi == NQ_EPI_DGRAD_GELU) && !has_bias;
 }
 
 inline int wgrad_ni(int mi, int k) { return k == 1 ? 2 : (mi <= 3 ? 6 : (mi <= 6 ? 4 : 3)); }
@@ -261,16 +261,14 @@ int64_t nq_conv_forward_ws_floats(int B, int Cin, int H, int W, int Cout, int k)
 }
 
 // 1 when nq_conv_forward can write its output y as split {hi | lo} words for this call (include/nq_hip.h)
-int nq_conv_split_out(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int in_gelu, int has_bias) {
+int nq_conv_split_out(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int has_bias) {
   if (!ks_ok(k) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  if (use_head_fwd(Cout, k, epilogue, in_gelu)) return 0;
-  if (!(nq_head_supported(Cin, k) && (epilogue == NQ_EPI_PLAIN || epilogue == NQ_EPI_DGRAD_GELU) && !in_gelu && !has_bias)) return 0;
+  if (use_head_fwd(Cout, k, epilogue) || !use_head_dgrad(Cin, k, epilogue, has_bias != 0)) return 0;
   return nq_head_dgrad_streams(B, Cout, H, W, Cin, k, epilogue == NQ_EPI_DGRAD_GELU ? r : 1, epilogue == NQ_EPI_DGRAD_GELU);
 }
 
 int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y, float* z, float* ws, int B, int Cin, int H,
-                    int W, int Cout, int k, int krows, int ld, int r, int epilogue, int in_gelu, const float* zprev,
-                    nq_stream_t stream) {
+                    int W, int Cout, int k, int krows, int ld, int r, int epilogue, const float* zprev, nq_stream_t stream) {
   if (!x || !wt || (!y && epilogue != NQ_EPI_PS) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0)
     return NQ_ERR_INVALID;
   if (!ks_ok(k)) return NQ_ERR_UNSUPPORTED;
@@ -278,7 +276,7 @@ int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y
   const int y_split = (epilogue & NQ_EPI_Y_SPLIT) ? 1 : 0;
   if (epilogue & NQ_EPI_X_SPLIT) return NQ_ERR_UNSUPPORTED;
   epilogue &= ~NQ_EPI_Y_SPLIT;
-  if (y_split && !nq_conv_split_out(B, Cin, H, W, Cout, k, r, epilogue, in_gelu, bias != nullptr)) return NQ_ERR_UNSUPPORTED;
+  if (y_split && !nq_conv_split_out(B, Cin, H, W, Cout, k, r, epilogue, bias != nullptr)) return NQ_ERR_UNSUPPORTED;
   if (epilogue < 0 || epilogue > NQ_EPI_DGRAD_GELU) return NQ_ERR_INVALID;
   if ((epilogue == NQ_EPI_PS_GELU || epilogue == NQ_EPI_PS) && (!z || r <= 0 || Cout % (r * r) != 0)) return NQ_ERR_INVALID;
   if (epilogue == NQ_EPI_DGRAD_GELU && (!zprev || r <= 0 || H % r != 0 || W % r != 0)) return NQ_ERR_INVALID;
@@ -288,13 +286,13 @@ int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y
   if (B > 65535) return NQ_ERR_UNSUPPORTED;
   hipStream_t st0 = nq_s(stream);
   // <= 4 output channels (the decoder head) / <= 4 input channels (its data gradient): HBM-bound vector kernels
-  if (use_head_fwd(Cout, k, epilogue, in_gelu))
+  if (use_head_fwd(Cout, k, epilogue))
     return nq_head_forward(x, wt, ld, bias, y, B, Cin, H, W, Cout, k, epilogue, st0);
-  if (use_head_dgrad(Cin, k, epilogue, in_gelu, bias))
+  if (use_head_dgrad(Cin, k, epilogue, bias != nullptr))
     return nq_head_dgrad(x, wt, ld, epilogue == NQ_EPI_DGRAD_GELU ? zprev : nullptr, y, B, Cout, H, W, Cin, k,
                          epilogue == NQ_EPI_DGRAD_GELU ? r : 1, y_split, st0);
   // 1x1 convolutions over a handful of pixels (decoder stem / first block): compact thread-per-output kernel
-  if (!in_gelu && nq_tiny_pw_supported(B, Cin, H, W, Cout, k))
+  if (nq_tiny_pw_supported(B, Cin, H, W, Cout, k))
     return nq_tiny_pw_forward(x, wt, bias, y, z, zprev, B, Cin, H, W, Cout, ld, r, epilogue, st0);
   const int mi = pick_mi_fwd(Cout);
   const int ns = pick_nsplit(B, Cin, H, W, Cout, k);
@@ -303,9 +301,9 @@ int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y
   hipStream_t st = nq_s(stream);
   int rc;
   switch (k) {
-    case 1: rc = nq_conv_igemm_k1(x, wt, bias, y, z, B, Cin, H, W, Cout, ld, r, epilogue, mi, ns, ws, in_gelu, zprev, st); break;
-    case 3: rc = nq_conv_igemm_k3(x, wt, bias, y, z, B, Cin, H, W, Cout, ld, r, epilogue, mi, ns, ws, in_gelu, zprev, st); break;
-    default: rc = nq_conv_igemm_k5(x, wt, bias, y, z, B, Cin, H, W, Cout, ld, r, epilogue, mi, ns, ws, in_gelu, zprev, st); break;
+    case 1: rc = nq_conv_igemm_k1(x, wt, bias, y, z, B, Cin, H, W, Cout, ld, r, epilogue, mi, ns, ws, zprev, st); break;
+    case 3: rc = nq_conv_igemm_k3(x, wt, bias, y, z, B, Cin, H, W, Cout, ld, r, epilogue, mi, ns, ws, zprev, st); break;
+    default: rc = nq_conv_igemm_k5(x, wt, bias, y, z, B, Cin, H, W, Cout, ld, r, epilogue, mi, ns, ws, zprev, st); break;
   }
   if (rc != NQ_OK || ns == 1) return rc;
   return nq_conv_splitk_finish(ws, bias, y, z, zprev, B, H, W, Cout, r, epilogue, ns, st);
@@ -317,26 +315,13 @@ int64_t nq_conv_wgrad_ws_floats(int B, int Cin, int H, int W, int Cout, int k) {
   return (int64_t)p.nsplit * p.co_pad * ((int64_t)p.n_pad + 1);
 }
 
-static int conv_wgrad_impl(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
-                           int Cout, int k, int x_gelu, nq_wgr_seg* seg, nq_stream_t stream);
-
+// seg == NULL: split kernel + reduction; seg != NULL: the split kernel only, *seg describes the pending reduction
 int nq_conv_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                  int k, int x_gelu, nq_stream_t stream) {
-  return conv_wgrad_impl(x, dy, dw, db, ws, B, Cin, H, W, Cout, k, x_gelu, nullptr, stream);
-}
-
-int nq_conv_wgrad_slabs(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                        int k, int x_gelu, nq_wgr_seg* seg, nq_stream_t stream) {
-  if (!seg) return NQ_ERR_INVALID;
-  return conv_wgrad_impl(x, dy, dw, db, ws, B, Cin, H, W, Cout, k, x_gelu, seg, stream);
-}
-
-static int conv_wgrad_impl(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
-                           int Cout, int k, int x_gelu, nq_wgr_seg* seg, nq_stream_t stream) {
+                  int k, nq_wgr_seg* seg, nq_stream_t stream) {
   if (!x || !dy || !dw || !ws || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
   if (!ks_ok(k)) return NQ_ERR_UNSUPPORTED;
   if (seg) *seg = nq_wgr_seg{nullptr, nullptr, dw, db, Cout, Cin * k * k, 0, 0, 0, 0, 1};
-  if (!x_gelu && nq_tiny_pw_supported(B, Cin, H, W, Cout, k))
+  if (nq_tiny_pw_supported(B, Cin, H, W, Cout, k))
     return nq_tiny_pw_wgrad(x, dy, dw, db, B, Cin, H, W, Cout, nq_s(stream));
   WgradPlan p = plan_wgrad(B, Cin, H, W, Cout, k);
   float* slab = ws;
@@ -344,9 +329,9 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dw, float* db
   hipStream_t st = nq_s(stream);
   int rc;
   switch (k) {
-    case 1: rc = nq_conv_wgrad_k1(x, dy, slab, slab_db, B, Cin, H, W, Cout, p.co_pad, p.n_pad, p.nsplit, p.mi, p.ni, x_gelu, st); break;
-    case 3: rc = nq_conv_wgrad_k3(x, dy, slab, slab_db, B, Cin, H, W, Cout, p.co_pad, p.n_pad, p.nsplit, p.mi, p.ni, x_gelu, st); break;
-    default: rc = nq_conv_wgrad_k5(x, dy, slab, slab_db, B, Cin, H, W, Cout, p.co_pad, p.n_pad, p.nsplit, p.mi, p.ni, x_gelu, st); break;
+    case 1: rc = nq_conv_wgrad_k1(x, dy, slab, slab_db, B, Cin, H, W, Cout, p.co_pad, p.n_pad, p.nsplit, p.mi, p.ni, st); break;
+    case 3: rc = nq_conv_wgrad_k3(x, dy, slab, slab_db, B, Cin, H, W, Cout, p.co_pad, p.n_pad, p.nsplit, p.mi, p.ni, st); break;
+    default: rc = nq_conv_wgrad_k5(x, dy, slab, slab_db, B, Cin, H, W, Cout, p.co_pad, p.n_pad, p.nsplit, p.mi, p.ni, st); break;
   }
   if (rc != NQ_OK) return rc;
   const int N = Cin * k * k;

@@ -642,12 +642,7 @@ int64_t nq_conv_wgrad3_ws_floats(int B, int Cin, int H, int W, int Cout, int k) 
 }
 
 static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
-                            int Cout, int k, int swap_kk, nq_wgr_seg* seg, nq_stream_t stream, int fmt = 0);
-
-int nq_conv_wgrad3(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                   int k, nq_stream_t stream) {
-  return conv_wgrad3_impl(x, dy, dw, db, ws, B, Cin, H, W, Cout, k, 0, nullptr, stream);
-}
+                            int Cout, int k, int swap_kk, nq_wgr_seg* seg, nq_stream_t stream, int fmt);
 
 // Operands as split {hi | lo} words (include/nq_hip.h): fmt bit 0 -- x, bit 1 -- dy; where nq_conv_wgrad3_split_io says so
 int nq_conv_wgrad3_split_io(int B, int Cin, int H, int W, int Cout, int k) {
@@ -655,34 +650,31 @@ int nq_conv_wgrad3_split_io(int B, int Cin, int H, int W, int Cout, int k) {
   const Wg3Plan p = plan_wgrad3(B, Cin, H, W, Cout, k);
   return (p.pc == 1 || p.pc == 12 || p.pc == 14) ? 3 : 0;
 }
-int nq_conv_wgrad3_fmt(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                       int k, int fmt, nq_stream_t stream) {
-  if (fmt & ~nq_conv_wgrad3_split_io(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
-  return conv_wgrad3_impl(x, dy, dw, db, ws, B, Cin, H, W, Cout, k, 0, nullptr, stream, fmt);
-}
-int nq_conv_wgrad3_slabs_fmt(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
-                             int Cout, int k, nq_wgr_seg* seg, int fmt, nq_stream_t stream) {
-  if (!seg) return NQ_ERR_INVALID;
+
+// seg == NULL: split kernel + reduction; seg != NULL: the split kernel only, *seg describes the pending reduction
+int nq_conv_wgrad3(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
+                   int k, int fmt, nq_wgr_seg* seg, nq_stream_t stream) {
   if (fmt & ~nq_conv_wgrad3_split_io(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
   return conv_wgrad3_impl(x, dy, dw, db, ws, B, Cin, H, W, Cout, k, 0, seg, stream, fmt);
 }
 
+// Role-swapped form, arguments of the ORIGINAL layer: 0 where the few-pixel kernel owns the exchanged shape (it has no
+// transposing store, so nq_conv_wgrad3_swapped refuses it), else the slab size of the exchanged problem's plan
+int64_t nq_conv_wgrad3_swapped_ws_floats(int B, int Cin, int H, int W, int Cout, int k) {
+  if (nq_conv_wgrad_flat3_ok(B, Cout, H, W, Cin, k)) return 0;
+  return nq_conv_wgrad3_ws_floats(B, Cout, H, W, Cin, k);
+}
+
+// where callers should route a weight gradient to the role-swapped form (narrower than what the launch accepts)
+int nq_conv_wgrad3_swapped_supported(int B, int Cin, int H, int W, int Cout, int k) {
+  return Cout <= 4 && Cin > 4 && Cout * k * k <= 64 && nq_conv_wgrad3_supported(B, Cout, H, W, Cin, k) &&
+         nq_conv_wgrad3_swapped_ws_floats(B, Cin, H, W, Cout, k) > 0;
+}
+
 int nq_conv_wgrad3_swapped(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout, int k,
-                           nq_stream_t stream) {
+                           nq_wgr_seg* seg, nq_stream_t stream) {
   // the kernel sees the exchanged problem: "x" = dy (Cout channels), "dy" = x (Cin channels)
-  return conv_wgrad3_impl(dy, x, dw, nullptr, ws, B, Cout, H, W, Cin, k, k * k, nullptr, stream);
-}
-
-int nq_conv_wgrad3_slabs(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
-                         int k, nq_wgr_seg* seg, nq_stream_t stream) {
-  if (!seg) return NQ_ERR_INVALID;
-  return conv_wgrad3_impl(x, dy, dw, db, ws, B, Cin, H, W, Cout, k, 0, seg, stream);
-}
-
-int nq_conv_wgrad3_swapped_slabs(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout,
-                                 int k, nq_wgr_seg* seg, nq_stream_t stream) {
-  if (!seg) return NQ_ERR_INVALID;
-  return conv_wgrad3_impl(dy, x, dw, nullptr, ws, B, Cout, H, W, Cin, k, k * k, seg, stream);
+  return conv_wgrad3_impl(dy, x, dw, nullptr, ws, B, Cout, H, W, Cin, k, k * k, seg, stream, 0);
 }
 
 int nq_wgrad_reduce_multi(const nq_wgr_seg* segs, int nseg, nq_stream_t stream) {
@@ -725,8 +717,8 @@ static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* d
     if (seg) *seg = nq_wgr_seg{nullptr, nullptr, dw, db, Cout, Cin * k * k, 0, 0, 0, 0, 1};
     return nq_conv_wgrad_flat3(x, dy, dw, db, B, Cin, H, W, Cout, k, nq_s(stream));
   }
-  // Role-swapped entries (here Cin / Cout are those of the EXCHANGED problem): the few-pixel kernel has no transposing
-  // store, and nq_conv_wgrad3_ws_floats sizes a 4-float token for its shapes -- the slabs below would not fit.  Refused.
+  // Role-swapped entry (here Cin / Cout are those of the EXCHANGED problem): the few-pixel kernel has no transposing
+  // store and no slabs (nq_conv_wgrad3_swapped_ws_floats answers 0).  Refused.
   if (swap_kk != 0 && nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
   Wg3Plan p = plan_wgrad3(B, Cin, H, W, Cout, k);
   float* slab = ws;

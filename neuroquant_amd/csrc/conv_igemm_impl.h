@@ -37,7 +37,7 @@ struct ConvArgs {
   const float* bias;
   float* y;
   float* z;
-  int B, Cin, H, W, Cout, ld, r, epi, tiles_x, tiles, co_tiles, ncg, nsplit, in_gelu;
+  int B, Cin, H, W, Cout, ld, r, epi, tiles_x, tiles, co_tiles, ncg, nsplit;
   const float* zprev;  // NQ_EPI_DGRAD_GELU: pre-activation of the layer below, (B,Cout,H,W)
   float* slab;  // [nsplit][B][Cout][H][W] partial sums when nsplit > 1
 };
@@ -68,8 +68,6 @@ __device__ __forceinline__ void igemm_steps(F&& f) {
     igemm_steps<I0 + 1, N>(f);
   }
 }
-
-__device__ __forceinline__ float gelu_exact(float v) { return v * 0.5f * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 // Kernel rows per slice: narrow channel tiles (MI <= 4: the data gradients 148->44, 176->53, 848->64) would otherwise
 // run only 6*MI MFMAs between barriers; they take a whole channel group (all KS kernel rows) per slice instead.
@@ -107,7 +105,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const float* __restrict__ xb = a.x + (int64_t)b * Cin * H * W;
   const float* __restrict__ wt = a.wt + co0;
   const int ld = a.ld;
-  const bool in_gelu = a.in_gelu != 0;  // the input is a pre-activation: apply GELU while staging (gelu(0)=0 keeps the halo)
 
   // ---- staging helpers ------------------------------------------------------------------------
   float pv[PPT];
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 #define NQ_STORE_PATCH(DST)                                                                       \
   _Pragma("unroll") for (int i = 0; i < PPT; ++i) {                                               \
-    if (plds[i] >= 0) (DST)[plds[i]] = in_gelu ? gelu_exact(pv[i]) : pv[i];                       \
+    if (plds[i] >= 0) (DST)[plds[i]] = pv[i];                                                     \
   }
 #define NQ_LOAD_W(CG, KH)                                                                         \
   _Pragma("unroll") for (int i = 0; i < WPT; ++i) {                                               \
@@ -472,8 +469,7 @@ int launch_igemm(const ConvArgs& a_in, int tiles, int co_tiles, hipStream_t st) 
 // mi_sel: channel blocks (of 16) per workgroup, chosen by nq_conv_pick_mi().
 extern "C" int NQ_CAT(nq_conv_igemm_k, NQ_KS)(const float* x, const float* wt, const float* bias, float* y, float* z,
                                                int B, int Cin, int H, int W, int Cout, int ld, int r, int epi,
-                                               int mi_sel, int nsplit, float* slab, int in_gelu, const float* zprev,
-                                               hipStream_t st) {
+                                               int mi_sel, int nsplit, float* slab, const float* zprev, hipStream_t st) {
   ConvArgs a;
   a.x = x; a.wt = wt; a.bias = bias; a.y = y; a.z = z;
   a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.ld = ld; a.r = r; a.epi = epi;
@@ -481,7 +477,6 @@ extern "C" int NQ_CAT(nq_conv_igemm_k, NQ_KS)(const float* x, const float* wt, c
   a.ncg = (Cin + CI - 1) / CI;
   a.nsplit = nsplit;
   a.slab = slab;
-  a.in_gelu = in_gelu;
   a.zprev = zprev;
   int tiles = a.tiles_x * ((H + TH - 1) / TH);
   int co_tiles = (Cout + 16 * mi_sel - 1) / (16 * mi_sel);

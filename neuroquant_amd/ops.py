@@ -596,14 +596,14 @@ def _conv_outputs(x, cout, epilogue, r):
 
 def conv_forward_raw(x, wt, dims, bias, cout, k, epilogue, r, zprev=None, fmt=0):
     """One nq_conv_forward launch.  Returns (y, z) as _conv_outputs describes them.  fmt = EPI_Y_SPLIT: y as split {hi | lo}
-    words (conv_split_out says where).  The kernels' GELU-on-load option is not offered here (nothing uses it)."""
+    words (conv_split_out says where)."""
     B, cin, H, W = x.shape
     y, z = _conv_outputs(x, cout, epilogue, r)
     nws = _q("nq_conv_forward_ws_floats", B, cin, H, W, cout, k)
     ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws else None
     _timed(("conv_igemm", k, cin, cout, H, W, B, epilogue),
            lambda: L.check(L.lib().nq_conv_forward(_p(x), _p(wt), _p(bias), _p(y), _p(z), _p(ws), B, cin, H, W, cout, k,
-                                                   dims[0], dims[1], r, epilogue | fmt, 0, _p(zprev), _stream()), "conv_forward"))
+                                                   dims[0], dims[1], r, epilogue | fmt, _p(zprev), _stream()), "conv_forward"))
     return y, z
 
 
@@ -623,7 +623,7 @@ def conv_wgrad3_split_io(B, cin, H, W, cout, k):
 
 def conv_split_out(B, cin, H, W, cout, k, r, epilogue, has_bias=False):
     """True when conv_forward_raw can write y as split words for this call (the streaming head data gradient)"""
-    return bool(_q("nq_conv_split_out", B, cin, H, W, cout, k, r, epilogue, 0, 1 if has_bias else 0))
+    return bool(_q("nq_conv_split_out", B, cin, H, W, cout, k, r, epilogue, 1 if has_bias else 0))
 
 
 def split_words(x):
@@ -684,24 +684,31 @@ class PendingReductions:
         self.segs, self.keep = [], []
 
 
+def _wgrad_outputs(x, cout, k, want_db, out):
+    """(dw, db) of a weight-gradient launch on x: out = (dw, db) pre-allocated contiguous outputs (views of a flat gradient
+    arena) or None -> allocated here; db is None unless want_db."""
+    dw = torch.empty((cout, x.shape[1], k, k), device=x.device, dtype=torch.float32) if out is None else out[0]
+    db = (torch.empty(cout, device=x.device, dtype=torch.float32) if out is None else out[1]) if want_db else None
+    return dw, db
+
+
+def _seg_ref(seg):
+    return None if seg is None else ctypes.byref(seg)
+
+
 def conv_wgrad3_raw(x, dy, cout, k, want_db, out=None, defer=None, fmt=0):
-    """bf16x3 counterpart of conv_wgrad_raw.  out = (dw, db) pre-allocated contiguous outputs (views of a flat
-    gradient arena) or None.  defer (PendingReductions): only the split kernel runs now, dw / db are valid after
-    defer.flush().  fmt bit 0 / 1: x / dy hold split {hi | lo} words (conv_wgrad3_split_io)."""
+    """bf16x3 counterpart of conv_wgrad_raw (out as _wgrad_outputs takes it).  defer (PendingReductions): only the split
+    kernel runs now, dw / db are valid after defer.flush().  fmt bit 0 / 1: x / dy hold split {hi | lo} words
+    (conv_wgrad3_split_io)."""
     B, cin, H, W = x.shape
     ws = torch.empty(_q("nq_conv_wgrad3_ws_floats", B, cin, H, W, cout, k), device=x.device, dtype=torch.float32)
-    dw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32) if out is None else out[0]
-    db = (torch.empty(cout, device=x.device, dtype=torch.float32) if out is None else out[1]) if want_db else None
-    if defer is not None:
-        seg = L.WgrSeg()
-        _timed(("conv_wgrad3", k, cin, cout, H, W, B, 0),
-               lambda: L.check(L.lib().nq_conv_wgrad3_slabs_fmt(_p(x), _p(dy), _p(dw), _p(db), _p(ws), B, cin, H, W, cout, k,
-                                                                ctypes.byref(seg), fmt, _stream()), "conv_wgrad3_slabs"))
-        defer.add(seg, ws, dw, db)
-        return dw, db
+    dw, db = _wgrad_outputs(x, cout, k, want_db, out)
+    seg = None if defer is None else L.WgrSeg()
     _timed(("conv_wgrad3", k, cin, cout, H, W, B, 0),
-           lambda: L.check(L.lib().nq_conv_wgrad3_fmt(_p(x), _p(dy), _p(dw), _p(db), _p(ws), B, cin, H, W, cout, k, fmt,
-                                                      _stream()), "conv_wgrad3"))
+           lambda: L.check(L.lib().nq_conv_wgrad3(_p(x), _p(dy), _p(dw), _p(db), _p(ws), B, cin, H, W, cout, k, fmt,
+                                                  _seg_ref(seg), _stream()), "conv_wgrad3"))
+    if seg is not None:
+        defer.add(seg, ws, dw, db)
     return dw, db
 
 
@@ -716,11 +723,8 @@ def channel_sum(x):
 
 def conv_wgrad_swapped3_supported(B, cin, H, W, cout, k):
     """True when conv_wgrad_swapped3 serves this (cin -> cout) layer: a head with <= 4 output channels whose exchanged problem
-    (cout -> cin) the tiled bf16x3 kernels take.  Exchanged shapes that nq_conv_wgrad3_supported accepts for the few-pixel
-    kernel are NOT served (that kernel has no exchanged form): nq_conv_wgrad3_ws_floats answers its 4-float token for them,
-    which no slab workspace is as small as."""
-    return (cout <= 4 and cin > 4 and cout * k * k <= 64 and conv_wgrad3_supported(B, cout, H, W, cin, k)
-            and _q("nq_conv_wgrad3_ws_floats", B, cout, H, W, cin, k) > 4)
+    (cout -> cin) the tiled bf16x3 kernels take (the few-pixel kernel has no exchanged form)."""
+    return bool(_q("nq_conv_wgrad3_swapped_supported", B, cin, H, W, cout, k))
 
 
 def conv_wgrad_swapped3(x, dy, cout, k, want_db, out=None, defer=None):
@@ -730,19 +734,15 @@ def conv_wgrad_swapped3(x, dy, cout, k, want_db, out=None, defer=None):
     read exactly once, only the 3-channel dy needs halo rows, and the MFMA tile is 37(->48) x 27(->64) instead of
     3(->16) x 333(->384)."""
     B, cin, H, W = x.shape
-    ws = torch.empty(_q("nq_conv_wgrad3_ws_floats", B, cout, H, W, cin, k), device=x.device, dtype=torch.float32)
-    dw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32) if out is None else out[0]
+    ws = torch.empty(_q("nq_conv_wgrad3_swapped_ws_floats", B, cin, H, W, cout, k), device=x.device, dtype=torch.float32)
+    dw, _ = _wgrad_outputs(x, cout, k, False, out)
+    seg = None if defer is None else L.WgrSeg()
     # the slab reduction writes dW[co][ci][K-1-kh][K-1-kw] directly (no permute / flip / copy passes)
-    if defer is not None:
-        seg = L.WgrSeg()
-        _timed(("conv_wgrad3", k, cout, cin, H, W, B, 0),
-               lambda: L.check(L.lib().nq_conv_wgrad3_swapped_slabs(_p(x), _p(dy), _p(dw), _p(ws), B, cin, H, W, cout, k,
-                                                                    ctypes.byref(seg), _stream()), "conv_wgrad3_swapped_slabs"))
+    _timed(("conv_wgrad3", k, cout, cin, H, W, B, 0),
+           lambda: L.check(L.lib().nq_conv_wgrad3_swapped(_p(x), _p(dy), _p(dw), _p(ws), B, cin, H, W, cout, k,
+                                                          _seg_ref(seg), _stream()), "conv_wgrad3_swapped"))
+    if seg is not None:
         defer.add(seg, ws, dw)
-    else:
-        _timed(("conv_wgrad3", k, cout, cin, H, W, B, 0),
-               lambda: L.check(L.lib().nq_conv_wgrad3_swapped(_p(x), _p(dy), _p(dw), _p(ws), B, cin, H, W, cout, k, _stream()),
-                               "conv_wgrad3_swapped"))
     db = None
     if want_db:
         db = channel_sum(dy)
@@ -753,21 +753,16 @@ def conv_wgrad_swapped3(x, dy, cout, k, want_db, out=None, defer=None):
 
 
 def conv_wgrad_raw(x, dy, cout, k, want_db, out=None, defer=None):
-    """fp32 weight (and bias) gradient; out / defer as conv_wgrad3_raw.  The kernels' GELU-on-load option is passed as 0."""
+    """fp32 weight (and bias) gradient; out / defer as conv_wgrad3_raw."""
     B, cin, H, W = x.shape
     ws = torch.empty(_q("nq_conv_wgrad_ws_floats", B, cin, H, W, cout, k), device=x.device, dtype=torch.float32)
-    dw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32) if out is None else out[0]
-    db = (torch.empty(cout, device=x.device, dtype=torch.float32) if out is None else out[1]) if want_db else None
-    if defer is not None:
-        seg = L.WgrSeg()
-        _timed(("conv_wgrad", k, cin, cout, H, W, B, 0),
-               lambda: L.check(L.lib().nq_conv_wgrad_slabs(_p(x), _p(dy), _p(dw), _p(db), _p(ws), B, cin, H, W, cout, k,
-                                                           0, ctypes.byref(seg), _stream()), "conv_wgrad_slabs"))
-        defer.add(seg, ws, dw, db)
-        return dw, db
+    dw, db = _wgrad_outputs(x, cout, k, want_db, out)
+    seg = None if defer is None else L.WgrSeg()
     _timed(("conv_wgrad", k, cin, cout, H, W, B, 0),
            lambda: L.check(L.lib().nq_conv_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(ws), B, cin, H, W, cout, k,
-                                                 0, _stream()), "conv_wgrad"))
+                                                 _seg_ref(seg), _stream()), "conv_wgrad"))
+    if seg is not None:
+        defer.add(seg, ws, dw, db)
     return dw, db
 
 
@@ -1289,7 +1284,8 @@ def plan_decoder(spec, wshapes, has_bias, B, H, W, want_emb_grad):
     # Which tensors travel as split {hi | lo} words (NQ_SPLIT_IO=0: none): the input x_l of layer l (l >= 2: written by the
     # GELU epilogue of layer l - 1, read by layer l's forward patch staging and by its weight gradient) and the conv-output
     # gradient g_l (written by the data gradient of layer l + 1, read by layer l's weight gradient and data gradient) --
-    # where EVERY kernel on both sides takes / writes that form.  Same values in the matrix pipe: identical results.
+    # where EVERY kernel on both sides takes / writes that form.  Same values in the matrix pipe: identical results, except
+    # that a weight gradient sums the bias gradient db from hi + lo of a split g_l (~2^-17 relative to the float path).
     split_on = use3 and os.environ.get("NQ_SPLIT_IO", "1") != "0"
     for l, p in enumerate(plan):
         below_act = l > 0 and plan[l - 1].act

@@ -20,7 +20,7 @@ def test_header_symbols_exported():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in nq_hip.h but not exported"
     assert declared == set(_lib.EXPORTS)
-    assert lib.nq_abi_version() == 5 == _lib.ABI_VERSION
+    assert lib.nq_abi_version() == 6 == _lib.ABI_VERSION
     assert lib.nq_error_string(-1) == b"invalid argument"
     # ... and nothing else: the library is built with -fvisibility=hidden, only NQ_API declarations are dynamic symbols
     import shutil
@@ -39,7 +39,7 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert lib.nq_fwht(ctypes.c_void_p(16), ctypes.c_void_p(32), 1, 12, 1, 12, 12, n) == -1      # not a power of two
     assert lib.nq_fwht(ctypes.c_void_p(16), ctypes.c_void_p(32), 1, 2048, 1, 8, 8, n) == -2      # too long
     assert lib.nq_conv_forward(ctypes.c_void_p(16), ctypes.c_void_p(16), n, ctypes.c_void_p(16), n, n, 1, 4, 8, 8, 4, 7, 196,
-                               16, 1, 0, 0, n, n) == -2                                       # k=7 not built
+                               16, 1, 0, n, n) == -2                                          # k=7 not built
     assert lib.nq_conv_forward_ws_floats(2, 44, 320, 640, 148, 5) == 0                        # enough tiles: no split-K
     assert lib.nq_conv_forward_ws_floats(2, 848, 40, 80, 64, 5) > 0                           # dec3 data gradient: split-K
     kr, ld = ctypes.c_int(), ctypes.c_int()
@@ -49,6 +49,33 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert kr.value == 56 * 25 and ld.value == 176
     assert lib.nq_conv_wgrad_ws_floats(2, 44, 320, 640, 148, 5) > 0
     assert lib.nq_reduce_ws_floats(4096 * 3 + 1) == 4
+
+
+def test_abi_v6_one_weight_gradient_entry_per_kernel_family():
+    """ABI v6, host-only: the five *_slabs / *_fmt entries are gone, every listed export resolves, and the three surviving
+    launch entries check their arguments before the device is touched -- with and without a pending-reduction record."""
+    from neuroquant_amd import _lib
+    lib = _lib.lib()
+    for name in ("nq_conv_wgrad_slabs", "nq_conv_wgrad3_fmt", "nq_conv_wgrad3_slabs", "nq_conv_wgrad3_slabs_fmt",
+                 "nq_conv_wgrad3_swapped_slabs"):
+        assert name not in _lib.EXPORTS and not hasattr(lib, name), name
+    for name in _lib.EXPORTS:
+        assert getattr(lib, name)
+    n, p = None, ctypes.c_void_p(16)
+    for seg in (None, ctypes.byref(_lib.WgrSeg())):
+        entries = [lambda x, dy, dw, ws, B, k: lib.nq_conv_wgrad(x, dy, dw, n, ws, B, 4, 8, 8, 4, k, seg, n),
+                   lambda x, dy, dw, ws, B, k: lib.nq_conv_wgrad3(x, dy, dw, n, ws, B, 4, 8, 8, 4, k, 0, seg, n),
+                   lambda x, dy, dw, ws, B, k: lib.nq_conv_wgrad3_swapped(x, dy, dw, ws, B, 4, 8, 8, 4, k, seg, n)]
+        for f in entries:
+            for args in [(n, p, p, p), (p, n, p, p), (p, p, n, p), (p, p, p, n)]:
+                assert f(*args, 1, 3) == -1                 # a null operand
+            assert f(p, p, p, p, 0, 3) == -1                # a non-positive size
+            assert f(p, p, p, p, 1, 7) == -2                # k = 7 not built
+    # a split-word format on a shape whose kernel does not take it: refused (here the 4-wave kernel and a few-pixel layer)
+    for shape in [(2, 36, 20, 40, 384, 3), (2, 77, 10, 20, 1024, 3)]:
+        B, cin, H, W, cout, k = shape
+        assert lib.nq_conv_wgrad3_split_io(*shape) == 0
+        assert lib.nq_conv_wgrad3(p, p, p, n, p, B, cin, H, W, cout, k, 3, n, n) == -2
 
 
 def test_wgrad3_plan_keeps_big_operands_off_the_32bit_offset_kernel():
@@ -114,12 +141,12 @@ def test_split_word_interchange_plan():
     assert lib.nq_conv_wgrad3_split_io(2, 36, 40, 80, 384, 3) == 3      # NeRV dec3: 40 splits instead of 42 keep it on that kernel
     for shape in [(2, 77, 10, 20, 1024, 3), (2, 36, 20, 40, 384, 3), (2, 3, 640, 1280, 37, 3)]:
         assert lib.nq_conv_wgrad3_split_io(*shape) == 0, shape           # few-pixel, 4-wave and the role-swapped head kernels
-    # nq_conv_split_out(B, Cin, H, W, Cout, k, r, epilogue, in_gelu, has_bias): the head's data gradient 3 -> 37 / 3 -> 24, un-shuffle 2
-    assert lib.nq_conv_split_out(2, 3, 640, 1280, 37, 3, 2, 4, 0, 0) == 1
-    assert lib.nq_conv_split_out(2, 3, 640, 1280, 24, 3, 2, 4, 0, 0) == 1
-    assert lib.nq_conv_split_out(2, 3, 640, 1280, 37, 3, 2, 4, 0, 1) == 0   # (a bias: not the data gradient)
-    assert lib.nq_conv_split_out(2, 37, 640, 1280, 3, 3, 1, 2, 0, 1) == 0   # the head forward
-    assert lib.nq_conv_split_out(2, 44, 320, 640, 148, 5, 2, 1, 0, 1) == 0  # an fp32 matrix-pipe layer
+    # nq_conv_split_out(B, Cin, H, W, Cout, k, r, epilogue, has_bias): the head's data gradient 3 -> 37 / 3 -> 24, un-shuffle 2
+    assert lib.nq_conv_split_out(2, 3, 640, 1280, 37, 3, 2, 4, 0) == 1
+    assert lib.nq_conv_split_out(2, 3, 640, 1280, 24, 3, 2, 4, 0) == 1
+    assert lib.nq_conv_split_out(2, 3, 640, 1280, 37, 3, 2, 4, 1) == 0      # (a bias: not the data gradient)
+    assert lib.nq_conv_split_out(2, 37, 640, 1280, 3, 3, 1, 2, 1) == 0      # the head forward
+    assert lib.nq_conv_split_out(2, 44, 320, 640, 148, 5, 2, 1, 1) == 0     # an fp32 matrix-pipe layer
 
 
 def test_ops_refuse_cpu_tensors():

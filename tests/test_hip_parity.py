@@ -459,6 +459,19 @@ def test_wgrad_swapped_roles_small_cout(ops, shape):
     close(dw32, ref, rtol=2e-5, atol=1e-5 * float(ref.abs().max()))
 
 
+@pytest.mark.parametrize("k", (1, 3, 5))
+def test_wgrad_fp32_deferred_reduction_is_bit_identical(ops, k):
+    """ops.conv_wgrad_raw with its reduction deferred to PendingReductions.flush() == the direct call.  k = 1 is a few-pixel
+    stem shape: the compact kernel writes dw / db itself and nothing is pending (seg.nsplit == 0)."""
+    g = torch.Generator().manual_seed(17)
+    x, dy = torch.randn(2, 5, 6, 8, generator=g).to(DEV), torch.randn(2, 8, 6, 8, generator=g).to(DEV)
+    dw, db = ops.conv_wgrad_raw(x, dy, 8, k, True)
+    pend = ops.PendingReductions()
+    dwd, dbd = ops.conv_wgrad_raw(x, dy, 8, k, True, defer=pend)
+    pend.flush()
+    assert torch.equal(dw, dwd) and torch.equal(db, dbd)
+
+
 def test_conv_is_deterministic(ops):
     g = torch.Generator().manual_seed(5)
     x = torch.randn(2, 20, 24, 40, generator=g).to(DEV).requires_grad_(True)

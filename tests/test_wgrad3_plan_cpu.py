@@ -184,6 +184,43 @@ def test_swapped_shapes_fall_back(lib):
             assert _swapped_offered(ops, lib, B, cout, H, W, cin, k)
 
 
+def _parent_rule(lib, B, cin, H, W, cout, k):
+    """ops.conv_wgrad_swapped3_supported as it was written in Python before ABI v6, on the queries it used"""
+    return int(cout <= 4 and cin > 4 and cout * k * k <= 64 and lib.nq_conv_wgrad3_supported(B, cout, H, W, cin, k) == 1
+               and lib.nq_conv_wgrad3_ws_floats(B, cout, H, W, cin, k) > 4)
+
+
+def test_swapped_queries_restate_the_python_rule(lib):
+    """nq_conv_wgrad3_swapped_supported / _ws_floats (ABI v6; arguments of the ORIGINAL layer) against the rule the Python
+    host used to spell out, over the grid of test_swapped_shapes_fall_back (both sides of the few-pixel kernel's thresholds)"""
+    shapes = [(1, 2500, 8, 8, 3, 3), (2, 2432, 8, 16, 3, 3), (2, 2700, 8, 16, 1, 5)]
+    for shape in shapes:                                  # the few-pixel kernel owns the exchanged shape
+        assert lib.nq_conv_wgrad3_swapped_ws_floats(*shape) == 0 and lib.nq_conv_wgrad3_swapped_supported(*shape) == 0
+    for k in (3, 5):
+        for cout in (1, 2, 3, 4, 5):
+            edge = -(-65536 // (cout * k * k))
+            for B, H, W in [(1, 128, 4), (2, 64, 4), (1, 129, 4), (1, 128, 5), (1, 8, 8), (2, 8, 16), (2, 16, 16), (2, 16, 17), (4, 8, 16)]:
+                shapes += [(B, cin, H, W, cout, k) for cin in (edge - 17, edge - 1, edge, edge + 1, edge + 40, 4, 5)]
+    shapes += [(B, cout, H, W, cin, k) for (B, cin, H, W, cout, k), _ in CASES if cin <= 4]
+    yes = no = 0
+    for shape in shapes:
+        B, cin, H, W, cout, k = shape
+        got = lib.nq_conv_wgrad3_swapped_supported(*shape)
+        assert got == _parent_rule(lib, *shape), shape
+        if got:
+            yes += 1
+            assert lib.nq_conv_wgrad3_swapped_ws_floats(*shape) == lib.nq_conv_wgrad3_ws_floats(B, cout, H, W, cin, k) > 4, shape
+        else:
+            no += 1
+    assert yes and no
+    for shape, want in [((2, 37, 640, 1280, 3, 3), 1), ((2, 37, 48, 96, 3, 3), 1),
+                        ((1, 2500, 8, 8, 3, 3), 0),        # the few-pixel kernel owns the exchanged shape
+                        ((2, 37, 48, 96, 5, 3), 0),        # Cout > 4
+                        ((2, 4, 48, 96, 3, 3), 0),         # Cin <= 4
+                        ((2, 37, 48, 96, 3, 5), 0)]:       # Cout * k * k = 75 > 64
+        assert lib.nq_conv_wgrad3_swapped_supported(*shape) == want, shape
+
+
 def test_lean_workspace_kept(lib):
     """the few-pixel layers of both 3M models still leave no slabs: a token workspace"""
     for shape in [(2, 77, 10, 20, 1024, 3), (2, 145, 2, 4, 1800, 3), (2, 72, 10, 20, 576, 3)]:

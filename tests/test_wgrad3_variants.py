@@ -100,10 +100,33 @@ def test_variant(ops, idx):
         assert torch.equal(dws, dwsd)
 
 
+@pytest.mark.parametrize("pc", (1, 12, 14))
+def test_split_word_operands_direct_and_deferred(ops, pc):
+    """fmt = 3 of nq_conv_wgrad3, with and without a pending reduction, on the smallest table row of each row-segment
+    producer/consumer kernel: dw has the bits of the float call, db (summed from hi + lo of dy) stays within the table's bound"""
+    shape, _ = min((c for c in CASES if c[1][2] == pc), key=lambda c: c[0][0] * (c[0][1] + c[0][4]) * c[0][2] * c[0][3])
+    B, cin, H, W, cout, k = shape
+    assert _plan(*shape)[3] == pc and ops.conv_wgrad3_split_io(*shape) == 3
+    x, dy = inputs(shape)
+    ref_db = dy.double().sum((0, 2, 3))       # reference()'s db (anchored in the CPU file), without its dw
+    xg, dyg = x.to(DEV), dy.to(DEV)
+    xs, ds = ops.split_words(xg), ops.split_words(dyg)
+    dw, db = ops.conv_wgrad3_raw(xg, dyg, cout, k, True)
+    dwf, dbf = ops.conv_wgrad3_raw(xs, ds, cout, k, True, fmt=3)
+    pend = ops.PendingReductions()
+    dwd, dbd = ops.conv_wgrad3_raw(xs, ds, cout, k, True, defer=pend, fmt=3)
+    pend.flush()
+    assert torch.equal(dw, dwf) and torch.equal(dw, dwd)
+    assert torch.equal(dbf, dbd)
+    e_db, d_db = _worst(dbf, ref_db, db_bound(ref_db)), _worst(dbf, db.cpu().double(), db_bound(ref_db))
+    print(f"wgrad3 fmt 3 pc {pc} {shape}: db error / bound {e_db:.4f}, db against the float call / bound {d_db:.4f}")
+    assert e_db <= 1.0 and d_db <= 1.0
+
+
 @pytest.mark.parametrize("shape", [(1, 2500, 8, 8, 3, 3), (2, 2432, 8, 16, 3, 3), (2, 2700, 8, 16, 1, 5)])
 def test_swapped_entries_refuse_few_pixel_shapes(ops, shape):
     """(B, cin, H, W, cout, k) of heads whose exchanged problem belongs to the few-pixel kernel: the library sizes a 4-float
-    token for it, and both role-swapped C entries refuse before anything is launched.  The workspace handed over here holds
+    token for it, and the role-swapped C entry refuses, direct and deferred, before anything is launched.  The workspace handed over here holds
     the slabs the launch used to write, so that a regression fails this test instead of writing out of bounds."""
     from neuroquant_amd import _lib
     B, cin, H, W, cout, k = shape
@@ -120,9 +143,9 @@ def test_swapped_entries_refuse_few_pixel_shapes(ops, shape):
     def p(t):
         return ctypes.c_void_p(t.data_ptr())
 
-    assert lib.nq_conv_wgrad3_swapped(p(xg), p(dyg), p(dw), p(ws), B, cin, H, W, cout, k, None) == -2
+    assert lib.nq_conv_wgrad3_swapped(p(xg), p(dyg), p(dw), p(ws), B, cin, H, W, cout, k, None, None) == -2
     seg = _lib.WgrSeg()
-    assert lib.nq_conv_wgrad3_swapped_slabs(p(xg), p(dyg), p(dw), p(ws), B, cin, H, W, cout, k, ctypes.byref(seg), None) == -2
+    assert lib.nq_conv_wgrad3_swapped(p(xg), p(dyg), p(dw), p(ws), B, cin, H, W, cout, k, ctypes.byref(seg), None) == -2
     torch.cuda.synchronize()
     assert float(ws.abs().max()) == 0.0 and bool((dw == 7.0).all())
     # the layer still gets its gradient: the fp32 kernel, where ops._wgrad_plain now sends it
