@@ -40,10 +40,10 @@ typedef void* nq_stream_t; /* hipStream_t */
 #define NQ_ERR_UNSUPPORTED (-2) /* shape outside what the kernels are built for */
 #define NQ_ERR_LAUNCH (-3)      /* HIP reported a launch error */
 
-/* 6.  History: v4 added the fused launches marked "ABI v4" below, v5 the split {hi | lo} word interchange.  v6 only removed:
+/* 7.  History: v4 added the fused launches marked "ABI v4" below, v5 the split {hi | lo} word interchange.  v6 only removed:
  * the *_slabs / *_fmt weight-gradient entries (now the `seg` / `fmt` arguments of nq_conv_wgrad, nq_conv_wgrad3 and
  * nq_conv_wgrad3_swapped), the GELU-on-load option of the fp32 kernels (in_gelu / x_gelu: nothing used it), and the
- * "workspace of the exchanged problem > 4 floats" idiom (now nq_conv_wgrad3_swapped_ws_floats / _supported). */
+ * "workspace of the exchanged problem > 4 floats" idiom (now nq_conv_wgrad3_swapped_ws_floats / _supported).  v7 added nq_conv_forward3_plan. */
 NQ_API int nq_abi_version(void);
 NQ_API const char* nq_error_string(int code);
 
@@ -293,6 +293,28 @@ NQ_API int nq_weight_layout3_multi(const nq_wl3_seg* segs, int nseg, nq_stream_t
 /* nq_weight_layout3_multi + nq_weight_layouts_multi in ONE launch (ABI v4): every operand a decoder needs per iteration, the
  * same bytes as the two calls (which it falls back to when a table does not fit one kernel-argument block). */
 NQ_API int nq_weight_layouts_all(const nq_wl3_seg* segs3, int n3, const nq_wl_seg* segsf, int nf, nq_stream_t stream);
+/* The launch plan nq_conv_forward3 will use for this shape (ABI v7; pure host function, the same for every epilogue): which kernel
+ * and which of its builds, the split over 16-channel chunks and the LDS of the launch.  Answered for every valid shape --
+ * nq_conv_forward3 launches whatever it is handed -- with `supported` = nq_conv3_supported, i.e. whether callers should route
+ * the shape here at all.  A few-pixel shape whose wave-private patches would need more than 160 KiB of LDS is not given to the
+ * few-pixel kernel: it takes the tiled kernel (and is `supported` only where that one fills the chip).
+ * NQ_ERR_INVALID for k outside {3,5}, a non-positive size or out == NULL. */
+#define NQ_CONV3_TILED 1 /* conv_igemm3: 8 x 32-pixel tiles x 16*mi channels per workgroup */
+#define NQ_CONV3_FLAT 2  /* conv_flat3: the pixels of all frames as one flat GEMM dimension (<= 512 pixels, W <= 32) */
+typedef struct nq_conv3_plan {
+  int kernel;          /* NQ_CONV3_TILED or NQ_CONV3_FLAT */
+  int supported;       /* nq_conv3_supported */
+  int split_io;        /* nq_conv3_split_io */
+  int mi;              /* 16*mi = channel tile of the weight operand (nq_weight_layout3) and of the tiled kernel */
+  int waves;           /* tiled: waves per SIMD its build is compiled for (2, or 3 for mi <= 3 on a short K loop); few-pixel: 0 */
+  int flat_nw, flat_nb, flat_mi; /* few-pixel: waves, 16-pixel blocks, 16-channel blocks per workgroup; tiled: 0 */
+  int nsplit;          /* splits of the K loop over workgroups; > 1: slabs in ws, nq_conv_splitk_finish writes y / z */
+  int per_split;       /* 16-channel chunks per split (the last split takes what is left) */
+  int tail;            /* last chunk by the channels c it holds: 0 c > 12 (a full chunk's k-steps), 3 c <= 12, 2 c <= 8, 1 c <= 4 */
+  int lds_bytes;       /* dynamic LDS of the launch ... */
+  int lds_bytes_dgrad; /* ... and with NQ_EPI_DGRAD_GELU (the unsplit tiled kernel with mi <= 4 transposes its tile through LDS) */
+} nq_conv3_plan;
+NQ_API int nq_conv_forward3_plan(int B, int Cin, int H, int W, int Cout, int k, nq_conv3_plan* out);
 NQ_API int nq_conv_forward3(const float* x, const void* wt3, const float* bias, float* y, float* z, const float* zprev, float* ws, int B,
                      int Cin, int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream);
 

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NQ_LIB") or os.path.join(_HERE, "libnqhip.so")
 
 NQ_OK = 0
-ABI_VERSION = 6   # nq_abi_version() of the library this binding was written against (include/nq_hip.h)
+ABI_VERSION = 7   # nq_abi_version() of the library this binding was written against (include/nq_hip.h)
 EPI_PLAIN, EPI_PS_GELU, EPI_TANH, EPI_PS, EPI_DGRAD_GELU = 0, 1, 2, 3, 4
 
 
@@ -52,6 +52,12 @@ class WgrSeg(Structure):
     """nq_wgr_seg (include/nq_hip.h): one pending slab reduction."""
     _fields_ = [("slab", c_void_p), ("slab_db", c_void_p), ("dw", c_void_p), ("db", c_void_p), ("Cout", c_int), ("N", c_int),
                 ("co_pad", c_int), ("n_pad", c_int), ("nsplit", c_int), ("swap_kk", c_int), ("sg", c_int)]
+
+
+class Conv3Plan(Structure):
+    """nq_conv3_plan (include/nq_hip.h): what nq_conv_forward3 launches for a shape."""
+    _fields_ = [(n, c_int) for n in ("kernel", "supported", "split_io", "mi", "waves", "flat_nw", "flat_nb", "flat_mi", "nsplit",
+                                     "per_split", "tail", "lds_bytes", "lds_bytes_dgrad")]
 
 
 class FqFwhtSeg(Structure):
@@ -128,6 +134,7 @@ def _load():
     sig("nq_weight_layouts_multi", I, POINTER(WLSeg), I, P)
     sig("nq_weight_layouts_all", I, POINTER(WL3Seg), I, POINTER(WLSeg), I, P)
     sig("nq_conv_forward3_ws_floats", L, I, I, I, I, I, I)
+    sig("nq_conv_forward3_plan", I, I, I, I, I, I, I, POINTER(Conv3Plan))
     sig("nq_conv_forward3", I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P)
     sig("nq_conv_wgrad3_supported", I, I, I, I, I, I, I)
     sig("nq_conv_wgrad3_ws_floats", L, I, I, I, I, I, I)
@@ -162,7 +169,7 @@ EXPORTS = (
     "nq_abi_version", "nq_error_string", "nq_scale_init_max", "nq_uaq_forward", "nq_uaq_backward",
     "nq_adaround_init", "nq_adaround_forward", "nq_adaround_backward", "nq_reduce_ws_floats", "nq_round_loss", "nq_round_loss_backward",
     "nq_adam_step", "nq_adaround_adam_multi", "nq_adaround_forward_multi", "nq_uaq_forward_multi", "nq_uaq_backward_multi", "nq_adaround_backward_multi", "nq_adam_step_multi", "nq_step_prologue", "nq_step_prologue_gather", "nq_adaround_backward_multi_dyn", "nq_adam_step_multi_dyn", "nq_fwht", "nq_fwht_multi", "nq_weight_layouts", "nq_conv_operand_dims", "nq_conv_forward_ws_floats", "nq_conv_forward",
-    "nq_conv3_supported", "nq_conv3_weight_bytes", "nq_weight_layout3", "nq_weight_layout3_multi", "nq_weight_layouts_multi", "nq_conv_forward3_ws_floats", "nq_conv_forward3",
+    "nq_conv3_supported", "nq_conv3_weight_bytes", "nq_weight_layout3", "nq_weight_layout3_multi", "nq_weight_layouts_multi", "nq_conv_forward3_ws_floats", "nq_conv_forward3_plan", "nq_conv_forward3",
     "nq_conv_wgrad3_supported", "nq_conv_wgrad3_ws_floats", "nq_conv_wgrad3_plan", "nq_conv_wgrad3", "nq_conv_wgrad3_swapped",
     "nq_conv_wgrad3_swapped_ws_floats", "nq_conv_wgrad3_swapped_supported", "nq_wgrad_reduce_multi",
     "nq_conv_wgrad_ws_floats", "nq_conv_wgrad", "nq_ps_gelu_backward", "nq_tanh_out_backward", "nq_l2_loss",

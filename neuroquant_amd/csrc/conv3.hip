@@ -15,7 +15,11 @@ int nq_conv3_nst8_k3();
 int nq_conv3_nst8_k5();
 int nq_conv3_nstk_k3(int);
 int nq_conv3_nstk_k5(int);
-int nq_conv_flat3_plan(int, int, int, int, int, int, int*, int*, int*, int*);
+int nq_conv_flat3_plan(int, int, int, int, int, int, NqFlat3Plan*);
+int nq_conv3_waves_k3(int, int, int, int, int);
+int nq_conv3_waves_k5(int, int, int, int, int);
+int nq_conv3_lds_k3(int, int, int);
+int nq_conv3_lds_k5(int, int, int);
 int nq_conv_flat3(const float*, const void*, const float*, float*, float*, const float*, float*, int, int, int, int, int, int, int, int,
                   int, int, int, int, hipStream_t);
 int nq_conv_wgrad_flat3_ok(int, int, int, int, int, int);
@@ -239,10 +243,12 @@ inline Fwd3Plan plan_fwd3(int B, int Cin, int H, int W, int Cout) {
 // finish launch), or when the tiled kernel's grid would not fill the chip even with split-K (it would fall back to the fp32
 // kernels).  Long K loops that the tiled split-K path already handles stay there: measured (us, kernel + finish) HNeRV dec2
 // data gradient 21.0 flat vs 21.7 tiled, NeRV dec1 data gradient 22.4 vs 18.7, NeRV dec2 data gradient 19.3 vs 25.6 (fp32).
-inline bool use_flat3(int B, int Cin, int H, int W, int Cout, int k, int* fns) {
-  int ns = 1;
-  if (!nq_conv_flat3_plan(B, Cin, H, W, Cout, k, nullptr, nullptr, &ns, nullptr)) return false;
+inline bool use_flat3(int B, int Cin, int H, int W, int Cout, int k, int* fns, NqFlat3Plan* fp = nullptr) {
+  NqFlat3Plan pl;
+  if (!nq_conv_flat3_plan(B, Cin, H, W, Cout, k, &pl)) return false;
+  const int ns = pl.nsplit;
   if (fns) *fns = ns;
+  if (fp) *fp = pl;
   if (ns == 1) return true;
   const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
   return p.wgs * p.nsplit < 128;
@@ -589,13 +595,41 @@ int nq_conv3_split_io(int B, int Cin, int H, int W, int Cout, int k) {
   return (p.mi >= 2 ? NQ_EPI_X_SPLIT : 0) | (p.nsplit == 1 ? NQ_EPI_Y_SPLIT : 0);
 }
 
+int nq_conv_forward3_plan(int B, int Cin, int H, int W, int Cout, int k, nq_conv3_plan* out) {
+  if (!(k == 3 || k == 5) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || !out) return NQ_ERR_INVALID;
+  nq_conv3_plan q{};
+  q.supported = nq_conv3_supported(B, Cin, H, W, Cout, k);
+  q.split_io = nq_conv3_split_io(B, Cin, H, W, Cout, k);
+  q.mi = pick_mi3(Cout);
+  q.tail = tail_kind_of(Cin, q.mi);
+  // the same questions, in the same order, as nq_conv_forward3 below
+  NqFlat3Plan fp;
+  if (use_flat3(B, Cin, H, W, Cout, k, nullptr, &fp)) {
+    q.kernel = NQ_CONV3_FLAT;
+    q.flat_nw = fp.nw; q.flat_nb = fp.nb; q.flat_mi = fp.mi;
+    q.nsplit = fp.nsplit; q.per_split = fp.per_split;
+    q.lds_bytes = q.lds_bytes_dgrad = fp.lds_bytes;
+  } else {
+    const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
+    const int nchunk = (Cin + CC - 1) / CC;
+    q.kernel = NQ_CONV3_TILED;
+    q.nsplit = p.nsplit; q.per_split = p.per;
+    q.waves = k == 3 ? nq_conv3_waves_k3(p.mi, nchunk, q.tail, p.nsplit, p.per) : nq_conv3_waves_k5(p.mi, nchunk, q.tail, p.nsplit, p.per);
+    q.lds_bytes = k == 3 ? nq_conv3_lds_k3(p.mi, NQ_EPI_PLAIN, p.nsplit) : nq_conv3_lds_k5(p.mi, NQ_EPI_PLAIN, p.nsplit);
+    q.lds_bytes_dgrad = k == 3 ? nq_conv3_lds_k3(p.mi, NQ_EPI_DGRAD_GELU, p.nsplit) : nq_conv3_lds_k5(p.mi, NQ_EPI_DGRAD_GELU, p.nsplit);
+  }
+  *out = q;
+  return NQ_OK;
+}
+
 int nq_conv_forward3(const float* x, const void* wt3, const float* bias, float* y, float* z, const float* zprev, float* ws, int B,
                      int Cin, int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream) {
-  if (!x || !wt3 || (!y && epilogue != NQ_EPI_PS) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
-  if (!(k == 3 || k == 5)) return NQ_ERR_UNSUPPORTED;
   // split {hi | lo} word interchange (include/nq_hip.h: NQ_EPI_X_SPLIT / NQ_EPI_Y_SPLIT): only where nq_conv3_split_io says so
+  // (taken off before the epilogue is looked at: NQ_EPI_PS | NQ_EPI_X_SPLIT with y == NULL was refused as invalid)
   const int fmt = epilogue & (NQ_EPI_X_SPLIT | NQ_EPI_Y_SPLIT);
   epilogue &= ~(NQ_EPI_X_SPLIT | NQ_EPI_Y_SPLIT);
+  if (!x || !wt3 || (!y && epilogue != NQ_EPI_PS) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
+  if (!(k == 3 || k == 5)) return NQ_ERR_UNSUPPORTED;
   if (fmt & ~nq_conv3_split_io(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
   if (epilogue < 0 || epilogue > NQ_EPI_DGRAD_GELU) return NQ_ERR_INVALID;
   if ((epilogue == NQ_EPI_PS_GELU || epilogue == NQ_EPI_PS) && (!z || r <= 0 || Cout % (r * r) != 0)) return NQ_ERR_INVALID;

@@ -29,3 +29,13 @@ __host__ __device__ __forceinline__ void wl3_elem(int kind, int KK, int s, int k
     tap = 2 * s + (kq >> 1);
   }
 }
+
+// Launch plan of the few-pixel kernel (nq_conv_flat3_plan, conv_flat3.hip): everything its launch derives from the shape, so
+// that the queries of conv3.hip (supported / workspace / split words / nq_conv_forward3_plan) and the launch agree by construction.
+struct NqFlat3Plan {
+  int nw, nb, mi;            // template instantiation: waves per workgroup, 16-pixel blocks and 16-channel blocks per workgroup
+  int nsplit, per_split;     // workgroup-level split over 16-channel chunks
+  int ngroups, cgroups;      // pixel groups (16*nb pixels) and channel groups (16*mi channels) of the grid
+  int ppix;                  // 16-byte units per (plane, octet) of a wave's patch
+  int lds_bytes;             // dynamic LDS of the launch: wave-private patches, re-used by the cross-wave reduction
+};

@@ -319,11 +319,18 @@ __global__ __launch_bounds__(NW * 64) void conv_flat3_kernel(FlatArgs a) {
 
 #define KS_MI2_OK(k_) ((k_) == 3)   /* two fragment sets of a 5 x 5 chunk (52 x 4 registers) do not fit */
 
+// dynamic LDS of a launch: NW wave-private patches [plane][octet][ppix] of 16-byte units, re-used as [wave][MI*NB][4][64] floats
+// by the cross-wave reduction
+constexpr size_t FLAT3_LDS_MAX = 160 * 1024;
+inline size_t flat3_lds_bytes(int nw, int mi, int nb, int ppix) {
+  const size_t patch_b = (size_t)nw * 4 * ppix * 16, red_b = (size_t)nw * mi * nb * 4 * 64 * 4;
+  return patch_b > red_b ? patch_b : red_b;
+}
+
 template <int KS, int NW, int MI, int NB>
 int launch_flat3(const FlatArgs& a, hipStream_t st) {
-  const size_t patch_b = (size_t)NW * 4 * a.ppix * 16, red_b = (size_t)NW * MI * NB * 4 * 64 * 4;
-  const size_t lds = patch_b > red_b ? patch_b : red_b;
-  if (lds > 160 * 1024) return NQ_ERR_UNSUPPORTED;
+  const size_t lds = flat3_lds_bytes(NW, MI, NB, a.ppix);
+  if (lds > FLAT3_LDS_MAX) return NQ_ERR_UNSUPPORTED;   // (nq_conv_flat3_plan does not offer such shapes)
   if (int rc = nq_lds_optin<&conv_flat3_kernel<KS, NW, MI, NB>>(lds)) return rc;
   hipLaunchKernelGGL((conv_flat3_kernel<KS, NW, MI, NB>), dim3((unsigned)(a.ngroups * a.cgroups * a.nsplit)), dim3(NW * 64), lds, st, a);
   return nq_launch_status();
@@ -332,19 +339,22 @@ int launch_flat3(const FlatArgs& a, hipStream_t st) {
 }  // namespace
 
 // Launch plan of the few-pixel kernel for a (Cin -> Cout, k) convolution over B frames of H x W (pure host function, shared
-// with conv3.hip): returns 0 when the shape is not one of its shapes.
-extern "C" int nq_conv_flat3_plan(int B, int Cin, int H, int W, int Cout, int k, int* nw, int* nb, int* nsplit, int* per_split) {
+// with conv3.hip): returns 0 when the shape is not one of its shapes -- more than 512 pixels, rows wider than 32, or
+// wave-private patches that do not fit the LDS of a workgroup (many waves x tall patches of wide rows at k = 5).
+extern "C" int nq_conv_flat3_plan(int B, int Cin, int H, int W, int Cout, int k, NqFlat3Plan* out) {
   static const int enabled = [] { const char* e = getenv("NQ_FLAT3"); return !(e && e[0] == '0'); }();
   if (!enabled || !(k == 3 || k == 5) || B <= 0 || Cin <= 4 || Cout <= 4 || H <= 0 || W <= 0) return 0;
-  const int64_t P = (int64_t)B * H * W;
-  if (P > 512 || W > 32 || (int64_t)B * Cin * H * W * 4 >= 0x7FFFFF00ll) return 0;
+  const int64_t P64 = (int64_t)B * H * W;
+  if (P64 > 512 || W > 32 || (int64_t)B * Cin * H * W * 4 >= 0x7FFFFF00ll) return 0;
+  const int P = (int)P64;
   const int NBv = P > 16 ? 5 : 1;
   const int nchunk = (Cin + 15) / 16;
   // waves per workgroup = K-splits inside it; 16 only with single-block patches (16 wave-private patches of a 5-block group
   // would not fit the LDS)
   // (16 waves = 128 VGPRs per lane: only with the 10 weight fragments of a 3 x 3 chunk in flight, not the 26 of a 5 x 5 one)
   const int NWv = (nchunk > 8 && NBv == 1 && k == 3) ? 16 : (nchunk > 4 ? 8 : 4);
-  const int ngroups = (int)((P + 16 * NBv - 1) / (16 * NBv)), cgroups = (Cout + 15) / 16;
+  const int ngroups = (P + 16 * NBv - 1) / (16 * NBv);
+  int cgroups = (Cout + 15) / 16;
   // workgroup-level split of long K loops (data gradients) while the grid is small: <= ~4 chunks per wave, <= ~512 workgroups
   static const int max_per_wave = [] { const char* e = getenv("NQ_FLAT3_CPW"); return e ? atoi(e) : 1; }();
   int ns = 1;
@@ -358,18 +368,32 @@ extern "C" int nq_conv_flat3_plan(int B, int Cin, int H, int W, int Cout, int k,
   int per = (nchunk + ns - 1) / ns;
   per = (per + NWv - 1) / NWv * NWv;          // whole rounds of the waves
   ns = (nchunk + per - 1) / per;
-  if (nw) *nw = NWv;
-  if (nb) *nb = NBv;
-  if (nsplit) *nsplit = ns;
-  if (per_split) *per_split = per;
+  // largest patch of any pixel group: rows from the first to the last pixel of the group in the stack of padded frames
+  const int pad = k / 2, VH = H + 2 * pad, PW = W + 2 * pad, HW = H * W;
+  int maxrows = 0;
+  for (int g = 0; g < ngroups; ++g) {
+    const int p0 = g * 16 * NBv, p1 = (p0 + 16 * NBv < P ? p0 + 16 * NBv : P) - 1;
+    const int v0 = (p0 / HW) * VH + (p0 % HW) / W, v1 = (p1 / HW) * VH + (p1 % HW) / W;
+    if (v1 - v0 + 1 + 2 * pad > maxrows) maxrows = v1 - v0 + 1 + 2 * pad;
+  }
+  const int ppix = (maxrows * PW + 3) / 4 * 4;
+  // 32 channels per workgroup (two A-fragment sets per wave) when 16 would need more than one workgroup per CU: the
+  // wave-private patches of a 5-block group allow one resident workgroup per CU, and a second round costs a whole
+  // workgroup latency (HNeRV dec2 forward: 320 workgroups of 16 channels 31 us, 160 of 32 ...)
+  const int MIv = (NBv == 5 && cgroups * ngroups * ns > 256 && KS_MI2_OK(k)) ? 2 : 1;
+  if (MIv == 2) cgroups = (Cout + 31) / 32;
+  const size_t lds = flat3_lds_bytes(NWv, MIv, NBv, ppix);
+  if (lds > FLAT3_LDS_MAX) return 0;
+  if (out) *out = NqFlat3Plan{NWv, NBv, MIv, ns, per, ngroups, cgroups, ppix, (int)lds};
   return 1;
 }
 
 extern "C" int nq_conv_flat3(const float* x, const void* wt3, const float* bias, float* y, float* z, const float* zprev, float* slab,
                              int B, int Cin, int H, int W, int Cout, int k, int r, int epi, int MT, int tail, int NST, int NSTT,
                              hipStream_t st) {
-  int NWv, NBv, ns, per;
-  if (!nq_conv_flat3_plan(B, Cin, H, W, Cout, k, &NWv, &NBv, &ns, &per)) return NQ_ERR_UNSUPPORTED;
+  NqFlat3Plan pl;
+  if (!nq_conv_flat3_plan(B, Cin, H, W, Cout, k, &pl)) return NQ_ERR_UNSUPPORTED;
+  const int NWv = pl.nw, NBv = pl.nb, MIv = pl.mi, ns = pl.nsplit, per = pl.per_split;
   FlatArgs a{};
   a.x = x; a.wt3 = reinterpret_cast<const u32x4*>(wt3); a.bias = bias; a.y = y; a.z = z; a.zprev = zprev; a.slab = slab;
   // bit 9 of `epi` (NQ_EPI_Y_SPLIT): y is written as split {hi | lo} words (nq_common.h) -- only without split-K
@@ -380,27 +404,14 @@ extern "C" int nq_conv_flat3(const float* x, const void* wt3, const float* bias,
   a.P = B * H * W;
   a.MT = MT; a.co_tiles = (Cout + MT - 1) / MT;
   a.nchunk = (Cin + 15) / 16; a.tail = tail; a.NST = NST; a.NSTT = NSTT;
-  a.ngroups = (a.P + 16 * NBv - 1) / (16 * NBv);
-  a.cgroups = (Cout + 15) / 16;
+  a.ngroups = pl.ngroups;
+  a.cgroups = pl.cgroups;
   a.nsplit = ns; a.per_split = per;
   a.x_bytes = (unsigned)((int64_t)B * Cin * H * W * 4);
   a.dHW = make_fdiv(H * W); a.dW = make_fdiv(W); a.dR = make_fdiv(r > 0 ? r : 1); a.dRR = make_fdiv(r > 0 ? r * r : 1);
   if (ns > 1 && !slab) return NQ_ERR_INVALID;
-  // largest patch of any pixel group: rows from the first to the last pixel of the group in the stack of padded frames
-  const int pad = k / 2, VH = H + 2 * pad, PW = W + 2 * pad, HW = H * W;
-  int maxrows = 0;
-  for (int g = 0; g < a.ngroups; ++g) {
-    const int p0 = g * 16 * NBv, p1 = (p0 + 16 * NBv < a.P ? p0 + 16 * NBv : a.P) - 1;
-    const int v0 = (p0 / HW) * VH + (p0 % HW) / W, v1 = (p1 / HW) * VH + (p1 % HW) / W;
-    if (v1 - v0 + 1 + 2 * pad > maxrows) maxrows = v1 - v0 + 1 + 2 * pad;
-  }
-  a.ppix = (maxrows * PW + 3) / 4 * 4;
-  a.dVH = make_fdiv(VH); a.dNQ = make_fdiv((PW + 3) / 4);
-  // 32 channels per workgroup (two A-fragment sets per wave) when 16 would need more than one workgroup per CU: the
-  // wave-private patches of a 5-block group allow one resident workgroup per CU, and a second round costs a whole
-  // workgroup latency (HNeRV dec2 forward: 320 workgroups of 16 channels 31 us, 160 of 32 ...)
-  const int MIv = (NBv == 5 && a.cgroups * a.ngroups * ns > 256 && KS_MI2_OK(k)) ? 2 : 1;
-  if (MIv == 2) a.cgroups = (Cout + 31) / 32;
+  a.ppix = pl.ppix;
+  a.dVH = make_fdiv(H + 2 * (k / 2)); a.dNQ = make_fdiv((W + 2 * (k / 2) + 3) / 4);
   a.dNG = make_fdiv(a.ngroups); a.dCG = make_fdiv(a.cgroups);
 #define NQ_FLAT_CASE(NW_, NB_)                                                           \
   if (NWv == NW_ && NBv == NB_ && MIv == 1) return k == 3 ? launch_flat3<3, NW_, 1, NB_>(a, st) : launch_flat3<5, NW_, 1, NB_>(a, st);

@@ -768,23 +768,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   });
 }
 
+// Which build of a tile a launch takes (waves per SIMD the registers are allocated for): 3 for the tiles of <= 48 channels on
+// a short K loop (NQ_IG3_OCC3_STEPS: largest k-step count that takes it; 0 = never), else 2.  ONE rule per kernel size, shared
+// by launch_igemm3 and the plan query (nq_conv_forward3_plan, conv3.hip).
+inline int igemm3_waves(int mi, int nchunk, int tail, int nsplit, int per_split) {
+  if (mi > 3) return 2;
+  static const int occ3_steps = [] { const char* e = getenv("NQ_IG3_OCC3_STEPS"); return e ? atoi(e) : NQ_IG3_OCC3_DEFAULT; }();
+  const int ksteps = (nsplit > 1 ? per_split : nchunk - 1) * NST + (nsplit > 1 ? 0 : nst_of_kind(tail));
+  return ksteps <= occ3_steps ? 3 : 2;
+}
+// Dynamic LDS of a launch; wide_epi: the data-gradient epilogue transposes through 4 waves x [MT][64] floats
+inline size_t igemm3_lds_bytes(int mi, bool wide_epi) {
+  const int MT = 16 * mi;
+  size_t lds = (size_t)(PATCH_U4 + 2 * 2 * 4 * MT) * 16;   // patch + two weight buffers (register-staged tiles)
+  if (mi >= 3) lds = (size_t)(PATCH_U4 + 4 * (2 * 4 * MT)) * 16;  // DMA ring of 4
+  if (wide_epi && lds < (size_t)MT * 1024) lds = (size_t)MT * 1024;
+  return lds;
+}
+// the wide data-gradient epilogue: tiles of <= 64 channels that write their own output (the kernel also wants W % 4 == 0)
+inline bool igemm3_wide_epi(int mi, int epi, int nsplit) { return epi == NQ_EPI_DGRAD_GELU && nsplit == 1 && mi <= 4; }
+
 template <int MI, bool XS = false>
 int launch_igemm3(const Conv3Args& a_in, int tiles, hipStream_t st) {
-  constexpr int MT = 16 * MI;
-  size_t lds = (size_t)(PATCH_U4 + 2 * 2 * 4 * MT) * 16;   // patch + two weight buffers (register-staged tiles)
-  if (MI >= 3) lds = (size_t)(PATCH_U4 + 4 * (2 * 4 * MT)) * 16;  // DMA ring of 4
   Conv3Args a = a_in;
-  a.lds_epi = 0;
-  if (a.epi == NQ_EPI_DGRAD_GELU && a.nsplit == 1 && MI <= 4) {   // 4 waves x [MT][64] floats for the wide epilogue
-    a.lds_epi = 1;
-    if (lds < (size_t)MT * 1024) lds = (size_t)MT * 1024;
-  }
+  a.lds_epi = igemm3_wide_epi(MI, a.epi, a.nsplit) ? 1 : 0;
+  const size_t lds = igemm3_lds_bytes(MI, a.lds_epi != 0);
   a.tiles = tiles;
   if constexpr (MI <= 3) {
-    // short K loop -> the three-waves-per-SIMD build (NQ_IG3_OCC3_STEPS: largest k-step count that takes it; 0 = never)
-    static const int occ3_steps = [] { const char* e = getenv("NQ_IG3_OCC3_STEPS"); return e ? atoi(e) : NQ_IG3_OCC3_DEFAULT; }();
-    const int ksteps = (a.nsplit > 1 ? a.per_split : a.nchunk - 1) * NST + (a.nsplit > 1 ? 0 : nst_of_kind(a.tail));
-    if (ksteps <= occ3_steps) {
+    if (igemm3_waves(MI, a.nchunk, a.tail, a.nsplit, a.per_split) == 3) {   // short K loop
       if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 3, XS>>(lds)) return rc;
       hipLaunchKernelGGL((conv_igemm3_kernel<MI, 3, XS>), dim3((unsigned)(tiles * a.co_tiles * a.B * a.nsplit)), dim3(256), lds, st, a);
       return nq_launch_status();
@@ -842,3 +853,10 @@ extern "C" int NQ_CAT(nq_conv_igemm3_k, NQ_KS)(const float* x, const void* wt3, 
 extern "C" int NQ_CAT(nq_conv3_nst_k, NQ_KS)() { return NST; }
 extern "C" int NQ_CAT(nq_conv3_nst8_k, NQ_KS)() { return NST8; }
 extern "C" int NQ_CAT(nq_conv3_nstk_k, NQ_KS)(int kind) { return nst_of_kind(kind); }
+// launch rules of this kernel size for the plan query (conv3.hip): waves per SIMD of the build, dynamic LDS bytes
+extern "C" int NQ_CAT(nq_conv3_waves_k, NQ_KS)(int mi, int nchunk, int tail, int nsplit, int per_split) {
+  return igemm3_waves(mi, nchunk, tail, nsplit, per_split);
+}
+extern "C" int NQ_CAT(nq_conv3_lds_k, NQ_KS)(int mi, int epi, int nsplit) {
+  return (int)igemm3_lds_bytes(mi, igemm3_wide_epi(mi, epi, nsplit));
+}

@@ -89,7 +89,7 @@ def test_c_entry_points_reject_bad_arguments_without_a_gpu():
     from neuroquant_amd import _lib
     lib = _lib.lib()
     assert "nq_ms_ssim" in _lib.EXPORTS and "nq_ms_ssim_ws_floats" in _lib.EXPORTS
-    assert lib.nq_abi_version() == 6
+    assert lib.nq_abi_version() == 7
     p, n = ctypes.c_void_p(16), None
     assert lib.nq_ms_ssim(n, p, p, p, 1, 3, 640, 1280, n) == -1
     assert lib.nq_ms_ssim(p, n, p, p, 1, 3, 640, 1280, n) == -1
