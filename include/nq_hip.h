@@ -445,6 +445,29 @@ NQ_API int nq_act_dd(const float* x, const float* g, const float* g2, float* y, 
 NQ_API int nq_pixel_shuffle(const float* x, float* y, int B, int C, int H, int W, int r, int inverse, nq_stream_t stream);
 NQ_API int nq_bias_add(const float* x, const float* bias, float* y, int B, int C, int64_t HW, nq_stream_t stream);
 
+/* ---- packed bit stream (additions are backward compatible: nq_abi_version() stays 7) ----
+ * Bit order: level i of a b-bit tensor occupies bits [i*b, (i+1)*b) of the stream; bit j of the stream is bit j % 32 of
+ * 32-bit word j / 32 (words are little-endian in a file), so a level straddles two words whenever b does not divide 32.
+ *   nq_packed_words   ceil(n * n_bits / 32); 0 for n <= 0 or n_bits outside 1..8.
+ *   nq_pack_levels    levels (n bytes, one level each; any alignment) -> words (nq_packed_words(n, n_bits), 4-byte aligned).
+ *                     A level is masked to n_bits bits; unused high bits of the last word are zero; every word has exactly
+ *                     one writer (a thread packs 32 levels into n_bits words): no atomics, bit-identical from call to call.
+ *   nq_unpack_dequant w[r][j] = ((float)level[r * row_len + j] - zp[r]) * delta[r], in that order, uncontracted: the expression
+ *                     of nq_uaq_forward / nq_adaround_forward (quantizer.py:117-119, 300), so the weights a player rebuilds are
+ *                     the quantiser's bit for bit.  rows = C_out with one delta / zp per row, rows = 1 for a layer-wise
+ *                     tensor or a bias.  No word at or beyond nq_packed_words(rows * row_len, n_bits) is read.
+ *   nq_frames_to_u8   dst = (uint8) rint(min(max(src, 0), 1) * 255), round to nearest even (torch.round), NaN -> 0.  src is
+ *                     (n, C, HW) fp32; layout 0 writes (n, C, HW) (planar), layout 1 writes (n, HW, C) (interleaved, what
+ *                     image writers take).  16-byte loads and dword stores when src is 16-byte and dst 4-byte aligned and,
+ *                     for layout 1, C == 3 and HW % 4 == 0 (C == 1 is planar); otherwise one byte per thread.
+ * NQ_ERR_INVALID for null pointers, non-positive sizes, n_bits outside 1..8, layout outside {0, 1} and element counts past
+ * int64, all checked before the device is touched; NQ_ERR_UNSUPPORTED for more than 2^31 - 1 workgroups. */
+NQ_API int64_t nq_packed_words(int64_t n, int n_bits);
+NQ_API int nq_pack_levels(const uint8_t* levels, uint32_t* words, int64_t n, int n_bits, nq_stream_t stream);
+NQ_API int nq_unpack_dequant(const uint32_t* words, const float* delta, const float* zp, float* w, int64_t rows, int64_t row_len,
+                      int n_bits, nq_stream_t stream);
+NQ_API int nq_frames_to_u8(const float* src, uint8_t* dst, int64_t n, int C, int64_t HW, int layout, nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

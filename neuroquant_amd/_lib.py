@@ -162,6 +162,10 @@ def _load():
     sig("nq_act_dd", I, P, P, P, P, L, I, P)
     sig("nq_pixel_shuffle", I, P, P, I, I, I, I, I, I, P)
     sig("nq_bias_add", I, P, P, P, I, I, L, P)
+    sig("nq_packed_words", L, L, I)
+    sig("nq_pack_levels", I, P, P, L, I, P)
+    sig("nq_unpack_dequant", I, P, P, P, P, L, L, I, P)
+    sig("nq_frames_to_u8", I, P, P, L, I, L, I, P)
     return lib
 
 
@@ -177,6 +181,7 @@ EXPORTS = (
     "nq_act_dd", "nq_pixel_shuffle", "nq_bias_add", "nq_conv3_split_io", "nq_conv_split_out", "nq_split_words",
     "nq_conv_wgrad3_split_io", "nq_head_forward_loss_ws_floats", "nq_head_forward_loss",
     "nq_adaround_fwht_multi", "nq_fwht_adaround_adam_multi", "nq_weight_layouts_all",
+    "nq_packed_words", "nq_pack_levels", "nq_unpack_dequant", "nq_frames_to_u8",
 )
 
 _lib = None

@@ -9,7 +9,8 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     python -m neuroquant_amd.methods.calibrate_network --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny \
         --ckpt epoch300.pth --batch_size 2 --channel_wise --init max --iters_w 21000 --weight 0.01 --b_start 20 \
         --b_end 2 --warmup 0.2 --lr 0.003 --precision 6 5 4 5 5 6 6
-    (--synthetic N uses N synthetic Bunny-shaped frames instead of --data_path)
+    (--synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --export_stream FILE.nqv also writes the
+    calibrated model as a packed bit stream that `python -m neuroquant_amd.methods.decode_stream` plays back)
 """
 import argparse
 import logging
@@ -55,6 +56,8 @@ def parse_args(argv):
     p.add_argument('--opt_mode', default='mse', type=str, choices=['mse', 'fisher_diag', 'fisher_full', 'lp_norm'])
     p.add_argument('--ckpt', default='None', type=str)
     p.add_argument('--dump_vis', action='store_true', default=False)
+    p.add_argument('--export_stream', type=str, default=None,
+                   help='write the calibrated model as a packed bit stream (.nqv, neuroquant_amd/bitstream.py) to this path')
     return p.parse_args(argv)
 
 
@@ -219,6 +222,12 @@ def calibrate(args, cfg):
     tag = 'CW' if args.channel_wise else 'LW'
     if rank == 0:
         torch.save(qnn, "{}/{}_W{}_prob{}_{}-init_{}.pth".format(args.outf, args.arch, args.qbits, args.input_prob, args.init, tag))
+        if getattr(args, 'export_stream', None):
+            from ..bitstream import write_stream
+            s = write_stream(qnn, args.export_stream, args.arch, cfg, frames=n,
+                             embeddings=cali_data if args.arch == 'hnerv' else None)
+            logging.info('bit stream: {} ({} bytes, {} bpp; nominal {} bytes)'.format(
+                args.export_stream, s['file_bytes'], round(s.get('bpp', float('nan')), 5), s['total_bytes_nominal']))
     args.qnn = qnn
     return res
 

@@ -1715,3 +1715,64 @@ def gather_frames_u8(frames_u8: torch.Tensor, idx: torch.Tensor) -> torch.Tensor
     out = torch.empty((n,) + tuple(frames_u8.shape[1:]), device=frames_u8.device, dtype=torch.float32)
     L.check(L.lib().nq_gather_frames_u8(_p(frames_u8), _p(idx), _p(out), n, flen, _stream()), "gather_frames")
     return out
+
+
+# ------------------------------------------------------------------------------------------ packed bit stream
+def packed_words(n: int, n_bits: int) -> int:
+    """32-bit words that n levels of n_bits bits occupy (0 for n <= 0 or n_bits outside 1..8)."""
+    return int(L.lib().nq_packed_words(int(n), int(n_bits)))
+
+
+def _dev_as(t, dtype, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"neuroquant_amd: {name} must live on the GPU (no CPU fallback exists)")
+    if t.dtype != dtype:
+        raise RuntimeError(f"neuroquant_amd: {name} must be {dtype}, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def pack_levels(levels_u8: torch.Tensor, n_bits: int) -> torch.Tensor:
+    """uint8 levels (any shape, flattened) -> int32 words of the packed stream (bit order: include/nq_hip.h).
+    ValueError for an empty tensor, n_bits outside 1..8 or a level that does not fit n_bits bits."""
+    lv = _dev_as(levels_u8, torch.uint8, "levels").reshape(-1)
+    if not 1 <= int(n_bits) <= 8 or lv.numel() == 0:
+        raise ValueError(f"pack_levels: n_bits must be 1..8 and levels non-empty, got n_bits={n_bits}, {lv.numel()} levels")
+    if int(lv.max()) >= 2 ** int(n_bits):
+        raise ValueError(f"pack_levels: level {int(lv.max())} does not fit {n_bits} bits")
+    words = torch.empty(packed_words(lv.numel(), n_bits), device=lv.device, dtype=torch.int32)
+    L.check(L.lib().nq_pack_levels(_p(lv), _p(words), lv.numel(), int(n_bits), _stream()), "pack_levels")
+    return words
+
+
+def unpack_dequant(words: torch.Tensor, delta: torch.Tensor, zp: torch.Tensor, shape, n_bits: int) -> torch.Tensor:
+    """packed words -> fp32 tensor of `shape`: (level - zp) * delta, the quantisers' own expression.  delta / zp hold one value
+    per shape[0] (channel-wise) or a single value."""
+    words = _dev_as(words, torch.int32, "words")
+    delta, zp = _dev(delta, "delta"), _dev(zp, "zero_point")
+    shape = tuple(int(s) for s in shape)
+    n = math.prod(shape)
+    if not 1 <= int(n_bits) <= 8 or n <= 0:
+        raise ValueError(f"unpack_dequant: n_bits must be 1..8 and the shape non-empty, got n_bits={n_bits}, shape {shape}")
+    if words.numel() < packed_words(n, n_bits):
+        raise ValueError(f"unpack_dequant: {words.numel()} words cannot hold {n} levels of {n_bits} bits")
+    if delta.numel() != zp.numel() or delta.numel() not in (1, shape[0]):
+        raise ValueError("unpack_dequant: delta / zero_point must hold one value per output channel or a single value")
+    rows = delta.numel()
+    w = torch.empty(shape, device=words.device, dtype=torch.float32)
+    L.check(L.lib().nq_unpack_dequant(_p(words), _p(delta), _p(zp), _p(w), rows, n // rows, int(n_bits), _stream()),
+            "unpack_dequant")
+    return w
+
+
+def frames_to_u8(x: torch.Tensor, layout: str = "chw") -> torch.Tensor:
+    """(n, C, H, W) fp32 -> uint8 round(clamp(x, 0, 1) * 255) (nearest even, NaN -> 0): (n, C, H, W) for layout 'chw',
+    (n, H, W, C) for 'hwc' (what image writers take)."""
+    if layout not in ("chw", "hwc"):
+        raise ValueError(f"frames_to_u8: layout must be 'chw' or 'hwc', got {layout!r}")
+    x = _dev(x.detach(), "x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"frames_to_u8 takes a non-empty (n, C, H, W) tensor, got {tuple(x.shape)}")
+    n, C, H, W = x.shape
+    out = torch.empty((n, C, H, W) if layout == "chw" else (n, H, W, C), device=x.device, dtype=torch.uint8)
+    L.check(L.lib().nq_frames_to_u8(_p(x), _p(out), n, C, H * W, 0 if layout == "chw" else 1, _stream()), "frames_to_u8")
+    return out
