@@ -468,6 +468,26 @@ NQ_API int nq_unpack_dequant(const uint32_t* words, const float* delta, const fl
                       int n_bits, nq_stream_t stream);
 NQ_API int nq_frames_to_u8(const float* src, uint8_t* dst, int64_t n, int C, int64_t HW, int layout, nq_stream_t stream);
 
+/* Entropy-coded levels: 64-lane interleaved rANS, one frequency table per tensor (probabilities in units of
+ * 1 / 4096), 32-bit states >= 2^16, 16-bit words.  The n levels (flat, C order) are cut into chunks of `chunk` symbols (a
+ * multiple of 64, the last may be short); lane l of a chunk owns its symbols l, l + 64, ...  One wavefront decodes one chunk.
+ *   nq_rans_chunks   ceil(n / chunk); 0 for n <= 0, chunk <= 0 or chunk not a multiple of 64.  Pure host function.
+ *   nq_rans_decode   words: every chunk's 16-bit words, chunk after chunk; states: 64 per chunk; offsets: chunks + 1 entries,
+ *                    chunk c owns words [offsets[c], offsets[c + 1]); freq: 2^n_bits entries that sum to 4096.  Outputs, either
+ *                    may be NULL but not both: levels[i] (one byte each) and w[i] = ((float)level[i] - zp[i / row_len]) *
+ *                    delta[i / row_len], the expression of the unpacking entry above, so the floats equal the packed path's bit
+ *                    for bit (delta / zp may be NULL when w is).  All pointers are device pointers.  A word index at or past
+ *                    the chunk's own word count reads as 0 and every table lookup is in range whatever freq holds; the caller
+ *                    guarantees that offsets never decrease and end at the number of words, and that words is non-NULL even
+ *                    when no chunk owns a word.
+ * NQ_ERR_INVALID, before the device is touched, for null pointers, n <= 0, n_bits outside 1..8, chunk <= 0 or not a multiple
+ * of 64, row_len <= 0 and both outputs NULL; NQ_ERR_UNSUPPORTED for n >= 2^32 (32-bit offsets) or more than 2^31 - 1
+ * workgroups. */
+NQ_API int64_t nq_rans_chunks(int64_t n, int64_t chunk);
+NQ_API int nq_rans_decode(const uint16_t* words, const uint32_t* states, const uint32_t* offsets, const uint16_t* freq, int64_t n,
+                   int n_bits, int64_t chunk, const float* delta, const float* zp, int64_t row_len, uint8_t* levels, float* w,
+                   nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,8 @@ def _load():
     sig("nq_pack_levels", I, P, P, L, I, P)
     sig("nq_unpack_dequant", I, P, P, P, P, L, L, I, P)
     sig("nq_frames_to_u8", I, P, P, L, I, L, I, P)
+    sig("nq_rans_chunks", L, L, L)
+    sig("nq_rans_decode", I, P, P, P, P, L, I, L, P, P, L, P, P, P)
     return lib
 
 
@@ -182,6 +184,7 @@ EXPORTS = (
     "nq_conv_wgrad3_split_io", "nq_head_forward_loss_ws_floats", "nq_head_forward_loss",
     "nq_adaround_fwht_multi", "nq_fwht_adaround_adam_multi", "nq_weight_layouts_all",
     "nq_packed_words", "nq_pack_levels", "nq_unpack_dequant", "nq_frames_to_u8",
+    "nq_rans_chunks", "nq_rans_decode",
 )
 
 _lib = None

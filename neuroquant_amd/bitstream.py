@@ -1,4 +1,4 @@
-"""Packed bit-stream container (`.nqv`) of a calibrated model and the GPU player that decodes it.
+"""Bit-stream container (`.nqv`) of a calibrated model and the GPU player that decodes it.
 
 `write_stream` turns a calibrated `QuantModel` into ONE self-describing file whose size is the nominal bit-rate: the integer
 levels of `export._levels`, packed at their bit-width by a HIP kernel, the quantiser scales, the biases and (HNeRV) the frame
@@ -8,7 +8,10 @@ builds each layer's convolution operand once and then decodes frames with the ve
 `models/_decode.run_decoder` issues, so for the same batch size and convolution precision its output equals the live
 model's evaluation bit for bit.
 
-The file realises the NOMINAL size (bits x parameters); the levels are not entropy coded and the embeddings stay fp32.
+By default (`coding="packed"`) the file realises the NOMINAL size (bits x parameters).  `coding="rans"` / `"auto"` store the
+levels entropy coded instead (§12): a 64-lane interleaved rANS code with one frequency table per tensor, encoded here on the
+host (`rans_encode`) and decoded at open by a HIP kernel, one wavefront per chunk.  The weights a player rebuilds are the same
+floats either way.  Scales, soft biases and embeddings are not coded.
 """
 import json
 import math
@@ -22,7 +25,14 @@ from . import ops
 
 MAGIC = b"NQV1"
 VERSION = 1
-_DTYPES = {"u32": "<u4", "f16": "<f2", "f32": "<f4"}
+_DTYPES = {"u16": "<u2", "u32": "<u4", "f16": "<f2", "f32": "<f4"}
+CODINGS = ("packed", "rans", "auto")
+# rANS constants (csrc/rans.hip holds the same three)
+RANS_PROB_BITS = 12
+RANS_M = 1 << RANS_PROB_BITS
+RANS_L = 1 << 16
+RANS_LANES = 64
+DEFAULT_CHUNK = 32768
 
 
 def _align4(n):
@@ -81,6 +91,104 @@ def read_container(path):
     return header, out
 
 
+# ------------------------------------------------------------------------------------------ rANS (host only)
+def rans_normalise(counts):
+    """histogram -> frequencies that sum to 4096, a symbol that occurs keeps f >= 1 (the rule of DESIGN.md §12):
+    f = max(1, floor(c * 4096 / n)); while the sum exceeds 4096 the largest f > 1 loses one (lowest symbol on ties); a
+    deficit goes whole to the symbol with the largest count (lowest symbol on ties)."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    n = int(c.sum())
+    if n <= 0 or (c < 0).any():
+        raise ValueError("rans_normalise: need a non-empty histogram of non-negative counts")
+    f = np.where(c > 0, np.maximum(1, c * RANS_M // n), 0)
+    while int(f.sum()) > RANS_M:
+        f[int(np.argmax(np.where(f > 1, f, 0)))] -= 1   # argmax returns the first (lowest) of equal maxima
+    f[int(np.argmax(c))] += RANS_M - int(f.sum())
+    return f.astype(np.uint16)
+
+
+def rans_encode(levels, n_bits, chunk=DEFAULT_CHUNK):
+    """levels (uint8, any shape, taken flat in C order) -> (freq u16 [2^n_bits], states u32 [64 * chunks], offsets u32
+    [chunks + 1], words u16), the four sections of a coded tensor.  Host numpy, vectorised over chunks and lanes: the Python
+    loop runs over the chunk's steps, last to first, and mirrors the decoder exactly (lanes 63 .. 0 inside a step, the words
+    reversed at the end)."""
+    lv = np.ascontiguousarray(np.asarray(levels).reshape(-1)).astype(np.int64)
+    n, n_bits, chunk = lv.size, int(n_bits), int(chunk)
+    if n == 0 or not 1 <= n_bits <= 8 or chunk <= 0 or chunk % RANS_LANES:
+        raise ValueError(f"rans_encode: need levels, n_bits in 1..8 and chunk a positive multiple of 64, got {n} levels, "
+                         f"n_bits={n_bits}, chunk={chunk}")
+    if int(lv.max()) >= 1 << n_bits or int(lv.min()) < 0:
+        raise ValueError(f"rans_encode: level {int(lv.max())} does not fit {n_bits} bits")
+    freq = rans_normalise(np.bincount(lv, minlength=1 << n_bits))
+    f_of = freq.astype(np.uint64)
+    cum_of = np.concatenate([[0], np.cumsum(f_of)[:-1]]).astype(np.uint64)
+    chunks = -(-n // chunk)
+    steps = -(-min(chunk, n) // RANS_LANES)
+    sym = np.zeros(chunks * steps * RANS_LANES, dtype=np.int64)
+    live = np.zeros(sym.size, dtype=bool)
+    sym[:n], live[:n] = lv, True                  # one chunk: steps * 64 >= n; several: steps * 64 == chunk
+    sym, live = sym.reshape(chunks, steps, RANS_LANES), live.reshape(chunks, steps, RANS_LANES)
+    x = np.full((chunks, RANS_LANES), RANS_L, dtype=np.uint64)
+    emitted = np.zeros((chunks, steps, RANS_LANES), dtype=bool)
+    word = np.zeros((chunks, steps, RANS_LANES), dtype=np.uint16)
+    for t in range(steps - 1, -1, -1):
+        a = live[:, t]
+        f = np.where(a, f_of[sym[:, t]], 1).astype(np.uint64)
+        e = a & (x >= (f << np.uint64(20)))
+        emitted[:, t], word[:, t] = e, (x & np.uint64(0xFFFF)).astype(np.uint16)
+        x = np.where(e, x >> np.uint64(16), x)
+        x = np.where(a, ((x // f) << np.uint64(RANS_PROB_BITS)) + x % f + cum_of[sym[:, t]], x)
+    # decode order inside a chunk: steps ascending, lanes ascending -- C order of (chunk, step, lane)
+    words = word[emitted]
+    offsets = np.concatenate([[0], np.cumsum(emitted.sum(axis=(1, 2)))]).astype(np.uint32)
+    return freq, x.astype(np.uint32).reshape(-1), offsets, words
+
+
+def rans_validate(freq, states, offsets, words, n, n_bits, chunk, what="coded tensor"):
+    """Host check of a coded tensor's four sections before they reach the GPU; ValueError names the rule that failed."""
+    if not isinstance(n_bits, int) or not 1 <= n_bits <= 8 or len(freq) != 1 << n_bits or int(np.sum(freq, dtype=np.int64)) != RANS_M:
+        raise ValueError(f"{what}: the frequency table must hold 2^n_bits entries that sum to {RANS_M}")
+    if not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES:
+        raise ValueError(f"{what}: chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
+    chunks = -(-int(n) // chunk)
+    if len(offsets) != chunks + 1:
+        raise ValueError(f"{what}: {len(offsets)} offsets stored, {n} levels in chunks of {chunk} need {chunks + 1}")
+    o = np.asarray(offsets, dtype=np.int64)
+    if o[0] != 0 or (np.diff(o) < 0).any() or o[-1] != len(words):
+        raise ValueError(f"{what}: offsets must start at 0, never decrease and end at the number of words ({len(words)})")
+    if len(states) != RANS_LANES * chunks or (np.asarray(states, dtype=np.int64) < RANS_L).any():
+        raise ValueError(f"{what}: need {RANS_LANES} states per chunk, each at least {RANS_L}")
+
+
+def coded_tensors(header, sec, what="stream"):
+    """{tensor name ('w0', 'b3', ...): (freq, states, offsets, words, chunk)} for every rANS-coded tensor of a parsed file
+    (`read_container`'s header and sections), each validated with `rans_validate`.  Host only: this is the check the player
+    runs before anything of a coded tensor reaches the GPU.  ValueError for an unknown coding, a missing section or a failed
+    rule."""
+    out = {}
+    for i, lay in enumerate(header["layers"]):
+        co, _, k, k2 = lay["shape"]
+        for tag, prefix, n, bits_key in (("w", "", co * lay["c_in_stored"] * k * k2, "n_bits"), ("b", "bias_", co, "bias_n_bits")):
+            coding = lay.get(prefix + "levels_coding", "packed")
+            if coding == "packed":
+                continue
+            name = f"{tag}{i}"
+            if coding != "rans":
+                raise ValueError(f"{what}: {name} is stored in an unknown coding {coding!r}")
+            if tag == "b" and header.get("bias") != "hard":
+                raise ValueError(f"{what}: {name} is marked as coded but the stream stores soft biases")
+            try:
+                parts = [sec[f"{name}.rans_{k}"] for k in ("freq", "states", "offsets", "words")]
+            except KeyError as e:
+                raise ValueError(f"{what}: {name} is rANS coded but section {e} is missing") from None
+            if [a.dtype.itemsize for a in parts] != [2, 4, 4, 2]:
+                raise ValueError(f"{what}: {name}: frequencies and words are u16 sections, states and offsets u32")
+            chunk = lay.get(prefix + "rans_chunk")
+            rans_validate(*parts, n, lay.get(bits_key), chunk, what=f"{what}: {name}")
+            out[name] = (*parts, chunk)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ writer
 def _scale_section(t):
     """fp16 when every entry survives the round trip (true after AdaRound's init, quantizer.py:264-265), else fp32."""
@@ -89,20 +197,33 @@ def _scale_section(t):
     return tag, t.numpy().astype(_DTYPES[tag])
 
 
-def _packed(q, x):
-    """packed words (numpy uint32) of tensor x under quantiser q.  Unpacks them again on the GPU and compares with q's
-    hard-rounded forward bit for bit, so a file that cannot reproduce the model is never written."""
-    from .export import _levels
+def _level_sections(q, x, name, coding, chunk):
+    """sections [(name, tag, array)] that store tensor x under quantiser q, the coding chosen ('packed' / 'rans') and the
+    entropy of its levels in bits.  Whatever is chosen is decoded again on the GPU and compared with q's hard-rounded forward
+    bit for bit, so a file that cannot reproduce the model is never written."""
+    from .export import _entropy_bits, _levels
     from .quantization.quantizer import AdaRoundQuantizer
     if isinstance(q, AdaRoundQuantizer):
         hard = ops.adaround_forward(x, q.alpha.data, q.delta.data, q.zero_point, q.n_levels, False)
     else:
         hard = ops.uaq_forward(x, q.delta.data, q.zero_point, q.n_levels)
-    words = ops.pack_levels(_levels(q, x), q.n_bits)
+    levels = _levels(q, x)
     delta, zp = q.delta.detach().float().reshape(-1), q.zero_point.detach().float().reshape(-1)
+    words = ops.pack_levels(levels, q.n_bits)
+    entropy = _entropy_bits(levels, q.n_levels)   # as export_quantized computes it
+    if coding != "packed":
+        coded = rans_encode(levels.cpu().numpy(), q.n_bits, chunk)
+        if coding == "rans" or sum(_align4(a.nbytes) for a in coded) < 4 * words.numel():
+            dev = [torch.from_numpy(a.view(np.int16 if a.dtype == np.uint16 else np.int32)).to(x.device) for a in coded]
+            freq, states, offsets, cw = dev
+            if not torch.equal(ops.rans_decode_dequant(cw, states, offsets, freq, delta, zp, x.shape, q.n_bits, chunk), hard):
+                raise RuntimeError("write_stream: coded levels do not reproduce the quantiser's output")
+            tags = ("u16", "u32", "u32", "u16")
+            kinds = ("rans_freq", "rans_states", "rans_offsets", "rans_words")
+            return [(f"{name}.{k}", t, a) for k, t, a in zip(kinds, tags, coded)], "rans", entropy
     if not torch.equal(ops.unpack_dequant(words, delta, zp, x.shape, q.n_bits), hard):
         raise RuntimeError("write_stream: packed levels do not reproduce the quantiser's output")
-    return words.cpu().numpy().view(np.uint32)
+    return [(f"{name}.levels", "u32", words.cpu().numpy().view(np.uint32))], "packed", entropy
 
 
 def _check_decoder_shape(arch, cfg):
@@ -113,15 +234,22 @@ def _check_decoder_shape(arch, cfg):
 
 
 @torch.no_grad()
-def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"):
+def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft", coding="packed", chunk=DEFAULT_CHUNK):
     """Write the calibrated `qnn` to `path`.  embeddings: HNeRV's per-frame input embeddings (tensor (N, c, h, w) or the list
     `evaluate()` returned); NeRV stores none and needs `frames`.  bias: 'soft' stores the fp32 bias the evaluated model uses,
-    'hard' its packed integer decision (export.py's module docstring).  -> summary: file size, bytes per kind of section,
-    bpp when the frame size is known, and the gap to the nominal size `export_quantized` reports."""
+    'hard' its integer decision (export.py's module docstring).  coding: 'packed' stores every level tensor at its bit-width,
+    'rans' entropy codes every one in chunks of `chunk` symbols, 'auto' codes a tensor only where its four
+    coded sections are smaller than its packed words.  -> summary: file size, bytes per kind of section, bpp when the frame
+    size is known, the gap to the nominal size `export_quantized` reports, and the bytes of all level sections
+    (`coded_level_bytes`) against the histogram entropy of those same tensors (`entropy_level_bytes`)."""
     from .quantization.quant_layer import QuantModule
     from .quantization.quantizer import AdaRoundQuantizer
     if bias not in ("soft", "hard"):
         raise ValueError(f"bias must be 'soft' or 'hard', got {bias!r}")
+    if coding not in CODINGS:
+        raise ValueError(f"coding must be one of {CODINGS}, got {coding!r}")
+    if coding != "packed" and (not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES):
+        raise ValueError(f"chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
     _check_decoder_shape(arch, cfg)
     emb = None
     if arch == "hnerv":
@@ -134,7 +262,7 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
     elif frames is None:
         raise ValueError("a NeRV stream needs the frame count: pass frames=")
     mods = [m for m in qnn.model.modules() if isinstance(m, QuantModule)]
-    layers, sections, nominal_bits = [], [], 0
+    layers, sections, nominal_bits, entropy_bits = [], [], 0, 0.0
     for i, m in enumerate(mods):
         wq, bq = m.weight_quantizer, m.bias_quantizer
         if not getattr(wq, "inited", True) or wq.delta is None or bq.delta is None or not m._hip_ok:
@@ -145,7 +273,11 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
             raise ValueError(f"layer {i}: weight quantiser still rounds softly; a stream stores hard decisions")
         lay = dict(shape=list(m.weight.shape), c_in_stored=int(src.shape[1]), n_bits=int(wq.n_bits),
                    scale_rows=int(wq.delta.numel()))
-        sections.append((f"w{i}.levels", "u32", _packed(wq, src)))
+        secs, chosen, e = _level_sections(wq, src, f"w{i}", coding, chunk)
+        sections += secs
+        entropy_bits += e
+        if chosen == "rans":
+            lay.update(levels_coding="rans", rans_chunk=chunk)
         for key, t in (("delta", wq.delta), ("zero_point", wq.zero_point)):
             lay[f"{key}_dtype"], arr = _scale_section(t)
             sections.append((f"w{i}.{key}", lay[f"{key}_dtype"], arr))
@@ -153,7 +285,11 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
             sections.append((f"b{i}.soft", "f32", bq(m.bias).detach().float().cpu().numpy()))
         else:
             lay.update(bias_n_bits=int(bq.n_bits), bias_scale_rows=int(bq.delta.numel()))
-            sections.append((f"b{i}.levels", "u32", _packed(bq, m.bias.data)))
+            secs, chosen, e = _level_sections(bq, m.bias.data, f"b{i}", coding, chunk)
+            sections += secs
+            entropy_bits += e
+            if chosen == "rans":
+                lay.update(bias_levels_coding="rans", bias_rans_chunk=chunk)
             for key, t in (("delta", bq.delta), ("zero_point", bq.zero_point)):
                 lay[f"bias_{key}_dtype"], arr = _scale_section(t)
                 sections.append((f"b{i}.{key}", lay[f"bias_{key}_dtype"], arr))
@@ -170,8 +306,12 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
         kind = "embeddings" if s["name"] == "embeddings" else ("weight_" if s["name"][0] == "w" else "bias_") + s["name"].split(".")[1]
         kinds[kind] = kinds.get(kind, 0) + _align4(s["bytes"])
     nominal = math.ceil(nominal_bits / 8)
+    coded = sum(v for k, v in kinds.items() if k.endswith("_levels") or "_rans_" in k)
+    entropy = math.ceil(entropy_bits / 8)
     summary = dict(path=path, file_bytes=size, header_bytes=size - sum(kinds.values()), section_bytes=kinds,
                    total_bytes_nominal=nominal, gap_to_nominal_bytes=size - nominal, frames=int(frames), bias=bias,
+                   coding=coding, coded_tensors=sum(("levels_coding" in l) + ("bias_levels_coding" in l) for l in layers),
+                   coded_level_bytes=coded, entropy_level_bytes=entropy, gap_to_entropy_bytes=coded - entropy,
                    scale_dtypes=[[l["delta_dtype"], l["zero_point_dtype"]] for l in layers])
     h, w = cfg.get("crop_h"), cfg.get("crop_w")
     if frames and h and w:
@@ -208,12 +348,36 @@ class StreamDecoder:
             a = np.array(sec[name])   # a writable copy; the packed words travel as int32, the dtype ops takes
             return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(self.device)
 
+        coded = coded_tensors(header, sec, what=path)   # host validation of every coded tensor, before any upload
+
+        def levels(tag, i, lay, prefix, shape, n_bits):
+            """the tensor stored as `{tag}{i}` in whichever coding the layer names, dequantised on the GPU"""
+            name, coding = f"{tag}{i}", lay.get(prefix + "levels_coding", "packed")
+            delta, zp = up(f"{name}.delta").float(), up(f"{name}.zero_point").float()
+            if coding == "packed":
+                self.level_bytes["packed"] += sec[f"{name}.levels"].nbytes
+                self.level_tensors["packed"] += 1
+                return ops.unpack_dequant(up(f"{name}.levels"), delta, zp, shape, n_bits)
+            *parts, chunk = coded[name]
+            self.level_bytes["rans"] += sum(a.nbytes for a in parts)
+            self.level_tensors["rans"] += 1
+            # one host buffer, one upload: the four arrays side by side at 4-byte boundaries, viewed by type on the device
+            starts = np.cumsum([0] + [_align4(a.nbytes) for a in parts])
+            host = np.zeros(int(starts[-1]), dtype=np.uint8)
+            for a, o in zip(parts, starts):
+                host[o:o + a.nbytes] = a.view(np.uint8)
+            dev = torch.from_numpy(host).to(self.device)
+            freq, states, offsets, words = (dev[o:o + a.nbytes].view(torch.int16 if a.dtype.itemsize == 2 else torch.int32)
+                                            for a, o in zip(parts, starts))
+            return ops.rans_decode_dequant(words, states, offsets, freq, delta, zp, shape, n_bits, chunk, trusted=True)
+
         self.weights, self.biases = [], []
+        self.level_bytes = {"packed": 0, "rans": 0}   # bytes of the level sections this file stores, per coding (unpadded)
+        self.level_tensors = {"packed": 0, "rans": 0}
         with torch.no_grad():
             for i, lay in enumerate(header["layers"]):
                 co, ci, k, k2 = lay["shape"]
-                w = ops.unpack_dequant(up(f"w{i}.levels"), up(f"w{i}.delta").float(),
-                                       up(f"w{i}.zero_point").float(), (co, lay["c_in_stored"], k, k2), lay["n_bits"])
+                w = levels("w", i, lay, "", (co, lay["c_in_stored"], k, k2), lay["n_bits"])
                 if header["hadamard"]:
                     w = ops.hadamard_along_channel_weight(w, n_out=ci)
                 elif lay["c_in_stored"] != ci:
@@ -221,8 +385,7 @@ class StreamDecoder:
                 if header["bias"] == "soft":
                     b = up(f"b{i}.soft").float()
                 else:
-                    b = ops.unpack_dequant(up(f"b{i}.levels"), up(f"b{i}.delta").float(),
-                                           up(f"b{i}.zero_point").float(), (co,), lay["bias_n_bits"])
+                    b = levels("b", i, lay, "bias_", (co,), lay["bias_n_bits"])
                 self.weights.append(w.contiguous())
                 self.biases.append(b.contiguous())
             if self.arch == "hnerv":

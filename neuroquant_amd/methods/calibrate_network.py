@@ -10,7 +10,8 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
         --ckpt epoch300.pth --batch_size 2 --channel_wise --init max --iters_w 21000 --weight 0.01 --b_start 20 \
         --b_end 2 --warmup 0.2 --lr 0.003 --precision 6 5 4 5 5 6 6
     (--synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --export_stream FILE.nqv also writes the
-    calibrated model as a packed bit stream that `python -m neuroquant_amd.methods.decode_stream` plays back)
+    calibrated model as a bit stream that `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding
+    packed | rans | auto chooses between levels packed at their bit-width and entropy-coded levels)
 """
 import argparse
 import logging
@@ -58,6 +59,8 @@ def parse_args(argv):
     p.add_argument('--dump_vis', action='store_true', default=False)
     p.add_argument('--export_stream', type=str, default=None,
                    help='write the calibrated model as a packed bit stream (.nqv, neuroquant_amd/bitstream.py) to this path')
+    p.add_argument('--stream_coding', type=str, default='packed', choices=['packed', 'rans', 'auto'],
+                   help='levels of --export_stream: packed at their bit-width, rANS coded, or whichever is smaller per tensor')
     return p.parse_args(argv)
 
 
@@ -225,9 +228,12 @@ def calibrate(args, cfg):
         if getattr(args, 'export_stream', None):
             from ..bitstream import write_stream
             s = write_stream(qnn, args.export_stream, args.arch, cfg, frames=n,
-                             embeddings=cali_data if args.arch == 'hnerv' else None)
-            logging.info('bit stream: {} ({} bytes, {} bpp; nominal {} bytes)'.format(
-                args.export_stream, s['file_bytes'], round(s.get('bpp', float('nan')), 5), s['total_bytes_nominal']))
+                             embeddings=cali_data if args.arch == 'hnerv' else None,
+                             coding=getattr(args, 'stream_coding', 'packed'))
+            logging.info('bit stream: {} ({} bytes, {} bpp; nominal {} bytes; coding {}: levels {} bytes, '
+                         'gap to entropy {} bytes)'.format(
+                             args.export_stream, s['file_bytes'], round(s.get('bpp', float('nan')), 5), s['total_bytes_nominal'],
+                             s['coding'], s['coded_level_bytes'], s['gap_to_entropy_bytes']))
     args.qnn = qnn
     return res
 

@@ -1,4 +1,4 @@
-"""Player driver: decode every frame of a packed bit stream (`.nqv`, neuroquant_amd/bitstream.py) on the GPU.
+"""Player driver: decode every frame of a bit stream (`.nqv`, packed or entropy-coded levels; neuroquant_amd/bitstream.py) on the GPU.
 
     python -m neuroquant_amd.methods.decode_stream --stream model.nqv [--out DIR] [--frames DIR | --synthetic N]
         [--batch_size B]
@@ -74,7 +74,8 @@ def run(args):
             if with_ssim:
                 acc['ssim'].append(ops.ms_ssim(img, ref))
                 acc['ssim_u8'].append(ops.ms_ssim(img8, ref))
-    res = dict(frames=n, batch_size=B, open_seconds=open_s, fps=n / dec_time, file_bytes=os.path.getsize(args.stream))
+    res = dict(frames=n, batch_size=B, open_seconds=open_s, fps=n / dec_time, file_bytes=os.path.getsize(args.stream),
+               level_bytes=dec.level_bytes, level_tensors=dec.level_tensors)
     for k, v in acc.items():
         if v:
             res[k] = torch.cat(v).cpu().mean()
@@ -86,6 +87,8 @@ def main(argv):
     res = run(args)
     print('stream {}: {} bytes, {} frames, opened in {:.3f} s, decode FPS {} (batch {})'.format(
         args.stream, res['file_bytes'], res['frames'], res['open_seconds'], round(res['fps'], 1), res['batch_size']))
+    print('levels: rans {} bytes in {} tensors, packed {} bytes in {} tensors'.format(
+        res['level_bytes']['rans'], res['level_tensors']['rans'], res['level_bytes']['packed'], res['level_tensors']['packed']))
     if 'psnr' in res:
         fmt = lambda k, d: RoundTensor(res[k], d) if k in res else 'n/a'
         print('float: PSNR {} | MS-SSIM {}'.format(fmt('psnr', 2), fmt('ssim', 4)))

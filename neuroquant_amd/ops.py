@@ -1776,3 +1776,57 @@ def frames_to_u8(x: torch.Tensor, layout: str = "chw") -> torch.Tensor:
     out = torch.empty((n, C, H, W) if layout == "chw" else (n, H, W, C), device=x.device, dtype=torch.uint8)
     L.check(L.lib().nq_frames_to_u8(_p(x), _p(out), n, C, H * W, 0 if layout == "chw" else 1, _stream()), "frames_to_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------ entropy-coded levels (rANS)
+def rans_chunks(n: int, chunk: int) -> int:
+    """chunks a tensor of n levels is cut into (0 for n <= 0, chunk <= 0 or chunk not a multiple of 64)."""
+    return int(L.lib().nq_rans_chunks(int(n), int(chunk)))
+
+
+def _rans_args(words, states, offsets, freq, n, n_bits, chunk, trusted, what):
+    """The four coded arrays as the kernel takes them: 16-bit words and frequencies travel as int16, 32-bit states and offsets
+    as int32 (the bit patterns of the file's u16 / u32).  Sizes are checked here; unless `trusted` (the caller has validated
+    the offsets on the host, as the player does) the offsets are checked on the device, which costs one synchronisation:
+    the kernel bounds a chunk's reads by its own offsets, so they must lie inside `words`."""
+    words, freq = _dev_as(words, torch.int16, "words").reshape(-1), _dev_as(freq, torch.int16, "freq").reshape(-1)
+    states, offsets = _dev_as(states, torch.int32, "states").reshape(-1), _dev_as(offsets, torch.int32, "offsets").reshape(-1)
+    chunks = rans_chunks(n, chunk) if 1 <= int(n_bits) <= 8 else 0
+    if chunks <= 0:
+        raise ValueError(f"{what}: need n > 0, n_bits in 1..8 and chunk a positive multiple of 64, got n={n}, n_bits={n_bits}, "
+                         f"chunk={chunk}")
+    if freq.numel() != 2 ** int(n_bits) or states.numel() != 64 * chunks or offsets.numel() != chunks + 1:
+        raise ValueError(f"{what}: {chunks} chunks of {n_bits}-bit levels need {2 ** int(n_bits)} frequencies, {64 * chunks} states "
+                         f"and {chunks + 1} offsets, got {freq.numel()}, {states.numel()} and {offsets.numel()}")
+    if not trusted:
+        o = offsets.long() & 0xFFFFFFFF
+        if int(o[0]) != 0 or int(o[-1]) != words.numel() or bool((o[1:] < o[:-1]).any()):
+            raise ValueError(f"{what}: offsets must start at 0, never decrease and end at the number of words ({words.numel()})")
+    if words.numel() == 0:   # a constant tensor costs no word; the entry still wants a pointer
+        words = torch.zeros(1, device=states.device, dtype=torch.int16)
+    return words, states, offsets, freq
+
+
+def rans_decode(words, states, offsets, freq, n: int, n_bits: int, chunk: int, trusted: bool = False) -> torch.Tensor:
+    """rANS-coded levels (bitstream.rans_encode writes them) -> n uint8 levels."""
+    words, states, offsets, freq = _rans_args(words, states, offsets, freq, n, n_bits, chunk, trusted, "rans_decode")
+    lv = torch.empty(int(n), device=states.device, dtype=torch.uint8)
+    L.check(L.lib().nq_rans_decode(_p(words), _p(states), _p(offsets), _p(freq), int(n), int(n_bits), int(chunk), None, None, 1,
+                                   _p(lv), None, _stream()), "rans_decode")
+    return lv
+
+
+def rans_decode_dequant(words, states, offsets, freq, delta: torch.Tensor, zp: torch.Tensor, shape, n_bits: int, chunk: int,
+                        trusted: bool = False) -> torch.Tensor:
+    """rANS-coded levels -> fp32 tensor of `shape`: (level - zp) * delta, bit-identical to `unpack_dequant` of the same levels.
+    delta / zp hold one value per shape[0] or a single value."""
+    shape = tuple(int(s) for s in shape)
+    n = math.prod(shape)
+    words, states, offsets, freq = _rans_args(words, states, offsets, freq, n, n_bits, chunk, trusted, "rans_decode_dequant")
+    delta, zp = _dev(delta, "delta"), _dev(zp, "zero_point")
+    if delta.numel() != zp.numel() or delta.numel() not in (1, shape[0]):
+        raise ValueError("rans_decode_dequant: delta / zero_point must hold one value per output channel or a single value")
+    w = torch.empty(shape, device=states.device, dtype=torch.float32)
+    L.check(L.lib().nq_rans_decode(_p(words), _p(states), _p(offsets), _p(freq), n, int(n_bits), int(chunk), _p(delta), _p(zp),
+                                   n // delta.numel(), None, _p(w), _stream()), "rans_decode_dequant")
+    return w
