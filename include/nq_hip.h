@@ -488,6 +488,30 @@ NQ_API int nq_rans_decode(const uint16_t* words, const uint32_t* states, const u
                    int n_bits, int64_t chunk, const float* delta, const float* zp, int64_t row_len, uint8_t* levels, float* w,
                    nq_stream_t stream);
 
+/* ---- bit allocation under a size budget (additive: nq_abi_version() stays 7) ----
+ * The Omega score of an allocation is a quadratic form: with K bit choices for each of L layers, the (L K) x (L K) Gram matrix
+ * G[(l,c),(m,d)] = <v_l(c), (H v_m(d))_l> of the per-layer perturbations gives Omega(b) = sum_l sum_m G[(l,b_l),(m,b_m)].
+ *   nq_rows_dot     out[r] = sum_i V[r * n + i] * g[i] for r < K, 1 <= K <= 8: the K entries G[(l,.), j] from layer l's slice g of
+ *                   H e_j.  Every product is formed in float64 (exact: 24 x 24 bits); the sums are float64 in a fixed order
+ *                   (per-thread strided partial sums, a wave tree, one partial per workgroup in ws, a finishing launch that adds
+ *                   the partials in index order): no atomics, bit-identical from call to call.  g is read once for all K rows.
+ *                   ws: nq_rows_dot_ws_bytes(K, n) bytes (0 for arguments the entry refuses), 8-byte aligned.
+ *   nq_bit_search   G: (L K) x (L K) row-major, row / column (l, c) at l K + c; size_bits: L x K.  A candidate is the
+ *                   mixed-radix index sum_l c_l K^l (layer 0 least significant).  Over every candidate with
+ *                   sum_l size_bits[l][c_l] <= budget_bits (the sum saturates at 2^64 - 1), Omega is summed from 0.0 with l
+ *                   ascending in the outer and m ascending in the inner loop by plain float64 additions, and the lexicographic
+ *                   minimum of (Omega, index) is kept: ties go to the lowest index, a NaN Omega is never selected.  Nothing
+ *                   fits: best_index = UINT64_MAX, best_omega = +inf.  G and size_bits are staged in LDS; workgroup minima go
+ *                   to ws (nq_bit_search_ws_bytes(L, K) bytes, 8-byte aligned; 0 for shapes the entry refuses), a finishing
+ *                   launch reduces them.  best_omega / best_index are device pointers to one element each.
+ * NQ_ERR_INVALID, before the device is touched, for null pointers, L < 1, K < 1, K > 8 and n < 1; NQ_ERR_UNSUPPORTED for L > 12,
+ * K^L >= 2^32 and an (L K)^2 table past 64 KB of LDS. */
+NQ_API int64_t nq_rows_dot_ws_bytes(int K, int64_t n);
+NQ_API int nq_rows_dot(const float* V, const float* g, double* out, int K, int64_t n, double* ws, nq_stream_t stream);
+NQ_API int64_t nq_bit_search_ws_bytes(int L, int K);
+NQ_API int nq_bit_search(const double* G, const uint64_t* size_bits, int L, int K, uint64_t budget_bits, double* best_omega,
+                  uint64_t* best_index, void* ws, nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,10 @@ def _load():
     sig("nq_frames_to_u8", I, P, P, L, I, L, I, P)
     sig("nq_rans_chunks", L, L, L)
     sig("nq_rans_decode", I, P, P, P, P, L, I, L, P, P, L, P, P, P)
+    sig("nq_rows_dot_ws_bytes", L, I, L)
+    sig("nq_rows_dot", I, P, P, P, I, L, P, P)
+    sig("nq_bit_search_ws_bytes", L, I, I)
+    sig("nq_bit_search", I, P, P, I, I, ctypes.c_uint64, P, P, P, P)
     return lib
 
 
@@ -185,6 +189,7 @@ EXPORTS = (
     "nq_adaround_fwht_multi", "nq_fwht_adaround_adam_multi", "nq_weight_layouts_all",
     "nq_packed_words", "nq_pack_levels", "nq_unpack_dequant", "nq_frames_to_u8",
     "nq_rans_chunks", "nq_rans_decode",
+    "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",
 )
 
 _lib = None

@@ -9,7 +9,8 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     python -m neuroquant_amd.methods.calibrate_network --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny \
         --ckpt epoch300.pth --batch_size 2 --channel_wise --init max --iters_w 21000 --weight 0.01 --b_start 20 \
         --b_end 2 --warmup 0.2 --lr 0.003 --precision 6 5 4 5 5 6 6
-    (--synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --export_stream FILE.nqv also writes the
+    (--precision_file bits.json takes the bit-widths from `bit_assign --budget_bytes N --out bits.json`;
+    --synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --export_stream FILE.nqv also writes the
     calibrated model as a bit stream that `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding
     packed | rans | auto chooses between levels packed at their bit-width and entropy-coded levels)
 """
@@ -42,7 +43,10 @@ def parse_args(argv):
     p.add_argument('--vid', type=str, default='Bunny')
     p.add_argument('--data_split', type=str, default='1_1_1')
     p.add_argument('--batch_size', default=12, type=int)
-    p.add_argument('--precision', type=int, nargs='+', default=[8] * 7)
+    prec = p.add_mutually_exclusive_group()
+    prec.add_argument('--precision', type=int, nargs='+', default=None, help='per-layer bit-widths (default: 8 for all 7 layers)')
+    prec.add_argument('--precision_file', type=str, default=None,
+                      help='read the bit-widths from the JSON that `bit_assign --out` writes (its "bits" list)')
     p.add_argument('--channel_wise', action='store_true')
     p.add_argument('--hadamard', action='store_true')
     p.add_argument('--iters_w', default=20000, type=int)
@@ -61,7 +65,25 @@ def parse_args(argv):
                    help='write the calibrated model as a packed bit stream (.nqv, neuroquant_amd/bitstream.py) to this path')
     p.add_argument('--stream_coding', type=str, default='packed', choices=['packed', 'rans', 'auto'],
                    help='levels of --export_stream: packed at their bit-width, rANS coded, or whichever is smaller per tensor')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.precision_file is not None:
+        args.precision = read_precision_file(args.precision_file)
+    elif args.precision is None:
+        args.precision = [8] * 7
+    return args
+
+
+def read_precision_file(path, n_layers=None):
+    """The "bits" list of the JSON `bit_assign --out` writes; ValueError if it is not a list of widths in 2..8 or, given
+    n_layers, not of that length."""
+    import json
+    with open(path) as f:
+        bits = json.load(f).get('bits')
+    if not isinstance(bits, list) or not bits or not all(isinstance(b, int) and 2 <= b <= 8 for b in bits):
+        raise ValueError(f'{path}: "bits" must be a list of bit-widths in 2..8, got {bits!r}')
+    if n_layers is not None and len(bits) != n_layers:
+        raise ValueError(f'{path} lists {len(bits)} bit-widths, the decoder has {n_layers} quantised layers')
+    return bits
 
 
 def seed_all(seed=903):
@@ -193,6 +215,8 @@ def calibrate(args, cfg):
 
     wq_params = {'n_bits': 8, 'channel_wise': args.channel_wise, 'scale_method': args.init}
     qnn = QuantModel(model=model, hadamard=args.hadamard, weight_quant_params=wq_params).to(device)
+    if getattr(args, 'precision_file', None):
+        read_precision_file(args.precision_file, len(qnn.quant_modules()))
     args.qbits = qnn.set_bitwidth(args.precision)
     qnn.eval()
     cali_data = torch.cat(embedding_list, dim=0)

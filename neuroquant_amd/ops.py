@@ -1830,3 +1830,39 @@ def rans_decode_dequant(words, states, offsets, freq, delta: torch.Tensor, zp: t
     L.check(L.lib().nq_rans_decode(_p(words), _p(states), _p(offsets), _p(freq), n, int(n_bits), int(chunk), _p(delta), _p(zp),
                                    n // delta.numel(), None, _p(w), _stream()), "rans_decode_dequant")
     return w
+
+
+# ------------------------------------------------------------------------------------------ bit allocation
+def rows_dot(V: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """out[r] = <V[r], g> for the K <= 8 rows of V, in float64 (exact products, fixed summation order: bit-identical from call
+    to call).  V: (K, ...) fp32, g: fp32 with the elements of one row."""
+    V, g = _dev(V.detach(), "V"), _dev(g.detach(), "g")
+    K, n = (V.shape[0], g.numel()) if V.dim() else (0, 0)
+    if not 1 <= K <= 8 or n < 1 or V.numel() != K * n:
+        raise ValueError(f"rows_dot: V must hold 1..8 rows of g's {n} elements, got {tuple(V.shape)} against {tuple(g.shape)}")
+    out = torch.empty(K, device=V.device, dtype=torch.float64)
+    ws = torch.empty(_q("nq_rows_dot_ws_bytes", K, n) // 8, device=V.device, dtype=torch.float64)
+    L.check(L.lib().nq_rows_dot(_p(V), _p(g), _p(out), K, n, _p(ws), _stream()), "rows_dot")
+    return out
+
+
+def bit_search(G: torch.Tensor, size_bits: torch.Tensor, budget_bits: int):
+    """Exhaustive search of the K^L allocations of an (L K) x (L K) Omega table G (float64) under sum_l size_bits[l][c_l] <=
+    budget_bits (size_bits: (L, K) int64, non-negative) -> (omega, index), index = sum_l c_l K^l; (inf, None) when nothing
+    fits.  Ties go to the lowest index; the sum order is the one of tests/bit_search_ref.py, so the two agree to the bit."""
+    G = _dev_as(G, torch.float64, "G")
+    size_bits = _dev_as(size_bits, torch.int64, "size_bits")
+    if size_bits.dim() != 2 or G.dim() != 2 or G.shape[0] != G.shape[1] or G.shape[0] != size_bits.numel() or G.numel() == 0:
+        raise ValueError(f"bit_search: G must be (L K, L K) for size_bits (L, K), got {tuple(G.shape)} and {tuple(size_bits.shape)}")
+    n_layers, K = size_bits.shape
+    budget_bits = int(budget_bits)
+    if not 0 <= budget_bits < 2 ** 64 or bool((size_bits < 0).any()):
+        raise ValueError("bit_search: sizes and the budget must be non-negative and below 2^64")
+    ws_bytes = _q("nq_bit_search_ws_bytes", n_layers, K)
+    ws = torch.empty(max(ws_bytes // 8, 1), device=G.device, dtype=torch.float64)
+    omega = torch.empty(1, device=G.device, dtype=torch.float64)
+    index = torch.empty(1, device=G.device, dtype=torch.int64)     # the bits of the entry's uint64
+    L.check(L.lib().nq_bit_search(_p(G), _p(size_bits), n_layers, K, budget_bits, _p(omega), _p(index), _p(ws), _stream()),
+            "bit_search")
+    ix = int(index) & 0xFFFFFFFFFFFFFFFF
+    return float(omega), (None if ix == 0xFFFFFFFFFFFFFFFF else ix)
