@@ -294,7 +294,9 @@ NQ_API int nq_weight_layout3_multi(const nq_wl3_seg* segs, int nseg, nq_stream_t
  * same bytes as the two calls (which it falls back to when a table does not fit one kernel-argument block). */
 NQ_API int nq_weight_layouts_all(const nq_wl3_seg* segs3, int n3, const nq_wl_seg* segsf, int nf, nq_stream_t stream);
 /* The launch plan nq_conv_forward3 will use for this shape (ABI v7; pure host function, the same for every epilogue): which kernel
- * and which of its builds, the split over 16-channel chunks and the LDS of the launch.  Answered for every valid shape --
+ * and which of its builds, the split over 16-channel chunks and the LDS of the launch.  It is not a second derivation: the launch,
+ * this query, nq_conv3_supported, nq_conv3_split_io and nq_conv_forward3_ws_floats all read ONE resolution of the shape
+ * (route_fwd3, csrc/conv3.hip; the weight-gradient entries likewise read route_wgrad3).  Answered for every valid shape --
  * nq_conv_forward3 launches whatever it is handed -- with `supported` = nq_conv3_supported, i.e. whether callers should route
  * the shape here at all.  A few-pixel shape whose wave-private patches would need more than 160 KiB of LDS is not given to the
  * few-pixel kernel: it takes the tiled kernel (and is `supported` only where that one fills the chip).

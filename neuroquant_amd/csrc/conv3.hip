@@ -9,19 +9,13 @@ int nq_conv_igemm3_k3(const float*, const void*, const float*, float*, float*, c
 int nq_conv_igemm3_k5(const float*, const void*, const float*, float*, float*, const float*, int, int, int, int, int, int, int,
                       int, int, int, float*, hipStream_t);
 int nq_conv_splitk_finish(const float*, const float*, float*, float*, const float*, int, int, int, int, int, int, int, hipStream_t);
-int nq_conv3_nst_k3();
-int nq_conv3_nst_k5();
-int nq_conv3_nst8_k3();
-int nq_conv3_nst8_k5();
-int nq_conv3_nstk_k3(int);
-int nq_conv3_nstk_k5(int);
 int nq_conv_flat3_plan(int, int, int, int, int, int, NqFlat3Plan*);
 int nq_conv3_waves_k3(int, int, int, int, int);
 int nq_conv3_waves_k5(int, int, int, int, int);
 int nq_conv3_lds_k3(int, int, int);
 int nq_conv3_lds_k5(int, int, int);
 int nq_conv_flat3(const float*, const void*, const float*, float*, float*, const float*, float*, int, int, int, int, int, int, int, int,
-                  int, int, int, int, hipStream_t);
+                  int, const NqFlat3Plan*, hipStream_t);
 int nq_conv_wgrad_flat3_ok(int, int, int, int, int, int);
 int nq_conv_wgrad_flat3(const float*, const float*, float*, float*, int, int, int, int, int, int, hipStream_t);
 int nq_conv_wgrad3_k3(const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
@@ -51,17 +45,9 @@ inline int pick_mi3(int Cout) {
   if (Cout > 256 && (Cout + 63) / 64 * 64 <= best_pad + best_pad * 6 / 100) return 4;
   return best;
 }
-inline int nst_of(int k) { return k == 5 ? nq_conv3_nst_k5() : nq_conv3_nst_k3(); }
-inline int nstk_of(int k, int kind) { return k == 5 ? nq_conv3_nstk_k5(kind) : nq_conv3_nstk_k3(kind); }
-// shape of the last 16-channel chunk by the channels r it really holds (Conv3Args::tail): 1: r <= 4, 2: r <= 8, 3: r <= 12,
-// 0: a full chunk -- it is laid out (and run) with fewer, denser k-steps
-inline int tail_kind_of(int Cin, int mi) {
-  const int r = Cin - CC * ((Cin + CC - 1) / CC - 1);
-  return r <= 4 ? 1 : (r <= 8 ? 2 : (r <= 12 ? 3 : 0));
-}
-inline int64_t total_steps3(int Cin, int k, int mi) {
-  const int nchunk = (Cin + CC - 1) / CC;
-  return (int64_t)(nchunk - 1) * nst_of(k) + nstk_of(k, tail_kind_of(Cin, mi));
+// what every entry point of this path asks of a shape before anything is planned for it
+inline bool shape_ok3(int B, int Cin, int H, int W, int Cout, int k) {
+  return (k == 3 || k == 5) && B > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0;
 }
 
 // Operand of the bf16x3 kernels: 16-byte fragment slots [global k-step][plane hi/lo][co tile][kq][MT] of 8 bf16 k-values.
@@ -243,15 +229,41 @@ inline Fwd3Plan plan_fwd3(int B, int Cin, int H, int W, int Cout) {
 // finish launch), or when the tiled kernel's grid would not fill the chip even with split-K (it would fall back to the fp32
 // kernels).  Long K loops that the tiled split-K path already handles stay there: measured (us, kernel + finish) HNeRV dec2
 // data gradient 21.0 flat vs 21.7 tiled, NeRV dec1 data gradient 22.4 vs 18.7, NeRV dec2 data gradient 19.3 vs 25.6 (fp32).
-inline bool use_flat3(int B, int Cin, int H, int W, int Cout, int k, int* fns, NqFlat3Plan* fp = nullptr) {
-  NqFlat3Plan pl;
-  if (!nq_conv_flat3_plan(B, Cin, H, W, Cout, k, &pl)) return false;
-  const int ns = pl.nsplit;
-  if (fns) *fns = ns;
-  if (fp) *fp = pl;
-  if (ns == 1) return true;
+//
+// Everything nq_conv_forward3 decides from the shape, resolved ONCE per call (shape_ok3 holds): the queries below read it and
+// the launch runs it, so they cannot disagree.  The only caller of nq_conv_flat3_plan and of plan_fwd3.
+struct Fwd3Route {
+  bool flat;               // the few-pixel kernel (conv_flat3.hip) has the shape, else the tiled one (conv_igemm3_impl.h)
+  int mi, tail;            // the operand's layout: 16*mi-channel tiles, kind of the last chunk; the tiled kernel's tile
+  int nsplit, per_split;   // K split of the kernel that has the shape
+  NqFlat3Plan fp;          // few-pixel launch plan (flat only)
+  int supported;           // nq_conv3_supported
+  int split_io;            // nq_conv3_split_io
+  int64_t ws_floats;       // nq_conv_forward3_ws_floats
+};
+inline Fwd3Route route_fwd3(int B, int Cin, int H, int W, int Cout, int k) {
+  Fwd3Route r{};
+  const bool fits = nq_conv_flat3_plan(B, Cin, H, W, Cout, k, &r.fp) != 0;
   const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
-  return p.wgs * p.nsplit < 128;
+  const bool tiled_fills = p.wgs * p.nsplit >= 128;   // still smaller grids stay on the fp32 split-K kernel
+  r.flat = fits && (r.fp.nsplit == 1 || !tiled_fills);
+  r.mi = p.mi;
+  r.tail = wl3_tail_kind(Cin);
+  r.nsplit = r.flat ? r.fp.nsplit : p.nsplit;
+  r.per_split = r.flat ? r.fp.per_split : p.per;
+  r.ws_floats = r.nsplit > 1 ? (int64_t)r.nsplit * B * Cout * H * W : 0;
+  // <= 4 channels on either side (the image head): the streaming VALU kernels of conv_head.hip are faster than a
+  // >80 %-padded MFMA tile (measured 0.17 / 0.23 ms vs 0.21 / 0.38 ms, forward / data gradient of 37->3 at 640x1280).
+  // The kernel addresses the input with 32-bit buffer offsets (conv_igemm3_impl.h): tensors of 4 GiB and more stay on the
+  // fp32 kernels.
+  if (Cout <= 4 || Cin <= 4 || (int64_t)B * Cin * H * W * 4 >= 0xFFFFFF00ll) return r;   // supported = split_io = 0
+  // few-pixel kernel -- offered for layers whose weight tensor is worth streaming; a toy convolution (a few hundred weights)
+  // stays on the exact-fp32 kernels: nothing to gain, and its callers keep fp32-level results
+  r.supported = (r.flat && (int64_t)Cin * k * k * Cout >= 65536) || tiled_fills;
+  // Which sides may travel as split {hi | lo} words: the input where the tiled kernel with >= 32-channel tiles stages it (the
+  // few-pixel kernel reads floats only), the output where the kernel's own epilogue writes it (no slabs)
+  if (r.supported) r.split_io = (!r.flat && r.mi >= 2 ? NQ_EPI_X_SPLIT : 0) | (r.nsplit == 1 ? NQ_EPI_Y_SPLIT : 0);
+  return r;
 }
 
 struct Wg3Plan {
@@ -350,6 +362,29 @@ inline Wg3Plan plan_wgrad3(int B, int Cin, int H, int W, int Cout, int k) {
     }
   }
   return p;
+}
+
+// Everything the weight-gradient entries decide from the shape, resolved ONCE per call (shape_ok3 holds); the role-swapped
+// entries resolve the EXCHANGED problem (Cin <-> Cout).  The only caller of nq_conv_wgrad_flat3_ok and of plan_wgrad3.
+struct Wg3Route {
+  bool flat;           // the few-pixel kernel (conv_wgrad_flat3.hip: no slabs, no reduction) has the shape
+  Wg3Plan p;           // plan of the tiled kernels (what nq_conv_wgrad3_plan reports, also for few-pixel shapes)
+  int supported;       // nq_conv_wgrad3_supported
+  int split_io;        // nq_conv_wgrad3_split_io
+  int sg;              // split groups of the slab reduction (wgrad3_reduce_kernel<sg>, nq_wgr_seg::sg)
+  int64_t ws_floats;   // nq_conv_wgrad3_ws_floats
+};
+inline Wg3Route route_wgrad3(int B, int Cin, int H, int W, int Cout, int k) {
+  Wg3Route r{};
+  r.flat = nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k) != 0;
+  r.p = plan_wgrad3(B, Cin, H, W, Cout, k);
+  // few-pixel layers leave no slabs (a token workspace keeps the pointer non-NULL)
+  r.ws_floats = r.flat ? 4 : (int64_t)r.p.nsplit * r.p.co_pad * ((int64_t)r.p.n_pad + 1);
+  // tiled kernels: enough 32-pixel segments to split over
+  r.supported = Cout > 4 && (r.flat || (int64_t)((W + 31) / 32) * H * B >= 128);
+  r.split_io = (r.supported && !r.flat && nq_wgrad3_pc_takes_split(r.p.pc)) ? 3 : 0;
+  r.sg = ((int64_t)Cout * Cin * k * k + Cout < 65536 && r.p.nsplit >= 16) ? 16 : 4;
+  return r;
 }
 
 // Fixed-order reduction of the split slabs: a workgroup owns 256/SG consecutive outputs, split group g adds slabs
@@ -472,33 +507,17 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(WGRMulti t) {
 extern "C" {
 
 int nq_conv3_supported(int B, int Cin, int H, int W, int Cout, int k) {
-  // <= 4 channels on either side (the image head): the streaming VALU kernels of conv_head.hip are faster than a
-  // >80 %-padded MFMA tile (measured 0.17 / 0.23 ms vs 0.21 / 0.38 ms, forward / data gradient of 37->3 at 640x1280)
-  if (!(k == 3 || k == 5) || B <= 0 || Cin <= 0 || Cout <= 4 || Cin <= 4) return 0;
-  // the kernel addresses the input with 32-bit buffer offsets (conv_igemm3_impl.h): tensors of 4 GiB and more stay on
-  // the fp32 kernels
-  if ((int64_t)B * Cin * H * W * 4 >= 0xFFFFFF00ll) return 0;
-  // few-pixel kernel (conv_flat3.hip) -- offered for layers whose weight tensor is worth streaming; a toy convolution (a few
-  // hundred weights) stays on the exact-fp32 kernels: nothing to gain, and its callers keep fp32-level results
-  if (use_flat3(B, Cin, H, W, Cout, k, nullptr) && (int64_t)Cin * k * k * Cout >= 65536) return 1;
-  const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
-  return p.wgs * p.nsplit >= 128;  // still smaller grids stay on the fp32 split-K kernel
+  return shape_ok3(B, Cin, H, W, Cout, k) ? route_fwd3(B, Cin, H, W, Cout, k).supported : 0;
 }
 
 int64_t nq_conv_forward3_ws_floats(int B, int Cin, int H, int W, int Cout, int k) {
-  if (!(k == 3 || k == 5) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  int fns = 1;
-  if (use_flat3(B, Cin, H, W, Cout, k, &fns)) return fns > 1 ? (int64_t)fns * B * Cout * H * W : 0;
-  const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
-  return p.nsplit > 1 ? (int64_t)p.nsplit * B * Cout * H * W : 0;
+  return shape_ok3(B, Cin, H, W, Cout, k) ? route_fwd3(B, Cin, H, W, Cout, k).ws_floats : 0;
 }
 
 int64_t nq_conv3_weight_bytes(int Cin, int Cout, int k) {
   if (!(k == 3 || k == 5)) return 0;
-  const int mi = pick_mi3(Cout), mt = 16 * mi;
-  const int64_t co_tiles = (Cout + mt - 1) / mt, nchunk = (Cin + CC - 1) / CC;
-  (void)nchunk;
-  return total_steps3(Cin, k, mi) * 2 * co_tiles * 4 * mt * 16;
+  const int mt = 16 * pick_mi3(Cout);
+  return wl3_bytes(Cin, k * k, (Cout + mt - 1) / mt, mt);
 }
 
 // w: OIHW weight tensor of the STORED conv (Cout_w, Cin_w, k, k).  transposed = 0 -> operand of the forward conv
@@ -507,9 +526,9 @@ static bool wl3_fill(WL3& p, const float* w, void* wt3, int Cin, int Cout, int k
   if (!w || !wt3 || !(k == 3 || k == 5) || Cin <= 0 || Cout <= 0) return false;
   const int mi = pick_mi3(Cout);
   p.w = w; p.out = reinterpret_cast<uint4*>(wt3);
-  p.Cin = Cin; p.Cout = Cout; p.KK = k * k; p.NST = nst_of(k); p.tail = tail_kind_of(Cin, mi); p.NSTT = nstk_of(k, p.tail);
+  p.Cin = Cin; p.Cout = Cout; p.KK = k * k; p.NST = wl3_steps(p.KK, 0); p.tail = wl3_tail_kind(Cin); p.NSTT = wl3_steps(p.KK, p.tail);
   p.MT = 16 * mi; p.co_tiles = (Cout + p.MT - 1) / p.MT; p.nchunk = (Cin + CC - 1) / CC; p.transposed = transposed;
-  p.slots = total_steps3(Cin, k, mi) * p.co_tiles * 4 * p.MT;
+  p.slots = wl3_plane_slots(Cin, p.KK, p.co_tiles, p.MT);
   p.co16 = (p.co_tiles * p.MT + 15) / 16;
   return true;
 }
@@ -586,37 +605,32 @@ int nq_weight_layouts_all(const nq_wl3_seg* segs3, int n3, const nq_wl_seg* segs
 // kernel with >= 32-channel tiles stages it), bit NQ_EPI_Y_SPLIT -- the output y (the tiled kernel's own epilogue writes it: no
 // split-K; the few-pixel kernel when it leaves no slabs).  0 for shapes this path does not serve.
 int nq_conv3_split_io(int B, int Cin, int H, int W, int Cout, int k) {
-  if (!nq_conv3_supported(B, Cin, H, W, Cout, k)) return 0;
-  {   // few-pixel kernel: reads floats only; writes the words when it needs no slabs (its own epilogue runs)
-    int fns = 1;
-    if (use_flat3(B, Cin, H, W, Cout, k, &fns)) return fns == 1 ? NQ_EPI_Y_SPLIT : 0;
-  }
-  const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
-  return (p.mi >= 2 ? NQ_EPI_X_SPLIT : 0) | (p.nsplit == 1 ? NQ_EPI_Y_SPLIT : 0);
+  return shape_ok3(B, Cin, H, W, Cout, k) ? route_fwd3(B, Cin, H, W, Cout, k).split_io : 0;
 }
 
+// the route nq_conv_forward3 resolves for the shape, written out; of the tiled kernel also which build of the tile and how much
+// LDS its launch takes (the per-kernel-size rules of conv_igemm3_impl.h)
 int nq_conv_forward3_plan(int B, int Cin, int H, int W, int Cout, int k, nq_conv3_plan* out) {
-  if (!(k == 3 || k == 5) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || !out) return NQ_ERR_INVALID;
+  if (!shape_ok3(B, Cin, H, W, Cout, k) || !out) return NQ_ERR_INVALID;
+  const Fwd3Route rt = route_fwd3(B, Cin, H, W, Cout, k);
   nq_conv3_plan q{};
-  q.supported = nq_conv3_supported(B, Cin, H, W, Cout, k);
-  q.split_io = nq_conv3_split_io(B, Cin, H, W, Cout, k);
-  q.mi = pick_mi3(Cout);
-  q.tail = tail_kind_of(Cin, q.mi);
-  // the same questions, in the same order, as nq_conv_forward3 below
-  NqFlat3Plan fp;
-  if (use_flat3(B, Cin, H, W, Cout, k, nullptr, &fp)) {
+  q.supported = rt.supported;
+  q.split_io = rt.split_io;
+  q.mi = rt.mi;
+  q.tail = rt.tail;
+  q.nsplit = rt.nsplit; q.per_split = rt.per_split;
+  if (rt.flat) {
     q.kernel = NQ_CONV3_FLAT;
-    q.flat_nw = fp.nw; q.flat_nb = fp.nb; q.flat_mi = fp.mi;
-    q.nsplit = fp.nsplit; q.per_split = fp.per_split;
-    q.lds_bytes = q.lds_bytes_dgrad = fp.lds_bytes;
+    q.flat_nw = rt.fp.nw; q.flat_nb = rt.fp.nb; q.flat_mi = rt.fp.mi;
+    q.lds_bytes = q.lds_bytes_dgrad = rt.fp.lds_bytes;
   } else {
-    const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
     const int nchunk = (Cin + CC - 1) / CC;
+    const auto waves = k == 3 ? nq_conv3_waves_k3 : nq_conv3_waves_k5;
+    const auto lds = k == 3 ? nq_conv3_lds_k3 : nq_conv3_lds_k5;
     q.kernel = NQ_CONV3_TILED;
-    q.nsplit = p.nsplit; q.per_split = p.per;
-    q.waves = k == 3 ? nq_conv3_waves_k3(p.mi, nchunk, q.tail, p.nsplit, p.per) : nq_conv3_waves_k5(p.mi, nchunk, q.tail, p.nsplit, p.per);
-    q.lds_bytes = k == 3 ? nq_conv3_lds_k3(p.mi, NQ_EPI_PLAIN, p.nsplit) : nq_conv3_lds_k5(p.mi, NQ_EPI_PLAIN, p.nsplit);
-    q.lds_bytes_dgrad = k == 3 ? nq_conv3_lds_k3(p.mi, NQ_EPI_DGRAD_GELU, p.nsplit) : nq_conv3_lds_k5(p.mi, NQ_EPI_DGRAD_GELU, p.nsplit);
+    q.waves = waves(rt.mi, nchunk, rt.tail, rt.nsplit, rt.per_split);
+    q.lds_bytes = lds(rt.mi, NQ_EPI_PLAIN, rt.nsplit);
+    q.lds_bytes_dgrad = lds(rt.mi, NQ_EPI_DGRAD_GELU, rt.nsplit);
   }
   *out = q;
   return NQ_OK;
@@ -630,49 +644,38 @@ int nq_conv_forward3(const float* x, const void* wt3, const float* bias, float* 
   epilogue &= ~(NQ_EPI_X_SPLIT | NQ_EPI_Y_SPLIT);
   if (!x || !wt3 || (!y && epilogue != NQ_EPI_PS) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
   if (!(k == 3 || k == 5)) return NQ_ERR_UNSUPPORTED;
-  if (fmt & ~nq_conv3_split_io(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
+  // the one resolution of this call; here, because the split-word check is the next of the argument checks
+  const Fwd3Route rt = route_fwd3(B, Cin, H, W, Cout, k);
+  if (fmt & ~rt.split_io) return NQ_ERR_UNSUPPORTED;
   if (epilogue < 0 || epilogue > NQ_EPI_DGRAD_GELU) return NQ_ERR_INVALID;
   if ((epilogue == NQ_EPI_PS_GELU || epilogue == NQ_EPI_PS) && (!z || r <= 0 || Cout % (r * r) != 0)) return NQ_ERR_INVALID;
   if (epilogue == NQ_EPI_DGRAD_GELU && (!zprev || r <= 0 || H % r != 0 || W % r != 0)) return NQ_ERR_INVALID;
   if (B > 65535) return NQ_ERR_UNSUPPORTED;
   hipStream_t st = nq_s(stream);
-  {   // few-pixel layers: pixels of all frames as one flat GEMM dimension, waves split the K loop (conv_flat3.hip)
-    int fns = 1;
-    if (use_flat3(B, Cin, H, W, Cout, k, &fns)) {
-      if (fns > 1 && !ws) return NQ_ERR_INVALID;
-      const int mi = pick_mi3(Cout), kind = tail_kind_of(Cin, mi);
-      int rc = nq_conv_flat3(x, wt3, bias, y, z, zprev, ws, B, Cin, H, W, Cout, k, r, epilogue | fmt, 16 * mi, kind, nst_of(k),
-                             nstk_of(k, kind), st);
-      if (rc != NQ_OK || fns == 1) return rc;
-      return nq_conv_splitk_finish(ws, bias, y, z, zprev, B, H, W, Cout, r, epilogue, fns, st);
-    }
-  }
-  const Fwd3Plan p = plan_fwd3(B, Cin, H, W, Cout);
-  if (p.nsplit > 1 && !ws) return NQ_ERR_INVALID;
-  int rc = (k == 3) ? nq_conv_igemm3_k3(x, wt3, bias, y, z, zprev, B, Cin, H, W, Cout, r, epilogue | fmt, p.mi, p.nsplit, p.per, ws, st)
-                    : nq_conv_igemm3_k5(x, wt3, bias, y, z, zprev, B, Cin, H, W, Cout, r, epilogue | fmt, p.mi, p.nsplit, p.per, ws, st);
-  if (rc != NQ_OK || p.nsplit == 1) return rc;
-  return nq_conv_splitk_finish(ws, bias, y, z, zprev, B, H, W, Cout, r, epilogue, p.nsplit, st);
+  if (rt.nsplit > 1 && !ws) return NQ_ERR_INVALID;
+  int rc;
+  if (rt.flat)   // few-pixel layers: pixels of all frames as one flat GEMM dimension, waves split the K loop (conv_flat3.hip)
+    rc = nq_conv_flat3(x, wt3, bias, y, z, zprev, ws, B, Cin, H, W, Cout, k, r, epilogue | fmt, 16 * rt.mi, &rt.fp, st);
+  else
+    rc = (k == 3 ? nq_conv_igemm3_k3 : nq_conv_igemm3_k5)(x, wt3, bias, y, z, zprev, B, Cin, H, W, Cout, r, epilogue | fmt, rt.mi,
+                                                          rt.nsplit, rt.per_split, ws, st);
+  if (rc != NQ_OK || rt.nsplit == 1) return rc;
+  return nq_conv_splitk_finish(ws, bias, y, z, zprev, B, H, W, Cout, r, epilogue, rt.nsplit, st);
 }
 
 int nq_conv_wgrad3_supported(int B, int Cin, int H, int W, int Cout, int k) {
-  if (!(k == 3 || k == 5) || B <= 0 || Cin <= 0 || Cout <= 4) return 0;
-  if (nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) return 1;   // few-pixel layers: conv_wgrad_flat3.hip (no slabs)
-  return (int64_t)((W + 31) / 32) * H * B >= 128;  // enough 32-pixel segments to split over
+  return shape_ok3(B, Cin, H, W, Cout, k) ? route_wgrad3(B, Cin, H, W, Cout, k).supported : 0;
 }
 
 int nq_conv_wgrad3_plan(int B, int Cin, int H, int W, int Cout, int k, int* mi, int* ni, int* nsplit, int* pc) {
-  if (!(k == 3 || k == 5) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || !mi || !ni || !nsplit || !pc) return NQ_ERR_INVALID;
-  const Wg3Plan p = plan_wgrad3(B, Cin, H, W, Cout, k);
+  if (!shape_ok3(B, Cin, H, W, Cout, k) || !mi || !ni || !nsplit || !pc) return NQ_ERR_INVALID;
+  const Wg3Plan p = route_wgrad3(B, Cin, H, W, Cout, k).p;
   *mi = p.mi; *ni = p.ni; *nsplit = p.nsplit; *pc = p.pc;
   return NQ_OK;
 }
 
 int64_t nq_conv_wgrad3_ws_floats(int B, int Cin, int H, int W, int Cout, int k) {
-  if (!(k == 3 || k == 5) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  if (nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) return 4;   // no slabs (a token workspace keeps the pointer non-NULL)
-  Wg3Plan p = plan_wgrad3(B, Cin, H, W, Cout, k);
-  return (int64_t)p.nsplit * p.co_pad * ((int64_t)p.n_pad + 1);
+  return shape_ok3(B, Cin, H, W, Cout, k) ? route_wgrad3(B, Cin, H, W, Cout, k).ws_floats : 0;
 }
 
 static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
@@ -680,29 +683,28 @@ static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* d
 
 // Operands as split {hi | lo} words (include/nq_hip.h): fmt bit 0 -- x, bit 1 -- dy; where nq_conv_wgrad3_split_io says so
 int nq_conv_wgrad3_split_io(int B, int Cin, int H, int W, int Cout, int k) {
-  if (!nq_conv_wgrad3_supported(B, Cin, H, W, Cout, k) || nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) return 0;
-  const Wg3Plan p = plan_wgrad3(B, Cin, H, W, Cout, k);
-  return (p.pc == 1 || p.pc == 12 || p.pc == 14) ? 3 : 0;
+  return shape_ok3(B, Cin, H, W, Cout, k) ? route_wgrad3(B, Cin, H, W, Cout, k).split_io : 0;
 }
 
 // seg == NULL: split kernel + reduction; seg != NULL: the split kernel only, *seg describes the pending reduction
 int nq_conv_wgrad3(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
                    int k, int fmt, nq_wgr_seg* seg, nq_stream_t stream) {
-  if (fmt & ~nq_conv_wgrad3_split_io(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
   return conv_wgrad3_impl(x, dy, dw, db, ws, B, Cin, H, W, Cout, k, 0, seg, stream, fmt);
 }
 
 // Role-swapped form, arguments of the ORIGINAL layer: 0 where the few-pixel kernel owns the exchanged shape (it has no
 // transposing store, so nq_conv_wgrad3_swapped refuses it), else the slab size of the exchanged problem's plan
 int64_t nq_conv_wgrad3_swapped_ws_floats(int B, int Cin, int H, int W, int Cout, int k) {
-  if (nq_conv_wgrad_flat3_ok(B, Cout, H, W, Cin, k)) return 0;
-  return nq_conv_wgrad3_ws_floats(B, Cout, H, W, Cin, k);
+  if (!shape_ok3(B, Cin, H, W, Cout, k)) return 0;
+  const Wg3Route rt = route_wgrad3(B, Cout, H, W, Cin, k);
+  return rt.flat ? 0 : rt.ws_floats;
 }
 
 // where callers should route a weight gradient to the role-swapped form (narrower than what the launch accepts)
 int nq_conv_wgrad3_swapped_supported(int B, int Cin, int H, int W, int Cout, int k) {
-  return Cout <= 4 && Cin > 4 && Cout * k * k <= 64 && nq_conv_wgrad3_supported(B, Cout, H, W, Cin, k) &&
-         nq_conv_wgrad3_swapped_ws_floats(B, Cin, H, W, Cout, k) > 0;
+  if (!shape_ok3(B, Cin, H, W, Cout, k) || !(Cout <= 4 && Cin > 4 && Cout * k * k <= 64)) return 0;
+  const Wg3Route rt = route_wgrad3(B, Cout, H, W, Cin, k);
+  return rt.supported && !rt.flat;   // (a tiled plan always has slabs: its workspace is never 0)
 }
 
 int nq_conv_wgrad3_swapped(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int H, int W, int Cout, int k,
@@ -742,19 +744,21 @@ int nq_wgrad_reduce_multi(const nq_wgr_seg* segs, int nseg, nq_stream_t stream) 
 
 static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,
                             int Cout, int k, int swap_kk, nq_wgr_seg* seg, nq_stream_t stream, int fmt) {
+  // the one resolution of this call (a shape that fails the checks below has no route: no split words either)
+  const Wg3Route rt = shape_ok3(B, Cin, H, W, Cout, k) ? route_wgrad3(B, Cin, H, W, Cout, k) : Wg3Route{};
+  if (fmt & ~rt.split_io) return NQ_ERR_UNSUPPORTED;
   if (!x || !dy || !dw || !ws || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
   if (!(k == 3 || k == 5)) return NQ_ERR_UNSUPPORTED;
   if ((int64_t)Cout * H * W >= (1ll << 31) || (int64_t)Cin * H * W >= (1ll << 31)) return NQ_ERR_UNSUPPORTED;
-  if (swap_kk == 0 && nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) {
+  if (rt.flat) {
+    // Role-swapped entry (here Cin / Cout are those of the EXCHANGED problem): the few-pixel kernel has no transposing
+    // store and no slabs (nq_conv_wgrad3_swapped_ws_floats answers 0).  Refused.
+    if (swap_kk != 0) return NQ_ERR_UNSUPPORTED;
     // few-pixel layer: every output block is owned by one wave for the whole K range -- dw / db are final, nothing pending
-    if (fmt) return NQ_ERR_UNSUPPORTED;
     if (seg) *seg = nq_wgr_seg{nullptr, nullptr, dw, db, Cout, Cin * k * k, 0, 0, 0, 0, 1};
     return nq_conv_wgrad_flat3(x, dy, dw, db, B, Cin, H, W, Cout, k, nq_s(stream));
   }
-  // Role-swapped entry (here Cin / Cout are those of the EXCHANGED problem): the few-pixel kernel has no transposing
-  // store and no slabs (nq_conv_wgrad3_swapped_ws_floats answers 0).  Refused.
-  if (swap_kk != 0 && nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
-  Wg3Plan p = plan_wgrad3(B, Cin, H, W, Cout, k);
+  const Wg3Plan& p = rt.p;
   float* slab = ws;
   float* slab_db = ws + (int64_t)p.nsplit * p.co_pad * p.n_pad;
   hipStream_t st = nq_s(stream);
@@ -764,11 +768,10 @@ static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* d
   const int N = Cin * k * k;
   int64_t total = (int64_t)Cout * N + Cout;
   if (seg) {   // deferred: describe the reduction, nq_wgrad_reduce_multi runs it (same split groups as below)
-    *seg = nq_wgr_seg{slab, db ? slab_db : nullptr, dw, db, Cout, N, p.co_pad, p.n_pad, p.nsplit, swap_kk,
-                      (total < 65536 && p.nsplit >= 16) ? 16 : 4};
+    *seg = nq_wgr_seg{slab, db ? slab_db : nullptr, dw, db, Cout, N, p.co_pad, p.n_pad, p.nsplit, swap_kk, rt.sg};
     return NQ_OK;
   }
-  if (total < 65536 && p.nsplit >= 16) {
+  if (rt.sg == 16) {
     hipLaunchKernelGGL(wgrad3_reduce_kernel<16>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, slab, slab_db, dw, db,
                        Cout, N, p.co_pad, p.n_pad, p.nsplit, swap_kk);
   } else {

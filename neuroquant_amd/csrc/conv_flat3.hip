@@ -75,7 +75,7 @@ __global__ __launch_bounds__(NW * 64) void conv_flat3_kernel(FlatArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, kq = lane >> 4;
   constexpr int KK = KS * KS, pad = KS >> 1;
-  constexpr int NSTMAX = (KK + 1) / 2;   // k-steps of a full chunk (tail chunks have fewer)
+  constexpr int NSTMAX = wl3_steps(KK, 0);   // k-steps of a full chunk (tail chunks have fewer)
   const int H = a.H, W = a.W, HW = H * W, PW = W + 2 * pad, VH = H + 2 * pad;
   int id = (int)blockIdx.x;
   const int id1 = fdiv(id, a.dNG), pg = id - id1 * a.ngroups;
@@ -388,11 +388,12 @@ extern "C" int nq_conv_flat3_plan(int B, int Cin, int H, int W, int Cout, int k,
   return 1;
 }
 
+// plan: what nq_conv_flat3_plan answered for this shape (route_fwd3, conv3.hip); MT: the channel tile the operand was laid out with
 extern "C" int nq_conv_flat3(const float* x, const void* wt3, const float* bias, float* y, float* z, const float* zprev, float* slab,
-                             int B, int Cin, int H, int W, int Cout, int k, int r, int epi, int MT, int tail, int NST, int NSTT,
+                             int B, int Cin, int H, int W, int Cout, int k, int r, int epi, int MT, const NqFlat3Plan* plan,
                              hipStream_t st) {
-  NqFlat3Plan pl;
-  if (!nq_conv_flat3_plan(B, Cin, H, W, Cout, k, &pl)) return NQ_ERR_UNSUPPORTED;
+  if (!plan) return NQ_ERR_INVALID;
+  const NqFlat3Plan& pl = *plan;
   const int NWv = pl.nw, NBv = pl.nb, MIv = pl.mi, ns = pl.nsplit, per = pl.per_split;
   FlatArgs a{};
   a.x = x; a.wt3 = reinterpret_cast<const u32x4*>(wt3); a.bias = bias; a.y = y; a.z = z; a.zprev = zprev; a.slab = slab;
@@ -403,7 +404,7 @@ extern "C" int nq_conv_flat3(const float* x, const void* wt3, const float* bias,
   a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.KS = k; a.r = r; a.epi = epi;
   a.P = B * H * W;
   a.MT = MT; a.co_tiles = (Cout + MT - 1) / MT;
-  a.nchunk = (Cin + 15) / 16; a.tail = tail; a.NST = NST; a.NSTT = NSTT;
+  a.nchunk = (Cin + 15) / 16; a.tail = wl3_tail_kind(Cin); a.NST = wl3_steps(k * k, 0); a.NSTT = wl3_steps(k * k, a.tail);
   a.ngroups = pl.ngroups;
   a.cgroups = pl.cgroups;
   a.nsplit = ns; a.per_split = per;

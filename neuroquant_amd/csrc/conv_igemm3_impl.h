@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "conv3_layout.h"
 #include "nq_common.h"
 
 #ifndef NQ_KS
@@ -85,18 +86,11 @@ constexpr int TH = 8, TW = 32;
 constexpr int PH = TH + KS - 1, PW = TW + KS - 1;
 constexpr int NPIX = PH * PW;
 constexpr int PP = (NPIX + 15) / 16 * 16;  // octet-plane stride in pixels (16-byte units): multiple of 256 B
-constexpr int NST = (KK + 1) / 2;          // k-steps per channel chunk
-constexpr int NST8 = (KK + 3) / 4;         // k-steps of a tail chunk of <= 8 channels (lane group kq -> tap 4*step + kq)
-constexpr int NHALF = (KK + 1) / 2;        // (4 channels x 2 taps) slots of a half octet
-constexpr int NST4 = (NHALF + 3) / 4;      // k-steps of a tail chunk of <= 4 channels
-constexpr int NST12 = (KK + NHALF + 3) / 4;  // k-steps of a tail chunk of 9..12 channels
-constexpr int nst_of_kind(int kind) { return kind == 1 ? NST4 : (kind == 2 ? NST8 : (kind == 3 ? NST12 : NST)); }
-// kind of the last 16-channel chunk (Conv3Args::tail) for Cin input channels on the 16*mi-channel tile; shared with
-// nq_weight_layout3 (conv3.hip), which must lay the operand out the same way
-static inline int nq_conv3_tail_kind(int Cin, int mi) {
-  const int r = Cin - 16 * ((Cin + 15) / 16 - 1);
-  return r <= 4 ? 1 : (r <= 8 ? 2 : (r <= 12 ? 3 : 0));
-}
+// k-steps per chunk of this kernel size, by the kind of the chunk (conv3_layout.h: the operand's layout)
+constexpr int NST = wl3_steps(KK, 0);      // full chunk
+constexpr int NST4 = wl3_steps(KK, 1);     // tail chunk of <= 4 channels
+constexpr int NST8 = wl3_steps(KK, 2);     // tail chunk of <= 8 channels (lane group kq -> tap 4*step + kq)
+constexpr int NST12 = wl3_steps(KK, 3);    // tail chunk of 9..12 channels
 constexpr int CC = 16;                     // channels per chunk
 constexpr int PATCH_U4 = 2 * 2 * PP;       // 16-byte units per patch buffer: [plane][octet][PP]
 constexpr int NITEM = 2 * NPIX;            // staging items (octet, pixel)
@@ -356,7 +350,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     constexpr int PAR = decltype(par_c)::value;
     constexpr int TK = decltype(tail_c)::value;   // tail kind (Conv3Args::tail), 0 = full chunk
     constexpr bool TAIL = TK != 0;
-    constexpr int NSTC = nst_of_kind(TK);
+    constexpr int NSTC = wl3_steps(KK, TK);
     const int g0 = ch * NST;   // every chunk in front of this one is a full chunk
     steps3<0, NSTC>([&](auto st_c) {
       constexpr int st = decltype(st_c)::value;
@@ -774,7 +768,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 inline int igemm3_waves(int mi, int nchunk, int tail, int nsplit, int per_split) {
   if (mi > 3) return 2;
   static const int occ3_steps = [] { const char* e = getenv("NQ_IG3_OCC3_STEPS"); return e ? atoi(e) : NQ_IG3_OCC3_DEFAULT; }();
-  const int ksteps = (nsplit > 1 ? per_split : nchunk - 1) * NST + (nsplit > 1 ? 0 : nst_of_kind(tail));
+  const int ksteps = (nsplit > 1 ? per_split : nchunk - 1) * NST + (nsplit > 1 ? 0 : wl3_steps(KK, tail));
   return ksteps <= occ3_steps ? 3 : 2;
 }
 // Dynamic LDS of a launch; wide_epi: the data-gradient epilogue transposes through 4 waves x [MT][64] floats
@@ -826,9 +820,9 @@ extern "C" int NQ_CAT(nq_conv_igemm3_k, NQ_KS)(const float* x, const void* wt3, 
   a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.r = r; a.epi = epi;
   a.tiles_x = (W + TW - 1) / TW;
   a.nchunk = (Cin + CC - 1) / CC;
-  a.tail = nq_conv3_tail_kind(Cin, mi_sel);
+  a.tail = wl3_tail_kind(Cin);
   a.co_tiles = (Cout + 16 * mi_sel - 1) / (16 * mi_sel);
-  a.w_bytes = (unsigned)(((int64_t)(a.nchunk - 1) * NST + nst_of_kind(a.tail)) * 2 * a.co_tiles * 4 * (16 * mi_sel) * 16);
+  a.w_bytes = (unsigned)wl3_bytes(Cin, KK, a.co_tiles, 16 * mi_sel);
   const int tiles = a.tiles_x * ((H + TH - 1) / TH);
   if (xs) {   // (the 16-channel tile is not offered with split input: no layer of the shipped models pairs them)
     switch (mi_sel) {
@@ -849,10 +843,6 @@ extern "C" int NQ_CAT(nq_conv_igemm3_k, NQ_KS)(const float* x, const void* wt3, 
   }
 }
 
-// steps per chunk for this kernel size (used by nq_weight_layout3)
-extern "C" int NQ_CAT(nq_conv3_nst_k, NQ_KS)() { return NST; }
-extern "C" int NQ_CAT(nq_conv3_nst8_k, NQ_KS)() { return NST8; }
-extern "C" int NQ_CAT(nq_conv3_nstk_k, NQ_KS)(int kind) { return nst_of_kind(kind); }
 // launch rules of this kernel size for the plan query (conv3.hip): waves per SIMD of the build, dynamic LDS bytes
 extern "C" int NQ_CAT(nq_conv3_waves_k, NQ_KS)(int mi, int nchunk, int tail, int nsplit, int per_split) {
   return igemm3_waves(mi, nchunk, tail, nsplit, per_split);

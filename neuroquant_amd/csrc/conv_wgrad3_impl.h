@@ -813,7 +813,7 @@ extern "C" int NQ_CAT(nq_conv_wgrad3_k, NQ_KS)(const float* x, const float* dy, 
                                                 int ni_sel, int pc, int fmt, hipStream_t st) {
   Wgrad3Args a;
   a.x_split = fmt & 1; a.dy_split = (fmt >> 1) & 1;   // split {hi | lo} word operands: the row-segment producer/consumer variants only
-  if (fmt && !(pc == 1 || pc == 12 || pc == 14)) return NQ_ERR_UNSUPPORTED;
+  if (fmt && !nq_wgrad3_pc_takes_split(pc)) return NQ_ERR_UNSUPPORTED;
   a.x = x; a.dy = dy; a.slab = slab; a.slab_db = slab_db;
   a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.N = Cin * KK;
   a.co_pad = co_pad; a.n_pad = n_pad;

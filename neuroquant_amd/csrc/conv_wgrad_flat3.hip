@@ -178,7 +178,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_flat3_kernel(WFlatArgs a) {
 
 }  // namespace
 
-// 1 when the few-pixel weight-gradient kernel takes this shape (pure host function, shared with conv3.hip)
+// 1 when the few-pixel weight-gradient kernel takes this shape (pure host function; asked once per call, by route_wgrad3 in
+// conv3.hip, which sends nq_conv_wgrad_flat3 below only the shapes this accepts)
 extern "C" int nq_conv_wgrad_flat3_ok(int B, int Cin, int H, int W, int Cout, int k) {
   static const int enabled = [] { const char* e = getenv("NQ_WGRAD_FLAT3"); return !(e && e[0] == '0'); }();
   if (!enabled || !(k == 3 || k == 5) || B <= 0 || Cin <= 0 || Cout <= 4 || H <= 0 || W <= 0) return 0;
@@ -192,7 +193,6 @@ extern "C" int nq_conv_wgrad_flat3_ok(int B, int Cin, int H, int W, int Cout, in
 
 extern "C" int nq_conv_wgrad_flat3(const float* x, const float* dy, float* dw, float* db, int B, int Cin, int H, int W, int Cout,
                                    int k, hipStream_t st) {
-  if (!nq_conv_wgrad_flat3_ok(B, Cin, H, W, Cout, k)) return NQ_ERR_UNSUPPORTED;
   WFlatArgs a{};
   a.x = x; a.dy = dy; a.dw = dw; a.db = db;
   a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.KS = k;

@@ -83,6 +83,9 @@ __device__ __forceinline__ float nq_split_word_f(float v) { return __builtin_bit
 __device__ __forceinline__ float nq_split_word_value(unsigned w) {
   return __builtin_bit_cast(float, w & 0xffff0000u) + __builtin_bit_cast(float, w << 16);
 }
+// the weight-gradient kernels that take x / dy as split words: the row-segment producer/consumer variants (Wg3Plan::pc of
+// conv3.hip: 1 / 12 / 14 = 1 / 2 / 4 rows per segment); the one rule behind nq_conv_wgrad3_split_io and the launch
+static inline bool nq_wgrad3_pc_takes_split(int pc) { return pc == 1 || pc == 12 || pc == 14; }
 
 // ---- wave / block reductions (wave = 64 lanes) ----
 __device__ __forceinline__ float nq_wave_sum(float v) {
