@@ -100,8 +100,8 @@ NQ_API int nq_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
 
 /* ---- multi-tensor variants: ONE launch for all layers (the per-iteration parameter side is 14 small tensors; 42
  * launch-bound kernels become 3).  `segs` is a HOST array (copied into the kernel arguments, <= 16 segments per launch,
- * longer lists are chunked); every pointer inside is a device pointer.  Per-element arithmetic is identical to the
- * single-tensor entry points above (same results bit for bit). */
+ * longer lists are chunked); every pointer inside is a device pointer.  The single-tensor entry points above are
+ * one-segment launches of the same kernels. */
 typedef struct nq_ada_seg {
   const float* x;      /* weights (rows x row_len) */
   const float* gy;     /* backward only: gradient w.r.t. the fake-quantised output */
@@ -143,7 +143,7 @@ NQ_API int nq_adaround_forward_multi(const nq_ada_seg* segs, int nseg, nq_stream
 /* The UAQ fake-quant (nq_uaq_forward) / its d(delta) (nq_uaq_backward without dx) for several tensors in one launch:
  * phase 1 of the calibration (calib_model.py:119-165).  Uses x, gy (backward), delta, zp, out (forward: y; backward:
  * d(delta), one value per reduction row), rows, row_len, per_row, n_levels of nq_ada_seg; alpha / soft / reg_weight are
- * ignored.  Bit-identical to the single-tensor entry points. */
+ * ignored.  nq_uaq_forward / nq_uaq_backward are one-segment launches of the same kernels. */
 NQ_API int nq_uaq_forward_multi(const nq_ada_seg* segs, int nseg, nq_stream_t stream);
 NQ_API int nq_uaq_backward_multi(const nq_ada_seg* segs, int nseg, nq_stream_t stream);
 NQ_API int nq_adaround_backward_multi(const nq_ada_seg* segs, int nseg, float reg_b, nq_stream_t stream);

@@ -2,6 +2,7 @@
 #include <cstdlib>
 #include "nq_common.h"
 #include "conv3_layout.h"
+#include "seg_table.h"
 
 extern "C" {
 int nq_conv_igemm3_k3(const float*, const void*, const float*, float*, float*, const float*, int, int, int, int, int, int, int,
@@ -133,70 +134,42 @@ __device__ __forceinline__ void wl3_tile(const WL3& p, int c, int g16, float* __
   }
 }
 
+__device__ __forceinline__ void wl3_seg_tile(const WL3& p, int blk, float* T) {
+  if (p.KK == 25) wl3_tile<25>(p, blk / p.co16, blk % p.co16, T);
+  else wl3_tile<9>(p, blk / p.co16, blk % p.co16, T);
+}
 __global__ __launch_bounds__(256) void weight_layout3_kernel(WL3 p) {
   __shared__ float T[16 * (16 * WL3_KKMAX + 1)];
-  if (p.KK == 25) wl3_tile<25>(p, (int)blockIdx.x / p.co16, (int)blockIdx.x % p.co16, T);
-  else wl3_tile<9>(p, (int)blockIdx.x / p.co16, (int)blockIdx.x % p.co16, T);
+  wl3_seg_tile(p, (int)blockIdx.x, T);
 }
 
 // all layers' operands (forward and data-gradient) in ONE launch: the table travels as a kernel argument
-constexpr int WL3_MAXSEG = 16;
-struct WL3Multi {
-  WL3 s[WL3_MAXSEG];
-  int blk0[WL3_MAXSEG + 1];
-  int nseg;
-};
-__global__ __launch_bounds__(256) void weight_layout3_multi_kernel(WL3Multi t) {
+__global__ __launch_bounds__(256) void weight_layout3_multi_kernel(NqSegTable<WL3> t) {
   __shared__ float T[16 * (16 * WL3_KKMAX + 1)];
-  int k = 0;
-  while (k + 1 < t.nseg && (int)blockIdx.x >= t.blk0[k + 1]) ++k;
-  const int blk = (int)blockIdx.x - t.blk0[k];
-  if (t.s[k].KK == 25) wl3_tile<25>(t.s[k], blk / t.s[k].co16, blk % t.s[k].co16, T);
-  else wl3_tile<9>(t.s[k], blk / t.s[k].co16, blk % t.s[k].co16, T);
+  int blk;
+  const int k = t.find((int)blockIdx.x, blk);
+  wl3_seg_tile(t.s[k], blk, T);
 }
 
 // Round 4: the fp32 operands of the layers that stay on the fp32 / vector kernels (the 1 x 1 stem, the head) in the SAME launch
 // as the bf16x3 operands: blocks past the bf16x3 tiles run the element code of weight_layouts_multi_kernel (conv.hip) -- the
 // same values, one launch (~5 us of launch floor) less per iteration.
-struct WLF {
-  const float* w;
-  float* wt;
-  int Cout, Cin, KK, krows, ld, bwd;
-};
 struct WLAll {
-  WL3 s3[WL3_MAXSEG];
-  int blk3[WL3_MAXSEG + 1];
-  int n3;
-  WLF sf[WL3_MAXSEG];
-  int blkf[WL3_MAXSEG + 1];
-  int nf;
+  NqSegTable<WL3> t3;
+  NqSegTable<NqWLSeg> tf;
 };
 __global__ __launch_bounds__(256) void weight_layouts_all_kernel(WLAll t) {
   __shared__ float T[16 * (16 * WL3_KKMAX + 1)];
-  const int nb3 = t.blk3[t.n3];
+  const int nb3 = t.t3.blocks();
   if ((int)blockIdx.x < nb3) {
-    int k = 0;
-    while (k + 1 < t.n3 && (int)blockIdx.x >= t.blk3[k + 1]) ++k;
-    const int blk = (int)blockIdx.x - t.blk3[k];
-    if (t.s3[k].KK == 25) wl3_tile<25>(t.s3[k], blk / t.s3[k].co16, blk % t.s3[k].co16, T);
-    else wl3_tile<9>(t.s3[k], blk / t.s3[k].co16, blk % t.s3[k].co16, T);
+    int blk;
+    const int k = t.t3.find((int)blockIdx.x, blk);
+    wl3_seg_tile(t.t3.s[k], blk, T);
     return;
   }
-  const int bf = (int)blockIdx.x - nb3;
-  int k = 0;
-  while (k + 1 < t.nf && bf >= t.blkf[k + 1]) ++k;
-  const WLF& g = t.sf[k];
-  const int64_t i = (int64_t)(bf - t.blkf[k]) * 256 + threadIdx.x;
-  if (i >= (int64_t)g.krows * g.ld) return;
-  const int row = (int)(i / g.ld), col = (int)(i - (int64_t)row * g.ld);
-  float v = 0.f;
-  if (g.bwd) {   // wt[(co*KK + tap')][ci] = w[co][ci][KK-1-tap']
-    const int co = row / g.KK, tap = row - co * g.KK;
-    if (co < g.Cout && col < g.Cin) v = g.w[((int64_t)co * g.Cin + col) * g.KK + (g.KK - 1 - tap)];
-  } else {       // wt[k][co] = w[co][k]
-    if (col < g.Cout && row < g.Cin * g.KK) v = g.w[(int64_t)col * (g.Cin * g.KK) + row];
-  }
-  g.wt[i] = v;
+  int blk;
+  const int k = t.tf.find((int)blockIdx.x - nb3, blk);
+  nq_wl_elem(t.tf.s[k], (int64_t)blk * 256 + threadIdx.x);
 }
 
 // split-K of the forward / data-gradient kernel over 16-channel chunks when the pixel x channel grid alone cannot fill
@@ -434,25 +407,18 @@ __global__ __launch_bounds__(256) void wgrad3_reduce_kernel(const float* __restr
 
 // Several pending reductions in ONE launch (nq_wgrad_reduce_multi): per segment the arithmetic of wgrad3_reduce_kernel<sg>
 // (sg = 4 / 16) or of the sequential fp32 reduction (sg = 1), so results are bit-identical to the single-tensor launches.
-constexpr int WGR_MAXSEG = 16;
-struct WGRMulti {
-  nq_wgr_seg s[WGR_MAXSEG];
-  int blk0[WGR_MAXSEG + 1];
-  int nseg;
-};
 // (round 3: a thread owns FOUR consecutive n of one channel -- one 16-byte load per slab instead of four 4-byte ones; the
 // launch read 115 MB of slabs at 2.8 TB/s with scalar loads.  Per output the slabs are still added in the order
 // j = g, g + SG, ... and the SG partial sums in the order 0 .. SG-1: bit-identical to the scalar form.)
-__global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(WGRMulti t) {
+__global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(NqSegTable<nq_wgr_seg> t) {
   __shared__ float4 part[256];
-  int k = 0;
-  while (k + 1 < t.nseg && (int)blockIdx.x >= t.blk0[k + 1]) ++k;
-  const nq_wgr_seg& q = t.s[k];
+  int blk;
+  const nq_wgr_seg& q = t.s[t.find((int)blockIdx.x, blk)];
   const int SG = q.sg, OG = 256 / SG;
   const int o = threadIdx.x % OG, g = threadIdx.x / OG;
   const int N = q.N, Cout = q.Cout, nsplit = q.nsplit;
   const int NQ = (N + 3) >> 2;                                   // quads per channel (n_pad is a multiple of 16)
-  const int64_t i = (int64_t)((int)blockIdx.x - t.blk0[k]) * OG + o;   // quad index, then the bias entries
+  const int64_t i = (int64_t)blk * OG + o;   // quad index, then the bias entries
   const int64_t total = (int64_t)Cout * NQ;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   int co = 0, n = 0;
@@ -540,22 +506,17 @@ int nq_weight_layout3(const float* w, void* wt3, int Cin, int Cout, int k, int t
   return nq_launch_status();
 }
 
+// table segment of one bf16x3 operand: its workgroups or NQ_ERR_INVALID
+static int64_t wl3_seg_fill(const nq_wl3_seg& h, WL3& d) {
+  return wl3_fill(d, h.w, h.wt3, h.Cin, h.Cout, h.k, h.transposed) ? d.nchunk * d.co16 : NQ_ERR_INVALID;
+}
+
 int nq_weight_layout3_multi(const nq_wl3_seg* segs, int nseg, nq_stream_t stream) {
-  if (!segs || nseg <= 0) return NQ_ERR_INVALID;
-  for (int base = 0; base < nseg; base += WL3_MAXSEG) {
-    WL3Multi t;
-    t.nseg = (nseg - base < WL3_MAXSEG) ? nseg - base : WL3_MAXSEG;
-    int blocks = 0;
-    for (int i = 0; i < t.nseg; ++i) {
-      const nq_wl3_seg& h = segs[base + i];
-      if (!wl3_fill(t.s[i], h.w, h.wt3, h.Cin, h.Cout, h.k, h.transposed)) return NQ_ERR_INVALID;
-      t.blk0[i] = blocks;
-      blocks += t.s[i].nchunk * t.s[i].co16;
-    }
-    t.blk0[t.nseg] = blocks;
-    hipLaunchKernelGGL(weight_layout3_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, nq_s(stream), t);
-  }
-  return nq_launch_status();
+  return NqSegTable<WL3>::launch_all(
+      segs, nseg, [&](int i, WL3& d) { return wl3_seg_fill(segs[i], d); },
+      [&](const NqSegTable<WL3>& t, unsigned blocks) {
+        hipLaunchKernelGGL(weight_layout3_multi_kernel, dim3(blocks), dim3(256), 0, nq_s(stream), t);
+      });
 }
 
 int nq_weight_layouts_all(const nq_wl3_seg* segs3, int n3, const nq_wl_seg* segsf, int nf, nq_stream_t stream) {
@@ -563,41 +524,21 @@ int nq_weight_layouts_all(const nq_wl3_seg* segs3, int n3, const nq_wl_seg* segs
   // count the fp32 operands (one per direction)
   int nfo = 0;
   for (int i = 0; i < nf; ++i) nfo += (segsf[i].wt_fwd ? 1 : 0) + (segsf[i].wt_bwd ? 1 : 0);
-  if (n3 > WL3_MAXSEG || nfo > WL3_MAXSEG || n3 == 0 || nfo == 0) {   // does not fit one argument block: the two launches
+  if (n3 > 16 || nfo > 16 || n3 == 0 || nfo == 0) {   // does not fit one argument block: the two launches
     if (n3 > 0)
       if (int rc = nq_weight_layout3_multi(segs3, n3, stream)) return rc;
     if (nf > 0) return nq_weight_layouts_multi(segsf, nf, stream);
     return NQ_OK;
   }
   WLAll t;
-  t.n3 = n3;
-  int blocks = 0;
-  for (int i = 0; i < n3; ++i) {
-    const nq_wl3_seg& h = segs3[i];
-    if (!wl3_fill(t.s3[i], h.w, h.wt3, h.Cin, h.Cout, h.k, h.transposed)) return NQ_ERR_INVALID;
-    t.blk3[i] = blocks;
-    blocks += t.s3[i].nchunk * t.s3[i].co16;
-  }
-  t.blk3[n3] = blocks;
-  t.nf = 0;
-  int bf = 0;
-  for (int i = 0; i < nf; ++i) {
-    const nq_wl_seg& h = segsf[i];
-    if (!h.w || h.Cout <= 0 || h.Cin <= 0 || h.k <= 0) return NQ_ERR_INVALID;
-    const int KK = h.k * h.k;
-    for (int bwd = 0; bwd < 2; ++bwd) {
-      float* wt = bwd ? h.wt_bwd : h.wt_fwd;
-      if (!wt) continue;
-      const int krows = bwd ? h.krows_bwd : h.krows_fwd, ld = bwd ? h.ld_bwd : h.ld_fwd;
-      if (bwd ? (krows < h.Cout * KK || ld < h.Cin) : (krows < h.Cin * KK || ld < h.Cout)) return NQ_ERR_INVALID;
-      t.sf[t.nf] = WLF{h.w, wt, h.Cout, h.Cin, KK, krows, ld, bwd};
-      t.blkf[t.nf] = bf;
-      bf += (int)(((int64_t)krows * ld + 255) / 256);
-      ++t.nf;
-    }
-  }
-  t.blkf[t.nf] = bf;
-  hipLaunchKernelGGL(weight_layouts_all_kernel, dim3((unsigned)(blocks + bf)), dim3(256), 0, nq_s(stream), t);
+  t.t3.clear();
+  t.tf.clear();
+  const auto fits = [] {};   // counted above: neither table runs full
+  if (int rc = t.t3.fill_all(n3, [&](int i, WL3& d) { return wl3_seg_fill(segs3[i], d); }, fits)) return rc;
+  if (int rc = t.tf.fill_all(2 * nf, [&](int i, NqWLSeg& d) { return nq_wl_fill(segsf, i, d); }, fits)) return rc;
+  const int64_t blocks = (int64_t)t.t3.blocks() + t.tf.blocks();
+  if (blocks > 0x7fffffffLL) return NQ_ERR_INVALID;
+  hipLaunchKernelGGL(weight_layouts_all_kernel, dim3((unsigned)blocks), dim3(256), 0, nq_s(stream), t);
   return nq_launch_status();
 }
 
@@ -714,32 +655,22 @@ int nq_conv_wgrad3_swapped(const float* x, const float* dy, float* dw, float* ws
 }
 
 int nq_wgrad_reduce_multi(const nq_wgr_seg* segs, int nseg, nq_stream_t stream) {
-  if (!segs || nseg < 0) return NQ_ERR_INVALID;
-  WGRMulti t;
-  t.nseg = 0;
-  int blocks = 0;
-  auto flush = [&]() {
-    if (t.nseg == 0) return;
-    t.blk0[t.nseg] = blocks;
-    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, nq_s(stream), t);
-    t.nseg = 0;
-    blocks = 0;
-  };
-  for (int i = 0; i < nseg; ++i) {
-    const nq_wgr_seg& h = segs[i];
-    if (h.nsplit == 0) continue;   // nothing pending (the kernel wrote dw itself)
-    if (!h.slab || !h.dw || h.Cout <= 0 || h.N <= 0 || h.nsplit < 0 || !(h.sg == 1 || h.sg == 4 || h.sg == 16) ||
-        (h.db && !h.slab_db))
-      return NQ_ERR_INVALID;
-    if (t.nseg == WGR_MAXSEG) flush();
-    t.s[t.nseg] = h;
-    t.blk0[t.nseg] = blocks;
-    const int og = 256 / h.sg;
-    blocks += (int)(((int64_t)h.Cout * ((h.N + 3) / 4) + h.Cout + og - 1) / og);   // quads of n, then the bias entries
-    ++t.nseg;
-  }
-  flush();
-  return nq_launch_status();
+  if (segs && nseg == 0) return nq_launch_status();   // an empty list is no error here
+  return NqSegTable<nq_wgr_seg>::launch_all(
+      segs, nseg,
+      [&](int i, nq_wgr_seg& d) -> int64_t {
+        const nq_wgr_seg& h = segs[i];
+        if (h.nsplit == 0) return 0;   // nothing pending (the kernel wrote dw itself)
+        if (!h.slab || !h.dw || h.Cout <= 0 || h.N <= 0 || h.nsplit < 0 || !(h.sg == 1 || h.sg == 4 || h.sg == 16) ||
+            (h.db && !h.slab_db))
+          return NQ_ERR_INVALID;
+        d = h;
+        const int og = 256 / h.sg;
+        return ((int64_t)h.Cout * ((h.N + 3) / 4) + h.Cout + og - 1) / og;   // quads of n, then the bias entries
+      },
+      [&](const NqSegTable<nq_wgr_seg>& t, unsigned blocks) {
+        hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), 0, nq_s(stream), t);
+      });
 }
 
 static int conv_wgrad3_impl(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W,

@@ -10,6 +10,7 @@
 // same order as the oracle, scaled by 1/sqrt(n) on the way out.  HBM-bound (one read + one write of the weight).
 #include "nq_common.h"
 #include "quant_elem.h"
+#include "seg_table.h"
 
 namespace {
 
@@ -22,7 +23,6 @@ namespace {
 #define NQ_FWHT_TPB 512
 #endif
 constexpr int TPB = NQ_FWHT_TPB;
-constexpr int FW_MAXSEG_FQ = 16;
 #ifndef NQ_FWHT_TILE
 #define NQ_FWHT_TILE 8192
 #endif
@@ -70,69 +70,87 @@ __device__ __forceinline__ void fwht_stages(float* lds, int n, int log2n, int TC
   else if (log2n - s == 1) fwht_pass<1>(lds, n, s, TC, LD);
 }
 
-__device__ __forceinline__ void fwht_block(float* lds, int blk, const float* __restrict__ x, float* __restrict__ y,
-                                           int64_t outer, int n, int log2n, int inner, int n_in, int n_out, int OPB,
-                                           float sqrt_n) {
-  const int64_t o0 = (int64_t)blk * OPB;
-  const int nob = (int)min((int64_t)OPB, outer - o0);   // outer rows of this block
-  const int TC = OPB * inner, LD = TC + 1;
-  // rows [n_in, n): the zero padding
-  for (int e = threadIdx.x; e < (n - n_in) * TC; e += TPB) {
-    const int c = n_in + e / TC, t = e - (e / TC) * TC;
-    lds[c * LD + t] = 0.f;
+// A workgroup's tile: OPB outer rows from o0 on (nob of them exist), TC columns, LDS row stride LD
+struct Tile {
+  int64_t o0;
+  int nob, TC, LD;
+  __device__ __forceinline__ Tile(int blk, int OPB, int64_t outer, int inner)
+      : o0((int64_t)blk * OPB), nob((int)min((int64_t)OPB, outer - o0)), TC(OPB * inner), LD(TC + 1) {}
+};
+
+// Linear sweep over a tile's contiguous piece [outer row][nc channels][inner] of global memory: the (channel, inner, outer
+// row) coordinates of element e = tid + TPB j are STEPPED from one j to the next (two compares instead of two integer
+// divisions per element: the divisions were most of this kernel's instructions -- 23.5 us for 43 MB on NeRV-3M's layers)
+struct TileWalk {
+  int c, ii, ol, nc, inner, d_c, d_i;   // TPB = d_c * inner + d_i
+  __device__ __forceinline__ TileWalk(int nc_, int inner_) : nc(nc_), inner(inner_), d_c(TPB / inner_), d_i(TPB - d_c * inner_) {
+    const int per_o = nc * inner;
+    ol = threadIdx.x / per_o;
+    const int r = threadIdx.x - ol * per_o;
+    c = r / inner;
+    ii = r - c * inner;
   }
-  // rows [0, n_in): linear sweep over the block's contiguous input.  The (outer row, channel, inner) coordinates of element
-  // e = tid + 256 j are STEPPED from one iteration to the next (two compares instead of two integer divisions per element:
-  // the divisions were most of this kernel's instructions -- 23.5 us for 43 MB on NeRV-3M's layers)
-  const int d_c = TPB / inner, d_i = TPB - d_c * inner;   // 256 = d_c * inner + d_i
-  {
-    const int per_o = n_in * inner, total = nob * per_o;
-    const float* __restrict__ xb = x + o0 * per_o;
-    int ol = threadIdx.x / per_o, r = threadIdx.x - ol * per_o;
-    int c = r / inner, ii = r - c * inner;
-    for (int e = threadIdx.x; e < OPB * per_o; e += TPB) {
-      lds[c * LD + ol * inner + ii] = (e < total) ? xb[e] : 0.f;
-      ii += d_i;
-      c += d_c;
-      if (ii >= inner) {
-        ii -= inner;
-        ++c;
-      }
-      while (c >= n_in) {
-        c -= n_in;
-        ++ol;
-      }
+  __device__ __forceinline__ int lds(int LD) const { return c * LD + ol * inner + ii; }   // the element's place in the LDS tile
+  __device__ __forceinline__ void step() {
+    ii += d_i;
+    c += d_c;
+    if (ii >= inner) {
+      ii -= inner;
+      ++c;
+    }
+    while (c >= nc) {
+      c -= nc;
+      ++ol;
     }
   }
+};
+
+// tile <- x (outer, n_in, inner), rows [n_in, n) zero: the padding
+__device__ __forceinline__ void fwht_load_tile(float* lds, const Tile& T, const float* __restrict__ x, int n, int n_in, int inner,
+                                               int OPB) {
+  for (int e = threadIdx.x; e < (n - n_in) * T.TC; e += TPB) {
+    const int c = n_in + e / T.TC, t = e - (e / T.TC) * T.TC;
+    lds[c * T.LD + t] = 0.f;
+  }
+  const int per_o = n_in * inner, total = T.nob * per_o;
+  const float* __restrict__ xb = x + T.o0 * per_o;
+  TileWalk w(n_in, inner);
+  for (int e = threadIdx.x; e < OPB * per_o; e += TPB, w.step()) lds[w.lds(T.LD)] = (e < total) ? xb[e] : 0.f;
+}
+
+// y (outer, n_out, inner) <- the tile's first n_out entries.  The scale is the oracle's division by sqrt(n); for n = 4^k it is
+// an exact power of two and a multiplication gives the same bits
+__device__ __forceinline__ void fwht_store_tile(const float* lds, const Tile& T, float* __restrict__ y, int n_out, int inner,
+                                                int log2n, float sqrt_n) {
+  const int per_o = n_out * inner, total = T.nob * per_o;
+  float* __restrict__ yb = y + T.o0 * per_o;
+  const bool pow2 = (log2n & 1) == 0;
+  const float inv = 1.0f / sqrt_n;
+  TileWalk w(n_out, inner);
+  for (int e = threadIdx.x; e < total; e += TPB, w.step()) {
+    const float v = lds[w.lds(T.LD)];
+    yb[e] = pow2 ? v * inv : v / sqrt_n;
+  }
+}
+
+// One tensor of nq_fwht / nq_fwht_multi
+struct FwSeg {
+  const float* x;
+  float* y;
+  int64_t outer;
+  int n, log2n, inner, n_in, n_out, OPB;
+  float sqrt_n;
+};
+
+__device__ __forceinline__ void fwht_block(float* lds, int blk, const FwSeg& g) {
+  const Tile T(blk, g.OPB, g.outer, g.inner);
+  fwht_load_tile(lds, T, g.x, g.n, g.n_in, g.inner, g.OPB);
   __syncthreads();
   // butterflies: up to three stages per pass over LDS (an element's 8 / 4 / 2 partners in registers), each stage the same
   // (a, b) -> (a + b, a - b) on the same operands as the one-stage-per-pass loop (bit-identical), with a third of the
   // LDS round trips and barriers
-  fwht_stages(lds, n, log2n, TC, LD);
-  // store the first n_out entries: linear sweep over the block's contiguous output (coordinates stepped as above).  The
-  // scale is the oracle's division by sqrt(n); for n = 4^k it is an exact power of two and a multiplication gives the same bits
-  {
-    const int per_o = n_out * inner, total = nob * per_o;
-    float* __restrict__ yb = y + o0 * per_o;
-    const bool pow2 = (log2n & 1) == 0;
-    const float inv = 1.0f / sqrt_n;
-    int ol = threadIdx.x / per_o, r = threadIdx.x - ol * per_o;
-    int c = r / inner, ii = r - c * inner;
-    for (int e = threadIdx.x; e < total; e += TPB) {
-      const float v = lds[c * LD + ol * inner + ii];
-      yb[e] = pow2 ? v * inv : v / sqrt_n;
-      ii += d_i;
-      c += d_c;
-      if (ii >= inner) {
-        ii -= inner;
-        ++c;
-      }
-      while (c >= n_out) {
-        c -= n_out;
-        ++ol;
-      }
-    }
-  }
+  fwht_stages(lds, g.n, g.log2n, T.TC, T.LD);
+  fwht_store_tile(lds, T, g.y, g.n_out, g.inner, g.log2n, g.sqrt_n);
 }
 
 // ---- round 4: the AdaRound fake-quant / its backward + Adam fused with the transform (NeRV-3M + Hadamard spends a sixth of an
@@ -153,78 +171,32 @@ struct FqSeg {
   int n, log2n, inner, c_in, OPB, per_row, soft;
   float sqrt_n, qmax, reg_weight;
 };
-struct FqMulti {
-  FqSeg s[FW_MAXSEG_FQ];
-  int blk0[FW_MAXSEG_FQ + 1];
-  int nseg;
-};
 
 // forward: y = H(Q(x))[:, :c_in]  (quant_layer.py:70-71 with AdaRoundQuantizer.forward, quantizer.py:288-300)
 __device__ __forceinline__ void fq_fwht_tile(float* lds, int blk, const FqSeg& g) {
-  const int n = g.n, inner = g.inner, OPB = g.OPB;
-  const int64_t o0 = (int64_t)blk * OPB;
-  const int nob = (int)min((int64_t)OPB, g.outer - o0);
-  const int TC = OPB * inner, LD = TC + 1;
-  const int d_c = TPB / inner, d_i = TPB - d_c * inner;
-  {
-    const int per_o = n * inner, total = nob * per_o;
-    const float* __restrict__ xb = g.x + o0 * per_o;
-    const float* __restrict__ ab = g.alpha + o0 * per_o;
-    int ol = threadIdx.x / per_o, r = threadIdx.x - ol * per_o;
-    int c = r / inner, ii = r - c * inner;
-    for (int e = threadIdx.x; e < OPB * per_o; e += TPB) {
-      float q = 0.f;
-      if (e < total) {
-        const int64_t row = g.per_row ? o0 + ol : 0;
-        float xq;
-        q = ada_fwd_elem(xb[e], ab[e], g.delta[row], g.zp[row], g.qmax, g.soft, xq);
-      }
-      lds[c * LD + ol * inner + ii] = q;
-      ii += d_i;
-      c += d_c;
-      if (ii >= inner) {
-        ii -= inner;
-        ++c;
-      }
-      while (c >= n) {
-        c -= n;
-        ++ol;
-      }
+  const Tile T(blk, g.OPB, g.outer, g.inner);
+  const int per_o = g.n * g.inner, total = T.nob * per_o;
+  const float* __restrict__ xb = g.x + T.o0 * per_o;
+  const float* __restrict__ ab = g.alpha + T.o0 * per_o;
+  TileWalk w(g.n, g.inner);
+  for (int e = threadIdx.x; e < g.OPB * per_o; e += TPB, w.step()) {
+    float q = 0.f;
+    if (e < total) {
+      const int64_t row = g.per_row ? T.o0 + w.ol : 0;
+      float xq;
+      q = ada_fwd_elem(xb[e], ab[e], g.delta[row], g.zp[row], g.qmax, g.soft, xq);
     }
+    lds[w.lds(T.LD)] = q;
   }
   __syncthreads();
-  fwht_stages(lds, n, g.log2n, TC, LD);
-  {
-    const int n_out = g.c_in;
-    const int per_o = n_out * inner, total = nob * per_o;
-    float* __restrict__ yb = g.y + o0 * per_o;
-    const bool pow2 = (g.log2n & 1) == 0;
-    const float inv = 1.0f / g.sqrt_n;
-    int ol = threadIdx.x / per_o, r = threadIdx.x - ol * per_o;
-    int c = r / inner, ii = r - c * inner;
-    for (int e = threadIdx.x; e < total; e += TPB) {
-      const float v = lds[c * LD + ol * inner + ii];
-      yb[e] = pow2 ? v * inv : v / g.sqrt_n;
-      ii += d_i;
-      c += d_c;
-      if (ii >= inner) {
-        ii -= inner;
-        ++c;
-      }
-      while (c >= n_out) {
-        c -= n_out;
-        ++ol;
-      }
-    }
-  }
+  fwht_stages(lds, g.n, g.log2n, T.TC, T.LD);
+  fwht_store_tile(lds, T, g.y, g.c_in, g.inner, g.log2n, g.sqrt_n);
 }
 
-__global__ __launch_bounds__(TPB) void adaround_fwht_multi_kernel(FqMulti t) {
+__global__ __launch_bounds__(TPB) void adaround_fwht_multi_kernel(NqSegTable<FqSeg> t) {
   __shared__ float lds[LDS_FLOATS];
-  int k = 0;
-  while (k + 1 < t.nseg && (int)blockIdx.x >= t.blk0[k + 1]) ++k;
-  const FqSeg& g = t.s[k];
-  const int blk = (int)blockIdx.x - t.blk0[k];
+  int blk;
+  const FqSeg& g = t.s[t.find((int)blockIdx.x, blk)];
   if (g.n > 0) {
     fq_fwht_tile(lds, blk, g);
     return;
@@ -241,115 +213,64 @@ __global__ __launch_bounds__(TPB) void adaround_fwht_multi_kernel(FqMulti t) {
 }
 
 // backward: g_T = H(pad(gy)) (the transform is its own transpose), then d(alpha) = ada_bwd_elem(x, g_T, alpha, ...) (+ the
-// regulariser's gradient) and Adam's update of alpha -- the arithmetic of adaround_adam_multi_kernel (quant.hip) element by
-// element, so alpha / m / v come out bit-identical to nq_fwht_multi + nq_adaround_adam_multi.
-__device__ __forceinline__ void fwht_ada_adam_tile(float* lds, int blk, const FqSeg& g, float reg_b, float rw, float step_size,
-                                                   float beta1, float beta2, float eps, float bc2_sqrt) {
-  const int n = g.n, inner = g.inner, OPB = g.OPB, n_in = g.c_in;
-  const int64_t o0 = (int64_t)blk * OPB;
-  const int nob = (int)min((int64_t)OPB, g.outer - o0);
-  const int TC = OPB * inner, LD = TC + 1;
-  for (int e = threadIdx.x; e < (n - n_in) * TC; e += TPB) {
-    const int c = n_in + e / TC, tt = e - (e / TC) * TC;
-    lds[c * LD + tt] = 0.f;
-  }
-  const int d_c = TPB / inner, d_i = TPB - d_c * inner;
-  {
-    const int per_o = n_in * inner, total = nob * per_o;
-    const float* __restrict__ xb = g.gy + o0 * per_o;
-    int ol = threadIdx.x / per_o, r = threadIdx.x - ol * per_o;
-    int c = r / inner, ii = r - c * inner;
-    for (int e = threadIdx.x; e < OPB * per_o; e += TPB) {
-      lds[c * LD + ol * inner + ii] = (e < total) ? xb[e] : 0.f;
-      ii += d_i;
-      c += d_c;
-      if (ii >= inner) {
-        ii -= inner;
-        ++c;
-      }
-      while (c >= n_in) {
-        c -= n_in;
-        ++ol;
-      }
-    }
-  }
+// regulariser's gradient) and Adam's update of alpha
+__device__ __forceinline__ void fwht_ada_adam_tile(float* lds, int blk, const FqSeg& g, const StepScalars& sc, float rw,
+                                                   float beta1, float beta2, float eps) {
+  const Tile T(blk, g.OPB, g.outer, g.inner);
+  fwht_load_tile(lds, T, g.gy, g.n, g.c_in, g.inner, g.OPB);
   __syncthreads();
-  fwht_stages(lds, n, g.log2n, TC, LD);
-  {
-    // d(alpha) + Adam over the tile, FQ_U elements per thread and round: ALL of a round's global loads are issued before its
-    // first store (the stores to m / v / alpha may alias the next loads as far as the compiler knows, so one element per loop
-    // iteration was one exposed memory round trip per element -- 16 per workgroup and launch).  Elements past the tile load
-    // the tile's last element (unconditional loads, no branches) and store nothing.  Same arithmetic per element.
-    const int per_o = n * inner, total = nob * per_o;
-    const int64_t base = o0 * per_o;
-    const bool pow2 = (g.log2n & 1) == 0;
-    const float inv = 1.0f / g.sqrt_n;
-    int ol = threadIdx.x / per_o, r = threadIdx.x - ol * per_o;
-    int c = r / inner, ii = r - c * inner;
-    for (int e0 = threadIdx.x; e0 < total; e0 += FQ_U * TPB) {
-      float xv[FQ_U], av[FQ_U], mv[FQ_U], vv[FQ_U], dl[FQ_U], zq[FQ_U], tv[FQ_U];
+  fwht_stages(lds, g.n, g.log2n, T.TC, T.LD);
+  // d(alpha) + Adam over the tile, FQ_U elements per thread and round: ALL of a round's global loads are issued before its
+  // first store (the stores to m / v / alpha may alias the next loads as far as the compiler knows, so one element per loop
+  // iteration was one exposed memory round trip per element -- 16 per workgroup and launch).  Elements past the tile load
+  // the tile's last element (unconditional loads, no branches) and store nothing.
+  const int per_o = g.n * g.inner, total = T.nob * per_o;
+  const int64_t base = T.o0 * per_o;
+  const bool pow2 = (g.log2n & 1) == 0;
+  const float inv = 1.0f / g.sqrt_n;
+  TileWalk w(g.n, g.inner);
+  for (int e0 = threadIdx.x; e0 < total; e0 += FQ_U * TPB) {
+    float xv[FQ_U], av[FQ_U], mv[FQ_U], vv[FQ_U], dl[FQ_U], zq[FQ_U], tv[FQ_U];
 #pragma unroll
-      for (int u = 0; u < FQ_U; ++u) {
-        const int e = e0 + u * TPB;
-        const bool ok = e < total;
-        const int64_t i = base + (ok ? e : total - 1);
-        const int64_t row = g.per_row ? o0 + (ok ? ol : nob - 1) : 0;
-        xv[u] = g.x[i];
-        av[u] = g.alpha[i];
-        mv[u] = g.m[i];
-        vv[u] = g.v[i];
-        dl[u] = g.delta[row];
-        zq[u] = g.zp[row];
-        tv[u] = lds[ok ? c * LD + ol * inner + ii : 0];
-        ii += d_i;
-        c += d_c;
-        if (ii >= inner) {
-          ii -= inner;
-          ++c;
-        }
-        while (c >= n) {
-          c -= n;
-          ++ol;
-        }
-      }
+    for (int u = 0; u < FQ_U; ++u, w.step()) {
+      const int e = e0 + u * TPB;
+      const bool ok = e < total;
+      const int64_t i = base + (ok ? e : total - 1);
+      const int64_t row = g.per_row ? T.o0 + (ok ? w.ol : T.nob - 1) : 0;
+      xv[u] = g.x[i];
+      av[u] = g.alpha[i];
+      mv[u] = g.m[i];
+      vv[u] = g.v[i];
+      dl[u] = g.delta[row];
+      zq[u] = g.zp[row];
+      tv[u] = lds[ok ? w.lds(T.LD) : 0];
+    }
 #pragma unroll
-      for (int u = 0; u < FQ_U; ++u) {
-        const int e = e0 + u * TPB;
-        if (e < total) {
-          const int64_t i = base + e;
-          const float gv = pow2 ? tv[u] * inv : tv[u] / g.sqrt_n;          // what nq_fwht stores
-          const float gr = ada_bwd_elem(xv[u], gv, av[u], dl[u], zq[u], g.qmax, rw, reg_b);
-          float mi = mv[u], vi = vv[u];
-          mi = mi + (1.f - beta1) * (gr - mi);
-          vi = vi * beta2 + (1.f - beta2) * (gr * gr);
-          const float denom = sqrtf(vi) / bc2_sqrt + eps;
-          g.m[i] = mi;
-          g.v[i] = vi;
-          g.alpha[i] = av[u] - step_size * (mi / denom);
-        }
+    for (int u = 0; u < FQ_U; ++u) {
+      const int e = e0 + u * TPB;
+      if (e < total) {
+        const int64_t i = base + e;
+        const float gv = pow2 ? tv[u] * inv : tv[u] / g.sqrt_n;          // what nq_fwht stores
+        const float gr = ada_bwd_elem(xv[u], gv, av[u], dl[u], zq[u], g.qmax, rw, sc.reg_b);
+        adam_elem(gr, mv[u], vv[u], av[u], sc.step_size, beta1, beta2, eps, sc.bc2_sqrt);
+        g.m[i] = mv[u];
+        g.v[i] = vv[u];
+        g.alpha[i] = av[u];
       }
     }
   }
 }
 
-__global__ __launch_bounds__(TPB) void fwht_adaround_adam_multi_kernel(FqMulti t, float reg_b, float step_size, float beta1,
-                                                                       float beta2, float eps, float bc2_sqrt,
+__global__ __launch_bounds__(TPB) void fwht_adaround_adam_multi_kernel(NqSegTable<FqSeg> t, float reg_b, float step_size,
+                                                                       float beta1, float beta2, float eps, float bc2_sqrt,
                                                                        const float* __restrict__ dyn) {
   __shared__ float lds[LDS_FLOATS];
-  float gate = 1.f;
-  if (dyn) {   // per-step scalars from device memory (graph replays): {reg_b, regulariser gate, lr/(1-beta1^t), sqrt(1-beta2^t)}
-    reg_b = dyn[0];
-    gate = dyn[1];
-    step_size = dyn[2];
-    bc2_sqrt = dyn[3];
-  }
-  int k = 0;
-  while (k + 1 < t.nseg && (int)blockIdx.x >= t.blk0[k + 1]) ++k;
-  const FqSeg& g = t.s[k];
-  const int blk = (int)blockIdx.x - t.blk0[k];
-  const float rw = dyn ? g.reg_weight * gate : g.reg_weight;   // gate is exactly 0 or 1
+  const StepScalars sc(dyn, reg_b, step_size, bc2_sqrt);
+  int blk;
+  const FqSeg& g = t.s[t.find((int)blockIdx.x, blk)];
+  const float rw = sc.reg_weight(g.reg_weight);
   if (g.n > 0) {
-    fwht_ada_adam_tile(lds, blk, g, reg_b, rw, step_size, beta1, beta2, eps, bc2_sqrt);
+    fwht_ada_adam_tile(lds, blk, g, sc, rw, beta1, beta2, eps);
     return;
   }
   const int64_t total = g.outer;
@@ -357,45 +278,27 @@ __global__ __launch_bounds__(TPB) void fwht_adaround_adam_multi_kernel(FqMulti t
   for (int u = 0; u < 4; ++u) {
     const int64_t i = (int64_t)blk * (TPB * 4) + u * TPB + threadIdx.x;
     if (i < total) {
-      const float gr = ada_bwd_elem(g.x[i], g.gy[i], g.alpha[i], g.delta[0], g.zp[0], g.qmax, rw, reg_b);
-      float mi = g.m[i], vi = g.v[i];
-      mi = mi + (1.f - beta1) * (gr - mi);
-      vi = vi * beta2 + (1.f - beta2) * (gr * gr);
-      const float denom = sqrtf(vi) / bc2_sqrt + eps;
+      const float gr = ada_bwd_elem(g.x[i], g.gy[i], g.alpha[i], g.delta[0], g.zp[0], g.qmax, rw, sc.reg_b);
+      float mi = g.m[i], vi = g.v[i], ai = g.alpha[i];
+      adam_elem(gr, mi, vi, ai, sc.step_size, beta1, beta2, eps, sc.bc2_sqrt);
       g.m[i] = mi;
       g.v[i] = vi;
-      g.alpha[i] = g.alpha[i] - step_size * (mi / denom);
+      g.alpha[i] = ai;
     }
   }
 }
 
-__global__ __launch_bounds__(TPB) void fwht_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t outer,
-                                                   int n, int log2n, int inner, int n_in, int n_out, int OPB,
-                                                   float sqrt_n) {
+__global__ __launch_bounds__(TPB) void fwht_kernel(FwSeg g) {
   __shared__ float lds[LDS_FLOATS];
-  fwht_block(lds, (int)blockIdx.x, x, y, outer, n, log2n, inner, n_in, n_out, OPB, sqrt_n);
+  fwht_block(lds, (int)blockIdx.x, g);
 }
 
 // several tensors in ONE launch (all layers of a decoder: the per-layer launches are 10 us each for ~1 us of traffic)
-constexpr int FW_MAXSEG = 16;
-struct FwSeg {
-  const float* x;
-  float* y;
-  int64_t outer;
-  int n, log2n, inner, n_in, n_out, OPB;
-  float sqrt_n;
-};
-struct FwMulti {
-  FwSeg s[FW_MAXSEG];
-  int blk0[FW_MAXSEG + 1];
-  int nseg;
-};
-__global__ __launch_bounds__(TPB) void fwht_multi_kernel(FwMulti t) {
+__global__ __launch_bounds__(TPB) void fwht_multi_kernel(NqSegTable<FwSeg> t) {
   __shared__ float lds[LDS_FLOATS];
-  int k = 0;
-  while (k + 1 < t.nseg && (int)blockIdx.x >= t.blk0[k + 1]) ++k;
-  const FwSeg& g = t.s[k];
-  fwht_block(lds, (int)blockIdx.x - t.blk0[k], g.x, g.y, g.outer, g.n, g.log2n, g.inner, g.n_in, g.n_out, g.OPB, g.sqrt_n);
+  int blk;
+  const int k = t.find((int)blockIdx.x, blk);
+  fwht_block(lds, blk, t.s[k]);
 }
 
 // Fallback for rows too long for the tile above (n*inner > 8192): TC arbitrary columns per workgroup, gathered.
@@ -429,78 +332,36 @@ __global__ __launch_bounds__(TPB) void fwht_cols_kernel(const float* __restrict_
   }
 }
 
-}  // namespace
-
-extern "C" int nq_fwht(const float* x, float* y, int64_t outer, int n, int64_t inner, int n_in, int n_out,
-                       nq_stream_t stream) {
-  if (!x || !y || x == y || outer <= 0 || inner <= 0 || n <= 0 || (n & (n - 1)) != 0) return NQ_ERR_INVALID;
-  if (n_in <= 0 || n_in > n || n_out <= 0 || n_out > n) return NQ_ERR_INVALID;
-  if (n > 1024) return NQ_ERR_UNSUPPORTED;
-  int log2n = 0;
-  while ((1 << log2n) < n) ++log2n;
-  if ((int64_t)n * inner > TILE) {   // one outer row does not fit the LDS tile: column-gather variant
-    int TC = TILE / n;
-    if (TC > 32) TC = 32;
-    int64_t ncols = outer * inner;
-    int64_t blocks = (ncols + TC - 1) / TC;
-    if (blocks > 0x7fffffffLL) return NQ_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(fwht_cols_kernel, dim3((unsigned)blocks), dim3(TPB), 0, nq_s(stream), x, y, ncols, n, log2n, inner,
-                       n_in, n_out, TC, sqrtf((float)n));
-    return nq_launch_status();
-  }
-  int OPB = (int)(TILE / ((int64_t)n * inner));   // outer rows per workgroup
-  const int cap = (int)((NQ_FWHT_COLS + inner - 1) / inner); // ~32 columns per workgroup keeps the grid large
-  if (OPB > cap) OPB = cap;
-  if (OPB < 1) OPB = 1;
-  int64_t blocks = (outer + OPB - 1) / OPB;
-  if (blocks > 0x7fffffffLL) return NQ_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(fwht_kernel, dim3((unsigned)blocks), dim3(TPB), 0, nq_s(stream), x, y, outer, n, log2n, (int)inner, n_in,
-                     n_out, OPB, sqrtf((float)n));
-  return nq_launch_status();
+// log2 n and the outer rows per workgroup of the tile kernels; OPB = 0: one outer row does not fit the LDS tile
+struct FwhtPlan {
+  int log2n, OPB;
+};
+FwhtPlan fwht_plan(int n, int64_t inner) {
+  FwhtPlan p{0, 0};
+  while ((1 << p.log2n) < n) ++p.log2n;
+  if ((int64_t)n * inner > TILE) return p;
+  p.OPB = (int)(TILE / ((int64_t)n * inner));
+  const int cap = (int)((NQ_FWHT_COLS + inner - 1) / inner);   // ~16 columns per workgroup keeps the grid large
+  if (p.OPB > cap) p.OPB = cap;
+  return p;
 }
 
-extern "C" int nq_fwht_multi(const nq_fwht_seg* segs, int nseg, nq_stream_t stream) {
-  if (!segs || nseg <= 0) return NQ_ERR_INVALID;
-  FwMulti t;
-  t.nseg = 0;
-  int blocks = 0;
-  auto flush = [&]() {
-    if (t.nseg == 0) return;
-    t.blk0[t.nseg] = blocks;
-    hipLaunchKernelGGL(fwht_multi_kernel, dim3((unsigned)blocks), dim3(TPB), 0, nq_s(stream), t);
-    t.nseg = 0;
-    blocks = 0;
-  };
-  for (int i = 0; i < nseg; ++i) {
-    const nq_fwht_seg& h = segs[i];
-    if (!h.x || !h.y || h.x == h.y || h.outer <= 0 || h.inner <= 0 || h.n <= 0 || (h.n & (h.n - 1)) != 0) return NQ_ERR_INVALID;
-    if (h.n_in <= 0 || h.n_in > h.n || h.n_out <= 0 || h.n_out > h.n) return NQ_ERR_INVALID;
-    if (h.n > 1024) return NQ_ERR_UNSUPPORTED;
-    if ((int64_t)h.n * h.inner > TILE) {   // long rows: the single-tensor column-gather variant
-      int rc = nq_fwht(h.x, h.y, h.outer, h.n, h.inner, h.n_in, h.n_out, stream);
-      if (rc != NQ_OK) return rc;
-      continue;
-    }
-    int log2n = 0;
-    while ((1 << log2n) < h.n) ++log2n;
-    int OPB = (int)(TILE / ((int64_t)h.n * h.inner));
-    const int cap = (int)((NQ_FWHT_COLS + h.inner - 1) / h.inner);
-    if (OPB > cap) OPB = cap;
-    if (OPB < 1) OPB = 1;
-    const int64_t nb = (h.outer + OPB - 1) / OPB;
-    if (nb + blocks > 0x7fffffffLL) return NQ_ERR_UNSUPPORTED;
-    if (t.nseg == FW_MAXSEG) flush();
-    t.s[t.nseg] = FwSeg{h.x, h.y, h.outer, h.n, log2n, (int)h.inner, h.n_in, h.n_out, OPB, sqrtf((float)h.n)};
-    t.blk0[t.nseg] = blocks;
-    blocks += (int)nb;
-    ++t.nseg;
-  }
-  flush();
-  return nq_launch_status();
+int fwht_check(const nq_fwht_seg& h) {
+  if (!h.x || !h.y || h.x == h.y || h.outer <= 0 || h.inner <= 0 || h.n <= 0 || (h.n & (h.n - 1)) != 0) return NQ_ERR_INVALID;
+  if (h.n_in <= 0 || h.n_in > h.n || h.n_out <= 0 || h.n_out > h.n) return NQ_ERR_INVALID;
+  if (h.n > 1024) return NQ_ERR_UNSUPPORTED;
+  return NQ_OK;
 }
 
-// One tensor of the fused launches (include/nq_hip.h: nq_fq_fwht_seg) -> device segment; 0 on success
-static int fq_fill(FqSeg& d, const nq_fq_fwht_seg& h, bool bwd, int* blocks) {
+// a checked tensor with a tile plan -> device segment; its workgroups or NQ_ERR_*
+int64_t fw_fill(const nq_fwht_seg& h, const FwhtPlan& p, FwSeg& d) {
+  d = FwSeg{h.x, h.y, h.outer, h.n, p.log2n, (int)h.inner, h.n_in, h.n_out, p.OPB, sqrtf((float)h.n)};
+  const int64_t nb = (h.outer + p.OPB - 1) / p.OPB;
+  return nb > 0x7fffffffLL ? NQ_ERR_UNSUPPORTED : nb;
+}
+
+// One tensor of the fused launches (include/nq_hip.h: nq_fq_fwht_seg) -> device segment; its workgroups or NQ_ERR_*
+int64_t fq_fill(const nq_fq_fwht_seg& h, bool bwd, FqSeg& d) {
   if (!h.x || !h.alpha || !h.delta || !h.zp || h.outer <= 0 || h.inner <= 0 || h.n_levels < 2) return NQ_ERR_INVALID;
   if (bwd ? (!h.gy || !h.m || !h.v) : !h.y) return NQ_ERR_INVALID;
   d.x = h.x; d.alpha = h.alpha; d.delta = h.delta; d.zp = h.zp; d.m = h.m; d.v = h.v; d.gy = h.gy; d.y = h.y;
@@ -509,58 +370,70 @@ static int fq_fill(FqSeg& d, const nq_fq_fwht_seg& h, bool bwd, int* blocks) {
     d.n = 0; d.log2n = 0; d.inner = 1; d.c_in = 0; d.OPB = 0; d.sqrt_n = 1.f;
     d.outer = h.outer * h.inner;
     if (d.per_row) return NQ_ERR_UNSUPPORTED;
-    *blocks = (int)((d.outer + TPB * 4 - 1) / (TPB * 4));
-    return NQ_OK;
+    return (d.outer + TPB * 4 - 1) / (TPB * 4);
   }
   if (h.n < 0 || (h.n & (h.n - 1)) != 0 || h.c_in <= 0 || h.c_in > h.n) return NQ_ERR_INVALID;
-  if (h.n > 1024 || (int64_t)h.n * h.inner > TILE) return NQ_ERR_UNSUPPORTED;   // (longer rows: the unfused launches)
-  int log2n = 0;
-  while ((1 << log2n) < h.n) ++log2n;
-  int OPB = (int)(TILE / ((int64_t)h.n * h.inner));
-  const int cap = (int)((NQ_FWHT_COLS + h.inner - 1) / h.inner);
-  if (OPB > cap) OPB = cap;
-  if (OPB < 1) OPB = 1;
-  d.outer = h.outer; d.n = h.n; d.log2n = log2n; d.inner = (int)h.inner; d.c_in = h.c_in; d.OPB = OPB; d.sqrt_n = sqrtf((float)h.n);
-  const int64_t nb = (h.outer + OPB - 1) / OPB;
-  if (nb > 0x3fffffffLL) return NQ_ERR_UNSUPPORTED;
-  *blocks = (int)nb;
-  return NQ_OK;
+  const FwhtPlan p = fwht_plan(h.n, h.inner);
+  if (h.n > 1024 || !p.OPB) return NQ_ERR_UNSUPPORTED;   // (longer rows: the unfused launches)
+  d.outer = h.outer; d.n = h.n; d.log2n = p.log2n; d.inner = (int)h.inner; d.c_in = h.c_in; d.OPB = p.OPB; d.sqrt_n = sqrtf((float)h.n);
+  const int64_t nb = (h.outer + p.OPB - 1) / p.OPB;
+  return nb > 0x3fffffffLL ? NQ_ERR_UNSUPPORTED : nb;
+}
+
+}  // namespace
+
+extern "C" int nq_fwht(const float* x, float* y, int64_t outer, int n, int64_t inner, int n_in, int n_out,
+                       nq_stream_t stream) {
+  const nq_fwht_seg h{x, y, outer, inner, n, n_in, n_out};
+  if (int rc = fwht_check(h)) return rc;
+  const FwhtPlan p = fwht_plan(n, inner);
+  if (!p.OPB) {   // column-gather variant
+    int TC = TILE / n;
+    if (TC > 32) TC = 32;
+    int64_t ncols = outer * inner;
+    int64_t blocks = (ncols + TC - 1) / TC;
+    if (blocks > 0x7fffffffLL) return NQ_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(fwht_cols_kernel, dim3((unsigned)blocks), dim3(TPB), 0, nq_s(stream), x, y, ncols, n, p.log2n, inner,
+                       n_in, n_out, TC, sqrtf((float)n));
+    return nq_launch_status();
+  }
+  FwSeg d;
+  const int64_t blocks = fw_fill(h, p, d);
+  if (blocks < 0) return (int)blocks;
+  hipLaunchKernelGGL(fwht_kernel, dim3((unsigned)blocks), dim3(TPB), 0, nq_s(stream), d);
+  return nq_launch_status();
+}
+
+extern "C" int nq_fwht_multi(const nq_fwht_seg* segs, int nseg, nq_stream_t stream) {
+  return NqSegTable<FwSeg>::launch_all(
+      segs, nseg,
+      [&](int i, FwSeg& d) -> int64_t {
+        const nq_fwht_seg& h = segs[i];
+        if (int rc = fwht_check(h)) return rc;
+        const FwhtPlan p = fwht_plan(h.n, h.inner);
+        // long rows: the single-tensor column-gather launch, and (NQ_OK) nothing for the table
+        if (!p.OPB) return nq_fwht(h.x, h.y, h.outer, h.n, h.inner, h.n_in, h.n_out, stream);
+        return fw_fill(h, p, d);
+      },
+      [&](const NqSegTable<FwSeg>& t, unsigned blocks) {
+        hipLaunchKernelGGL(fwht_multi_kernel, dim3(blocks), dim3(TPB), 0, nq_s(stream), t);
+      });
 }
 
 extern "C" int nq_adaround_fwht_multi(const nq_fq_fwht_seg* segs, int nseg, nq_stream_t stream) {
-  if (!segs || nseg <= 0) return NQ_ERR_INVALID;
-  for (int base = 0; base < nseg; base += FW_MAXSEG_FQ) {
-    FqMulti t;
-    t.nseg = (nseg - base < FW_MAXSEG_FQ) ? nseg - base : FW_MAXSEG_FQ;
-    int blocks = 0;
-    for (int i = 0; i < t.nseg; ++i) {
-      int nb = 0;
-      if (int rc = fq_fill(t.s[i], segs[base + i], false, &nb)) return rc;
-      t.blk0[i] = blocks;
-      blocks += nb;
-    }
-    t.blk0[t.nseg] = blocks;
-    hipLaunchKernelGGL(adaround_fwht_multi_kernel, dim3((unsigned)blocks), dim3(TPB), 0, nq_s(stream), t);
-  }
-  return nq_launch_status();
+  return NqSegTable<FqSeg>::launch_all(
+      segs, nseg, [&](int i, FqSeg& d) { return fq_fill(segs[i], false, d); },
+      [&](const NqSegTable<FqSeg>& t, unsigned blocks) {
+        hipLaunchKernelGGL(adaround_fwht_multi_kernel, dim3(blocks), dim3(TPB), 0, nq_s(stream), t);
+      });
 }
 
 extern "C" int nq_fwht_adaround_adam_multi(const nq_fq_fwht_seg* segs, int nseg, float reg_b, float step_size, float beta1,
                                            float beta2, float eps, float bc2_sqrt, const float* dyn, nq_stream_t stream) {
-  if (!segs || nseg <= 0) return NQ_ERR_INVALID;
-  for (int base = 0; base < nseg; base += FW_MAXSEG_FQ) {
-    FqMulti t;
-    t.nseg = (nseg - base < FW_MAXSEG_FQ) ? nseg - base : FW_MAXSEG_FQ;
-    int blocks = 0;
-    for (int i = 0; i < t.nseg; ++i) {
-      int nb = 0;
-      if (int rc = fq_fill(t.s[i], segs[base + i], true, &nb)) return rc;
-      t.blk0[i] = blocks;
-      blocks += nb;
-    }
-    t.blk0[t.nseg] = blocks;
-    hipLaunchKernelGGL(fwht_adaround_adam_multi_kernel, dim3((unsigned)blocks), dim3(TPB), 0, nq_s(stream), t, reg_b, step_size,
-                       beta1, beta2, eps, bc2_sqrt, dyn);
-  }
-  return nq_launch_status();
+  return NqSegTable<FqSeg>::launch_all(
+      segs, nseg, [&](int i, FqSeg& d) { return fq_fill(segs[i], true, d); },
+      [&](const NqSegTable<FqSeg>& t, unsigned blocks) {
+        hipLaunchKernelGGL(fwht_adaround_adam_multi_kernel, dim3(blocks), dim3(TPB), 0, nq_s(stream), t, reg_b, step_size, beta1,
+                           beta2, eps, bc2_sqrt, dyn);
+      });
 }

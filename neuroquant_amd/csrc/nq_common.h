@@ -87,6 +87,40 @@ __device__ __forceinline__ float nq_split_word_value(unsigned w) {
 // conv3.hip: 1 / 12 / 14 = 1 / 2 / 4 rows per segment); the one rule behind nq_conv_wgrad3_split_io and the launch
 static inline bool nq_wgrad3_pc_takes_split(int pc) { return pc == 1 || pc == 12 || pc == 14; }
 
+// ---- one fp32 conv operand of the multi-tensor weight-layout launches (conv.hip; conv3.hip runs them behind its own) ----
+struct NqWLSeg {
+  const float* w;
+  float* wt;
+  int Cout, Cin, KK, krows, ld, bwd;
+};
+// element i of the operand: forward wt[k][co] = w[co][k]; data gradient wt[(co*KK + tap')][ci] = w[co][ci][KK-1-tap']
+__device__ __forceinline__ void nq_wl_elem(const NqWLSeg& g, int64_t i) {
+  if (i >= (int64_t)g.krows * g.ld) return;
+  const int row = (int)(i / g.ld), col = (int)(i - (int64_t)row * g.ld);
+  float v = 0.f;
+  if (g.bwd) {
+    const int co = row / g.KK, tap = row - co * g.KK;
+    if (co < g.Cout && col < g.Cin) v = g.w[((int64_t)co * g.Cin + col) * g.KK + (g.KK - 1 - tap)];
+  } else {
+    if (col < g.Cout && row < g.Cin * g.KK) v = g.w[(int64_t)col * (g.Cin * g.KK) + row];
+  }
+  g.wt[i] = v;
+}
+// Table segment i of a layer list: layer i / 2, its forward (even i) or data-gradient (odd i) operand.  Workgroups of 256
+// elements, 0 where the caller wants no such operand, or NQ_ERR_INVALID.
+static inline int64_t nq_wl_fill(const nq_wl_seg* segs, int i, NqWLSeg& d) {
+  const nq_wl_seg& h = segs[i / 2];
+  const int bwd = i & 1;
+  if (!h.w || h.Cout <= 0 || h.Cin <= 0 || h.k <= 0) return NQ_ERR_INVALID;
+  const int KK = h.k * h.k;
+  float* wt = bwd ? h.wt_bwd : h.wt_fwd;
+  if (!wt) return 0;
+  const int krows = bwd ? h.krows_bwd : h.krows_fwd, ld = bwd ? h.ld_bwd : h.ld_fwd;
+  if (bwd ? (krows < h.Cout * KK || ld < h.Cin) : (krows < h.Cin * KK || ld < h.Cout)) return NQ_ERR_INVALID;
+  d = NqWLSeg{h.w, wt, h.Cout, h.Cin, KK, krows, ld, bwd};
+  return ((int64_t)krows * ld + 255) / 256;
+}
+
 // ---- wave / block reductions (wave = 64 lanes) ----
 __device__ __forceinline__ float nq_wave_sum(float v) {
 #pragma unroll

@@ -36,6 +36,8 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     lib = _lib.lib()
     n = None
     assert lib.nq_uaq_forward(n, n, n, n, 4, 4, 1, 16, n) == -1
+    p16 = ctypes.c_void_p(16)
+    assert lib.nq_adaround_forward(p16, p16, p16, p16, p16, n, 1, 2 ** 31, 0, 16, 1, n) == -1     # a row past the int the table holds
     assert lib.nq_fwht(ctypes.c_void_p(16), ctypes.c_void_p(32), 1, 12, 1, 12, 12, n) == -1      # not a power of two
     assert lib.nq_fwht(ctypes.c_void_p(16), ctypes.c_void_p(32), 1, 2048, 1, 8, 8, n) == -2      # too long
     assert lib.nq_conv_forward(ctypes.c_void_p(16), ctypes.c_void_p(16), n, ctypes.c_void_p(16), n, n, 1, 4, 8, 8, 4, 7, 196,

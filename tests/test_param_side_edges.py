@@ -119,47 +119,92 @@ def placed(tensors, mode, which):
 
 
 # ================================================================================================ single-tensor quantisers
+@pytest.fixture(scope="module")
+def single():
+    cache = {}
+
+    def get(shape, per_row, nb):
+        key = (shape, per_row, nb)
+        if key not in cache:
+            cache[key] = R.single_case(*shape, per_row, nb)
+        return cache[key]
+
+    return get
+
+
 @pytest.mark.parametrize("nb", R.SINGLE_BITS)
 @pytest.mark.parametrize("per_row", (True, False), ids=("per_row", "scalar"))
 @pytest.mark.parametrize("shape", R.SINGLE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
-def test_single_tensor_quantisers(ops, shape, per_row, nb):
+def test_single_tensor_quantisers(ops, single, shape, per_row, nb):
+    """every tensor in its own allocation (the cases and ids this test has always had; the checks: _single_tensor_quantisers)"""
+    _single_tensor_quantisers(ops, single, shape, per_row, nb, "own")
+
+
+@pytest.mark.parametrize("place", (1, 2, 3), ids=lambda p: f"at{p}")
+@pytest.mark.parametrize("nb", R.SINGLE_BITS)
+@pytest.mark.parametrize("per_row", (True, False), ids=("per_row", "scalar"))
+@pytest.mark.parametrize("shape", R.SINGLE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_single_tensor_quantisers_in_an_arena(ops, single, shape, per_row, nb, place):
+    """the placement parameter of test_single_tensor_quantisers: 1, 2, 3 floats past a 16-byte boundary"""
+    _single_tensor_quantisers(ops, single, shape, per_row, nb, place)
+
+
+def _single_tensor_quantisers(ops, single, shape, per_row, nb, place):
     """scale_init / uaq_fwd / uaq_bwd / adaround_alpha_init / adaround_fwd / adaround_bwd of quant.hip at row lengths on both
-    sides of one reduction pass (256) and of one block per row (1024: bpr > 1 from 1025 on), per-row and scalar scale."""
-    c = R.single_case(*shape, per_row, nb)
-    nl, tag = c["nl"], f"{shape} per_row={per_row} bits={nb}"
-    x, gy = G(c["x"]), G(c["gy"])
+    sides of one reduction pass (256) and of one block of 1024 elements, per-row and scalar scale.  The single-tensor entries
+    are one-segment launches of the multi-tensor kernels: `place` puts x, gy, alpha and the outputs passed through out= each in
+    its own allocation (16-byte accesses, the row lookup across a thread's four elements) or 1, 2, 3 floats past a 16-byte
+    boundary of one arena (the element-by-element branch); want_dx / want_xq run the two instantiations only they launch."""
+    c = single(shape, per_row, nb)
+    nl, tag = c["nl"], f"{shape} per_row={per_row} bits={nb} place={place}"
+    x, gy, alpha = G(c["x"]), G(c["gy"]), G(c["alpha"])
+    outs = [None] * 4
+    if place != "own":
+        arena = Arena(7 * x.numel(), 7)
+        x, gy, alpha = (arena.put(t, place) for t in (x, gy, alpha))
+        outs = [arena.put(torch.full_like(x, -77.0), place) for _ in range(4)]
     # ---- UAQ
     d0, z0 = ops.scale_init_max(x, nl, per_row)
     exact(d0, c["d0"], "scale_init delta " + tag)
     exact(z0, c["z0"], "scale_init zp " + tag)
     d0, z0 = G(c["d0"]), G(c["z0"])
-    exact(ops.uaq_forward(x, d0, z0, nl), O.uaq_fake_quant(c["x"], c["d0"], c["z0"], nl), "uaq_forward " + tag)
+    exact(ops.uaq_forward(x, d0, z0, nl, out=outs[0]), O.uaq_fake_quant(c["x"], c["d0"], c["z0"], nl), "uaq_forward " + tag)
     dd, dx = ops.uaq_backward(x, gy, d0, z0, nl, want_dx=True)
     t = R.uaq_ddelta_terms(c["x"], c["gy"], c["d0"], c["z0"], nl).double()
     dims = (1, 2, 3) if per_row else (0, 1, 2, 3)
     assert dd.shape == d0.shape
     sum_close(dd, t.sum(dims), t.abs().sum(dims), "uaq_backward d(delta) " + tag)
     exact(dx, R.uaq_dx(c["x"], c["gy"], c["d0"], c["z0"], nl), "uaq_backward dx " + tag)
+    exact(ops.uaq_backward(x, gy, d0, z0, nl), dd, "uaq_backward without dx " + tag)      # the other instantiation: same sums
     # ---- AdaRound init
     d, z, a0 = ops.adaround_init(x, d0, z0)
     exact(d, c["d"], "adaround_init delta " + tag)
     exact(z, c["z"], "adaround_init zp " + tag)
     within(a0, c["a0"], R.ALPHA0_RTOL * c["a0"].abs() + R.ALPHA0_ATOL, "alpha0 " + tag)
     # ---- AdaRound forward / backward
-    d, z, alpha = G(c["d"]), G(c["z"]), G(c["alpha"])
-    yh, xqh = ops.adaround_forward(x, alpha, d, z, nl, False, want_xq=True)
+    d, z = G(c["d"]), G(c["z"])
+    yh, xqh = ops.adaround_forward(x, alpha, d, z, nl, False, want_xq=True, out=outs[1])
     rh, rxh = O.adaround_fake_quant(c["x"], c["alpha"], c["d"], c["z"], nl, False)
     exact(yh, rh, "hard forward " + tag)
     exact(xqh, rxh, "hard x_quant " + tag)
-    ys, xqs = ops.adaround_forward(x, alpha, d, z, nl, True, want_xq=True)
+    ys, xqs = ops.adaround_forward(x, alpha, d, z, nl, True, want_xq=True, out=outs[2])
     rs, rxs = O.adaround_fake_quant(c["x"], c["alpha"], c["d"], c["z"], nl, True)
     within(ys, rs, R.soft_bound(rs, c["d"]), "soft forward " + tag)
     within(xqs, rxs, 4e-6 * nl, "soft x_quant " + tag)
+    exact(ops.adaround_forward(x, alpha, d, z, nl, True), ys, "soft forward without x_quant " + tag)
     t1, _, bound = R.dalpha_terms(c["x"], c["gy"], c["alpha"], c["d"], c["z"], nl)
-    within(ops.adaround_backward(x, gy, alpha, d, z, nl), t1, bound, "d(alpha) " + tag)
+    within(ops.adaround_backward(x, gy, alpha, d, z, nl, out=outs[3]), t1, bound, "d(alpha) " + tag)
     rw, rb = R.SINGLE_REG
     t1, t2, bound = R.dalpha_terms(c["x"], c["gy"], c["alpha"], c["d"], c["z"], nl, rw, rb)
-    within(ops.adaround_backward(x, gy, alpha, d, z, nl, reg_weight=rw, reg_b=rb), t1 + t2, bound, "d(alpha) + regulariser " + tag)
+    within(ops.adaround_backward(x, gy, alpha, d, z, nl, reg_weight=rw, reg_b=rb, out=outs[3]), t1 + t2, bound,
+           "d(alpha) + regulariser " + tag)
+    if place != "own":      # the inputs are untouched and nothing was written between the arena's tensors
+        exact(x, c["x"], "x " + tag), exact(gy, c["gy"], "gy " + tag), exact(alpha, c["alpha"], "alpha " + tag)
+        used = torch.zeros_like(arena.buf, dtype=torch.bool)
+        for v in [x, gy, alpha] + outs:
+            off = (v.data_ptr() - arena.buf.data_ptr()) // 4
+            used[off:off + v.numel()] = True
+        assert not bool(arena.buf[~used].any()), "a write outside the tensors " + tag
 
 
 def test_uaq_backward_whole_tensor_as_one_row(ops):
@@ -254,6 +299,28 @@ def test_adaround_adam_multi_against_oracle(ops, multi, mode, variant):
         assert torch.equal(t["x"], G(c["x"])) and torch.equal(t["gy"], G(c["gys"][0])) and torch.equal(t["gy1"], G(c["gys"][1]))
 
 
+def _check_adam_step_single(ops, n, place):
+    """ops.adam_step: the one-segment launch of the multi-tensor Adam kernel, three steps, p / g / m / v each in its own
+    allocation or 1, 2, 3 floats past a 16-byte boundary"""
+    g = torch.Generator().manual_seed(70 + n)
+    p0 = torch.randn(n, generator=g)
+    grads = [torch.randn(n, generator=g) * (10.0 if k == 1 else 0.1) for k in range(3)]
+    ts = dict(p=G(p0), m=torch.zeros(n, device=DEV), v=torch.zeros(n, device=DEV), g0=G(grads[0]), g1=G(grads[1]), g2=G(grads[2]))
+    if place != "own":
+        arena = Arena(6 * n, 6)
+        ts = {k: arena.put(t, place) for k, t in ts.items()}
+    rp, rm, rv = p0.clone(), torch.zeros(n), torch.zeros(n)
+    for step in range(3):
+        ops.adam_step(ts["p"], ts[f"g{step}"], ts["m"], ts["v"], R.MULTI_LR, step + 1)
+        R.adam_step(rp, grads[step], rm, rv, R.MULTI_LR, step + 1)
+    what = f"adam_step n={n} place={place}"
+    within(ts["p"], rp, R.ADAM_RTOL * rp.abs() + R.ADAM_ATOL, what + " p")
+    within(ts["m"], rm, 2e-6 * (rm.abs() + 0.1 * sum(g_.abs() for g_ in grads)), what + " m")
+    within(ts["v"], rv, R.BETA2_DEV * rv + 1e-30, what + " v")
+    for k in range(3):
+        exact(ts[f"g{k}"], grads[k], what + " gradient untouched")
+
+
 @pytest.mark.parametrize("use_dyn", (False, True), ids=("host", "dyn"))
 @pytest.mark.parametrize("mode", ("own", "p", "g", "all"))
 def test_fused_adam_step_against_torch_restatement(ops, mode, use_dyn):
@@ -279,6 +346,9 @@ def test_fused_adam_step_against_torch_restatement(ops, mode, use_dyn):
         within(params[i], rp[i], R.ADAM_RTOL * rp[i].abs() + R.ADAM_ATOL, f"{what} p segment {i}")
         within(opt.m[i], rm[i], 2e-6 * (rm[i].abs() + 0.1 * sum(g[i].abs() for g in grads)), f"{what} m segment {i}")
         within(opt.v[i], rv[i], R.BETA2_DEV * rv[i] + 1e-30, f"{what} v segment {i}")
+    if not use_dyn:      # the single-tensor entry (no device scalars): aligned with "own", else 1, 2 or 3 floats off
+        for n in (1, 3, 1023, 1025):
+            _check_adam_step_single(ops, n, {"own": "own", "p": 1, "g": 2, "all": 3}[mode])
 
 
 @pytest.mark.parametrize("mode", ("own", "x", "gy", "all"))
