@@ -319,6 +319,24 @@ typedef struct nq_conv3_plan {
 NQ_API int nq_conv_forward3_plan(int B, int Cin, int H, int W, int Cout, int k, nq_conv3_plan* out);
 NQ_API int nq_conv_forward3(const float* x, const void* wt3, const float* bias, float* y, float* z, const float* zprev, float* ws, int B,
                      int Cin, int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream);
+/* ---- "levels" forward for decoded bit streams: integer weights, two BF16 MFMAs per product (additive to ABI v7) ----
+ * A stored weight is W[co][..] = n[co][..] * scale[co] with n = level - zero_point an INTEGER, |n| <= 255 for 2..8 bits.  bf16
+ * carries an 8-bit significand and so holds every integer up to 256 exactly: n_hi = n, n_lo = 0.  The per-channel scale commutes
+ * with the sum over K, hence
+ *     y[co] = scale[co] * sum_k n[co][k] * (x_hi[k] + x_lo[k]) + bias[co]
+ * with the products n*x_hi and n*x_lo only (the bf16x3 term a_lo*b_hi is zero, and neither the rounding of W to hi + lo nor the
+ * dropped lo*lo term exists), the scale applied once per output and the bias added after it (two roundings, not contracted).
+ *   nq_conv3_levels_supported : 1 exactly where nq_conv_forward3_plan reports kernel == NQ_CONV3_TILED, supported and nsplit == 1
+ *                               (the same single resolution of the shape; pure host function)
+ *   nq_conv_forward3_levels   : wt = the nq_weight_layout3 operand (transposed = 0) of the OIHW tensor n -- every entry must be an
+ *                               integer of magnitude <= 256, else n is NOT exact and the result is wrong --, scale (Cout);
+ *                               epilogues NQ_EPI_PLAIN / PS_GELU / TANH / PS with the outputs of nq_conv_forward3, floats in and
+ *                               out.  NQ_ERR_INVALID: a null x / wt / scale, a missing y / z, a non-positive size,
+ *                               NQ_EPI_DGRAD_GELU.  NQ_ERR_UNSUPPORTED: k outside {3,5}, a split-word bit, B > 65535, a shape
+ *                               for which nq_conv3_levels_supported is 0. */
+NQ_API int nq_conv3_levels_supported(int B, int Cin, int H, int W, int Cout, int k);
+NQ_API int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z, int B,
+                                   int Cin, int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream);
 
 /* Weight + bias gradient of the same convolution: dw (Cout,Cin,k,k), db (Cout) (db may be NULL), from x (B,Cin,H,W) and
  * dy (B,Cout,H,W).  ws: scratch of >= nq_conv_wgrad_ws_floats(...) floats.  Deterministic (fixed split-K order).

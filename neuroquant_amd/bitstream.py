@@ -323,12 +323,27 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
 class StreamDecoder:
     """Decode frames from a `.nqv` file alone.  Weights, biases and embeddings are rebuilt once at open; each layer's
     convolution operand is built once (per kernel family, the first time a batch size selects it); `decode` issues plain
-    launches only."""
+    launches only.
 
-    def __init__(self, path, device="cuda"):
+    arithmetic='exact' (default) is the live model's arithmetic, bit for bit.  arithmetic='levels'  runs the
+    layers the unsplit tiled bf16x3 kernel has on the stored integers instead: y = delta[co] * conv(x, level - zero_point) +
+    bias, two MFMAs per product, no rounding of the weights at all; every other layer takes exactly the 'exact' launch.
+    `levels_used[B]` lists the layers that took that path at batch size B (filled the first time a B is decoded),
+    `levels_ineligible` says why a layer never can."""
+
+    ARITHMETICS = ("exact", "levels")
+
+    def __init__(self, path, device="cuda", arithmetic="exact"):
+        if arithmetic not in self.ARITHMETICS:
+            raise ValueError(f"arithmetic must be one of {self.ARITHMETICS}, got {arithmetic!r}")
         if not torch.cuda.is_available():
             raise RuntimeError("neuroquant_amd needs an AMD GPU (no CPU path)")
         header, sec = read_container(path)
+        if arithmetic == "levels" and header.get("hadamard"):
+            raise ValueError(f"{path}: a Hadamard-domain file stores the levels of the TRANSFORMED weights, not the convolution's: "
+                             "arithmetic='levels' does not apply")
+        self.arithmetic, self.levels_used = arithmetic, {}
+        self.levels_ineligible = {}    # arithmetic='levels': layer -> why it can never take the path (whatever the batch size)
         self.header, self.device = header, torch.device(device)
         self.arch, self.cfg, self.frames = header["arch"], header["cfg"], int(header["frames"])
         _check_decoder_shape(self.arch, self.cfg)
@@ -350,14 +365,18 @@ class StreamDecoder:
 
         coded = coded_tensors(header, sec, what=path)   # host validation of every coded tensor, before any upload
 
-        def levels(tag, i, lay, prefix, shape, n_bits):
-            """the tensor stored as `{tag}{i}` in whichever coding the layer names, dequantised on the GPU"""
+        def levels(tag, i, lay, prefix, shape, n_bits, integers=False):
+            """the tensor stored as `{tag}{i}` in whichever coding the layer names, dequantised on the GPU.  integers: ->
+            (that tensor, n = level - zero_point, delta): the same kernel once more with a step of one, (float(level) - zp) * 1,
+            which is exact"""
             name, coding = f"{tag}{i}", lay.get(prefix + "levels_coding", "packed")
             delta, zp = up(f"{name}.delta").float(), up(f"{name}.zero_point").float()
             if coding == "packed":
                 self.level_bytes["packed"] += sec[f"{name}.levels"].nbytes
                 self.level_tensors["packed"] += 1
-                return ops.unpack_dequant(up(f"{name}.levels"), delta, zp, shape, n_bits)
+                packed = up(f"{name}.levels")
+                w = ops.unpack_dequant(packed, delta, zp, shape, n_bits)
+                return (w, ops.unpack_dequant(packed, torch.ones_like(delta), zp, shape, n_bits), delta) if integers else w
             *parts, chunk = coded[name]
             self.level_bytes["rans"] += sum(a.nbytes for a in parts)
             self.level_tensors["rans"] += 1
@@ -369,15 +388,33 @@ class StreamDecoder:
             dev = torch.from_numpy(host).to(self.device)
             freq, states, offsets, words = (dev[o:o + a.nbytes].view(torch.int16 if a.dtype.itemsize == 2 else torch.int32)
                                             for a, o in zip(parts, starts))
-            return ops.rans_decode_dequant(words, states, offsets, freq, delta, zp, shape, n_bits, chunk, trusted=True)
+            w = ops.rans_decode_dequant(words, states, offsets, freq, delta, zp, shape, n_bits, chunk, trusted=True)
+            if not integers:
+                return w
+            return w, ops.rans_decode_dequant(words, states, offsets, freq, torch.ones_like(delta), zp, shape, n_bits, chunk,
+                                              trusted=True), delta
 
         self.weights, self.biases = [], []
+        self._levels = [None] * len(header["layers"])   # per layer: (levels operand, delta per output channel) where eligible
         self.level_bytes = {"packed": 0, "rans": 0}   # bytes of the level sections this file stores, per coding (unpadded)
         self.level_tensors = {"packed": 0, "rans": 0}
         with torch.no_grad():
             for i, lay in enumerate(header["layers"]):
                 co, ci, k, k2 = lay["shape"]
-                w = levels("w", i, lay, "", (co, lay["c_in_stored"], k, k2), lay["n_bits"])
+                w = levels("w", i, lay, "", (co, lay["c_in_stored"], k, k2), lay["n_bits"], integers=arithmetic == "levels")
+                if arithmetic == "levels":
+                    w, n, delta = w
+                    # eligible: a 3 x 3 / 5 x 5 layer with integer n that bf16 holds exactly and finite steps; the reason a
+                    # layer is not stays on the decoder.  (The operand is then built without a second look at n: whatever
+                    # levels_operand still raises is a fault of this code, not a property of the file.)
+                    why = (f"kernel size {k} x {k2}" if k != k2 or k not in (3, 5) else
+                           "a step that is not finite" if not bool(torch.isfinite(delta).all()) else
+                           "level - zero_point is not an integer of magnitude <= 256" if not ops.levels_representable(n) else None)
+                    if why is None:
+                        self._levels[i] = (ops.levels_operand(n, checked=True), delta.reshape(-1).expand(co).contiguous())
+                    else:
+                        self.levels_ineligible[i] = why
+                    del n
                 if header["hadamard"]:
                     w = ops.hadamard_along_channel_weight(w, n_out=ci)
                 elif lay["c_in_stored"] != ci:
@@ -400,12 +437,21 @@ class StreamDecoder:
         self._operands = [dict() for _ in self.weights]   # per layer: 'bf16x3' / 'fp32' operand, built once
         torch.cuda.synchronize(self.device)
 
+    def _takes_levels(self, i, x):
+        """layer i runs on its integer levels for input x: eligible, bf16x3 precision, and the library offers the shape"""
+        cout, cin, k, _ = self.weights[i].shape
+        B, _, H, W = x.shape
+        return self._levels[i] is not None and ops._use3(None) and ops.conv3_levels_supported(B, cin, H, W, cout, k)
+
     def _conv(self, i, x):
         """layer i on x: the kernel family ops.conv2d_fused picks in its inference branch, on the cached operand."""
         w, b = self.weights[i], self.biases[i]
         cout, cin, k, _ = w.shape
         B, _, H, W = x.shape
         ops_ = self._operands[i]
+        if self._takes_levels(i, x):
+            lv = self._levels[i]
+            return ops.conv3_forward_levels_raw(x, lv[0], lv[1], b, cout, k, self._epi[i], self._r[i])[0]
         if ops._use3(None) and ops.conv3_supported(B, cin, H, W, cout, k):
             if "bf16x3" not in ops_:
                 ops_["bf16x3"] = ops.weight_layout3(w)
@@ -428,9 +474,13 @@ class StreamDecoder:
         if not idx or min(idx) < 0 or max(idx) >= self.frames:
             raise IndexError(f"frame indices must lie in [0, {self.frames})")
         x = self._emb[idx[0]] if len(idx) == 1 else torch.cat([self._emb[i] for i in idx])
-        x = self._conv(0, x)
-        if self.fc_hw != (1, 1):
-            x = ops._space_from_channels(x, *self.fc_hw).contiguous()
-        for i in range(1, len(self.weights)):
+        taken = None if len(idx) in self.levels_used else []    # the first decode of a batch size records its path
+        for i in range(len(self.weights)):
+            if taken is not None and self._takes_levels(i, x):
+                taken.append(i)
             x = self._conv(i, x)
+            if i == 0 and self.fc_hw != (1, 1):
+                x = ops._space_from_channels(x, *self.fc_hw).contiguous()
+        if taken is not None:
+            self.levels_used[len(idx)] = taken
         return x if out == "float" else ops.frames_to_u8(x, layout)

@@ -9,6 +9,10 @@ int nq_conv_igemm3_k3(const float*, const void*, const float*, float*, float*, c
                       int, int, int, float*, hipStream_t);
 int nq_conv_igemm3_k5(const float*, const void*, const float*, float*, float*, const float*, int, int, int, int, int, int, int,
                       int, int, int, float*, hipStream_t);
+int nq_conv_igemm3l_k3(const float*, const void*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int,
+                       hipStream_t);
+int nq_conv_igemm3l_k5(const float*, const void*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int,
+                       hipStream_t);
 int nq_conv_splitk_finish(const float*, const float*, float*, float*, const float*, int, int, int, int, int, int, int, hipStream_t);
 int nq_conv_flat3_plan(int, int, int, int, int, int, NqFlat3Plan*);
 int nq_conv3_waves_k3(int, int, int, int, int);
@@ -602,6 +606,31 @@ int nq_conv_forward3(const float* x, const void* wt3, const float* bias, float* 
                                                           rt.nsplit, rt.per_split, ws, st);
   if (rc != NQ_OK || rt.nsplit == 1) return rc;
   return nq_conv_splitk_finish(ws, bias, y, z, zprev, B, H, W, Cout, r, epilogue, rt.nsplit, st);
+}
+
+// Levels build of the tiled forward (conv_igemm3_impl.h, template parameter WX): offered exactly where the one resolution of the
+// shape gives the UNSPLIT tiled kernel to a shape this path serves -- the few-pixel and the split-K kernels have no such build.
+static inline bool levels_route_ok(const Fwd3Route& rt) { return !rt.flat && rt.supported && rt.nsplit == 1; }
+
+int nq_conv3_levels_supported(int B, int Cin, int H, int W, int Cout, int k) {
+  return shape_ok3(B, Cin, H, W, Cout, k) && levels_route_ok(route_fwd3(B, Cin, H, W, Cout, k)) ? 1 : 0;
+}
+
+int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z, int B, int Cin,
+                            int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream) {
+  const int fmt = epilogue & (NQ_EPI_X_SPLIT | NQ_EPI_Y_SPLIT);
+  epilogue &= ~(NQ_EPI_X_SPLIT | NQ_EPI_Y_SPLIT);
+  if (!x || !wt || !scale || (!y && epilogue != NQ_EPI_PS) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
+  if (epilogue < 0 || epilogue >= NQ_EPI_DGRAD_GELU) return NQ_ERR_INVALID;   // forward epilogues only
+  if ((epilogue == NQ_EPI_PS_GELU || epilogue == NQ_EPI_PS) && (!z || r <= 0 || Cout % (r * r) != 0)) return NQ_ERR_INVALID;
+  if (!(k == 3 || k == 5)) return NQ_ERR_UNSUPPORTED;
+  if (fmt) return NQ_ERR_UNSUPPORTED;        // floats in, floats out: the player passes no split words
+  if (B > 65535) return NQ_ERR_UNSUPPORTED;
+  // the one resolution of this call: the same the plan query and nq_conv3_levels_supported read
+  const Fwd3Route rt = route_fwd3(B, Cin, H, W, Cout, k);
+  if (!levels_route_ok(rt)) return NQ_ERR_UNSUPPORTED;
+  return (k == 3 ? nq_conv_igemm3l_k3 : nq_conv_igemm3l_k5)(x, wt, scale, bias, y, z, B, Cin, H, W, Cout, r, epilogue, rt.mi,
+                                                            nq_s(stream));
 }
 
 int nq_conv_wgrad3_supported(int B, int Cin, int H, int W, int Cout, int k) {

@@ -49,7 +49,10 @@ struct Conv3Args {
   const float* zprev;
   int B, Cin, H, W, Cout, r, epi, tiles_x, tiles, nchunk, co_tiles;
   int nsplit, per_split;  // split-K over channel chunks: blockIdx.z = b*nsplit + split, chunks [split*per, +per)
-  float* slab;            // [nsplit][B][Cout][H][W] raw partial sums when nsplit > 1 (nq_conv_splitk_finish adds them)
+  union {
+    float* slab;          // [nsplit][B][Cout][H][W] raw partial sums when nsplit > 1 (nq_conv_splitk_finish adds them)
+    const float* scale;   // levels build (template parameter WX; never split): the quantiser step per output channel, [Cout]
+  };
   int lds_epi;            // the launch reserved MT*1024 B of LDS: the data-gradient epilogue may transpose through it
   int y_split;            // y is written as split {hi | lo} words (nq_common.h) instead of floats; x: template parameter XS
   unsigned w_bytes;       // size of the wt3 operand (buffer resource range)
@@ -122,7 +125,12 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo
 // With the weights travelling by LDS-DMA the 48-channel tile holds 167 VGPRs and 48.5 KB of LDS: three workgroups per CU
 // (with two weight register sets it needed 264 B of scratch for that: 132 -> 202 us).
 // XS: the input x holds split {hi | lo} words (written by a producer with y_split): staging re-packs halves, no conversion.
-template <int MI, int WPE = 2, bool XS = false>
+// WX ("weights exact", the levels build of a decoded bit stream): the weight operand holds the integers n = level - zero_point,
+// |n| <= 256, which bf16 represents exactly -- the operand's lo plane is all zeros.  The k-step then issues a_hi*b_hi and
+// a_hi*b_lo only (two MFMAs per product, no LDS read of the weight lo fragment) and the epilogue multiplies the sum by
+// a.scale[co] (the quantiser step of the output channel) before the bias: y = scale * sum n * (x_hi + x_lo) + bias.
+// Everything else -- staging, the ring, the counted waits, LDS -- is the bf16x3 kernel's.  Forward, unsplit, float input only.
+template <int MI, int WPE = 2, bool XS = false, bool WX = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void conv_igemm3_kernel(Conv3Args a) {
   constexpr int MT = 16 * MI;
   constexpr int W_U4 = 2 * 4 * MT;            // 16-byte units per weight buffer: [plane][kq][MT]
@@ -432,13 +440,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       }
       }
       const u32x4* __restrict__ wb = wl0 + (g & WMASK) * WS + a_lane;
-      bf16x8 ah0 = __builtin_bit_cast(bf16x8, wb[0]), al0 = __builtin_bit_cast(bf16x8, wb[4 * MT]);
+      bf16x8 ah0 = __builtin_bit_cast(bf16x8, wb[0]), al0{};
+      if constexpr (!WX) al0 = __builtin_bit_cast(bf16x8, wb[4 * MT]);
       steps3<0, MI>([&](auto mi_c) {
         constexpr int mi = decltype(mi_c)::value;
         bf16x8 ah = ah0, al = al0;
         if constexpr (mi + 1 < MI) {  // prefetch the next channel block's fragments
           ah0 = __builtin_bit_cast(bf16x8, wb[(mi + 1) * 16]);
-          al0 = __builtin_bit_cast(bf16x8, wb[4 * MT + (mi + 1) * 16]);
+          if constexpr (!WX) al0 = __builtin_bit_cast(bf16x8, wb[4 * MT + (mi + 1) * 16]);
         }
         // product-major order: the three MFMAs that accumulate into one register are 4 issues apart (a dependent MFMA
         // issued back to back waits for its predecessor's result: the compiler otherwise chains them through a temporary)
@@ -454,8 +463,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         for (int nb = 0; nb < 4; ++nb) acc[mi][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[nb], acc[mi][nb], 0, 0, 0);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) acc[mi][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[nb], acc[mi][nb], 0, 0, 0);
+        if constexpr (!WX) {   // (WX: a_lo is zero -- the two MFMAs into one accumulator stay 4 issues apart)
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) acc[mi][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[nb], acc[mi][nb], 0, 0, 0);
+        }
         }
         if constexpr (mi == (MI - 1) / 2) {
           // publish the next weights in the MIDDLE of the MFMA block (the LDS write latency is covered by the remaining
@@ -555,7 +566,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   }
   const int Cout = a.Cout, r = a.r, rr = a.r * a.r;
   const int cob = co0 + 4 * kq;
-  if (a.nsplit > 1) {  // raw partial sums of this split; bias / activation happen in the finish kernel
+  if constexpr (WX) {
+    // levels build: the integer sums times the output channel's quantiser step, rounded once; the epilogues below add the
+    // bias to that (a second rounding: the build does not contract).  A padded channel (>= Cout) reads no scale.
+    steps3<0, MI>([&](auto mi_c) {
+      constexpr int mi = decltype(mi_c)::value;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int cc = cob + mi * 16 + reg;
+        const float sc = cc < Cout ? a.scale[cc] : 0.f;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[mi][nb][reg] *= sc;
+      }
+    });
+  }
+  if (!WX && a.nsplit > 1) {  // raw partial sums of this split; bias / activation happen in the finish kernel
     float* __restrict__ ys = a.slab + ((int64_t)split * a.B + b) * Cout * HW;
     steps3<0, MI>([&](auto mi_c) {
       constexpr int mi = decltype(mi_c)::value;
@@ -573,7 +598,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     return;
   }
   const int epi = a.epi;
-  if (epi == NQ_EPI_DGRAD_GELU && a.lds_epi && (W & 3) == 0) {
+  if (!WX && epi == NQ_EPI_DGRAD_GELU && a.lds_epi && (W & 3) == 0) {
     // Wide variant (the epilogue is bound by the NUMBER of global load/store instructions, not by bytes): every wave
     // transposes its 2 x 32 pixel x MT channel tile through its own LDS region so that a lane then owns 4 consecutive
     // pixels of one channel: ONE 16-byte load of gelu' and, for r = 2, TWO 8-byte stores (even / odd pixels go to
@@ -623,7 +648,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     }
     return;
   }
-  if (epi == NQ_EPI_DGRAD_GELU) {
+  if (!WX && epi == NQ_EPI_DGRAD_GELU) {
     // data gradient w.r.t. the pre-activation below: acc * gelu'(z) (zprev = the derivative saved by the forward
     // epilogue, same NCHW layout as this conv's output), stored un-shuffled: channel c*r*r + (y%r)*r + x%r at
     // (y/r, x/r).  Both offsets split into a per-channel base (b*Cout + c)*H*W and a per-pixel part.
@@ -800,11 +825,62 @@ int launch_igemm3(const Conv3Args& a_in, int tiles, hipStream_t st) {
   return nq_launch_status();
 }
 
+#ifdef NQ_IG3_LEVELS
+// the levels build of tile MI: same grid, same LDS, same choice between the 2- and 3-waves build as launch_igemm3
+template <int MI>
+int launch_igemm3_levels(const Conv3Args& a_in, int tiles, hipStream_t st) {
+  Conv3Args a = a_in;
+  a.lds_epi = 0;
+  const size_t lds = igemm3_lds_bytes(MI, false);
+  a.tiles = tiles;
+  if constexpr (MI <= 3) {
+    if (igemm3_waves(MI, a.nchunk, a.tail, 1, a.per_split) == 3) {   // short K loop
+      if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 3, false, true>>(lds)) return rc;
+      hipLaunchKernelGGL((conv_igemm3_kernel<MI, 3, false, true>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
+      return nq_launch_status();
+    }
+  }
+  if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 2, false, true>>(lds)) return rc;
+  hipLaunchKernelGGL((conv_igemm3_kernel<MI, 2, false, true>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
+  return nq_launch_status();
+}
+#endif
+
 }  // namespace
 
 #define NQ_CAT2(a, b) a##b
 #define NQ_CAT(a, b) NQ_CAT2(a, b)
 
+#ifdef NQ_IG3_LEVELS
+// Translation units conv_igemm3l_k{3,5}.hip: the 8 levels builds (WX) of this kernel size and nothing else.  wt3 is the
+// nq_weight_layout3 image of the integer tensor n (its lo plane is zero and never read), scale the quantiser step per output
+// channel.  Unsplit forward with float input and output only: the caller (nq_conv_forward3_levels, conv3.hip) has checked that.
+extern "C" int NQ_CAT(nq_conv_igemm3l_k, NQ_KS)(const float* x, const void* wt3, const float* scale, const float* bias, float* y,
+                                                 float* z, int B, int Cin, int H, int W, int Cout, int r, int epi, int mi_sel,
+                                                 hipStream_t st) {
+  if ((int64_t)B * Cin * H * W * 4 >= 0xFFFFFF00ll) return NQ_ERR_UNSUPPORTED;   // 32-bit buffer offsets into x
+  if (!scale || epi < 0 || epi > NQ_EPI_PS) return NQ_ERR_INVALID;
+  Conv3Args a;
+  a.x = x; a.wt3 = wt3; a.bias = bias; a.y = y; a.z = z; a.zprev = nullptr; a.scale = scale;
+  a.y_split = 0;
+  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.r = r; a.epi = epi;
+  a.tiles_x = (W + TW - 1) / TW;
+  a.nchunk = (Cin + CC - 1) / CC;
+  a.nsplit = 1; a.per_split = a.nchunk;
+  a.tail = wl3_tail_kind(Cin);
+  a.co_tiles = (Cout + 16 * mi_sel - 1) / (16 * mi_sel);
+  a.w_bytes = (unsigned)wl3_bytes(Cin, KK, a.co_tiles, 16 * mi_sel);
+  const int tiles = a.tiles_x * ((H + TH - 1) / TH);
+  switch (mi_sel) {
+    case 1: return launch_igemm3_levels<1>(a, tiles, st);
+    case 2: return launch_igemm3_levels<2>(a, tiles, st);
+    case 3: return launch_igemm3_levels<3>(a, tiles, st);
+    case 4: return launch_igemm3_levels<4>(a, tiles, st);
+    case 5: return launch_igemm3_levels<5>(a, tiles, st);
+    default: return NQ_ERR_UNSUPPORTED;
+  }
+}
+#else
 extern "C" int NQ_CAT(nq_conv_igemm3_k, NQ_KS)(const float* x, const void* wt3, const float* bias, float* y, float* z,
                                                 const float* zprev, int B, int Cin, int H, int W, int Cout, int r, int epi,
                                                 int mi_sel, int nsplit, int per_split, float* slab, hipStream_t st) {
@@ -850,3 +926,4 @@ extern "C" int NQ_CAT(nq_conv3_waves_k, NQ_KS)(int mi, int nchunk, int tail, int
 extern "C" int NQ_CAT(nq_conv3_lds_k, NQ_KS)(int mi, int epi, int nsplit) {
   return (int)igemm3_lds_bytes(mi, igemm3_wide_epi(mi, epi, nsplit));
 }
+#endif

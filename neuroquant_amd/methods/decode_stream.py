@@ -1,14 +1,16 @@
 """Player driver: decode every frame of a bit stream (`.nqv`, packed or entropy-coded levels; neuroquant_amd/bitstream.py) on the GPU.
 
     python -m neuroquant_amd.methods.decode_stream --stream model.nqv [--out DIR] [--frames DIR | --synthetic N]
-        [--batch_size B]
+        [--batch_size B] [--arithmetic exact|levels]
 
 The file is all it needs: no checkpoint, no QuantModel, no configuration.  --out writes frame%05d.png through the 8-bit
 interleaved path (ops.frames_to_u8).  --frames (sorted PNGs, centre-cropped as the calibration driver crops them) or
 --synthetic N (the calibration driver's synthetic frames; same --seed) reports PSNR and MS-SSIM (ops.frame_psnr /
 ops.ms_ssim) of the float output and of the 8-bit frames.  FPS covers decode only (ground truth and metrics excluded).
 With --batch_size 1 (the default, and what calibrate_network's evaluation uses) the float PSNR is the one that driver logged
-for 'Weight quantization w/ opt'.
+for 'Weight quantization w/ opt'.  --arithmetic levels runs the big 3 x 3 / 5 x 5 layers on the stored integer levels with two
+MFMAs per product (not bit-identical to the live model, within its float64 bounds) and names the layers that
+took that path.
 """
 import argparse
 import os
@@ -31,6 +33,8 @@ def parse_args(argv):
     p.add_argument('--synthetic', type=int, default=0, help='ground truth = N synthetic frames (calibrate_network --synthetic)')
     p.add_argument('--seed', default=903, type=int)
     p.add_argument('--batch_size', default=1, type=int)
+    p.add_argument('--arithmetic', default='exact', choices=StreamDecoder.ARITHMETICS,
+                   help="'levels': integer-level convolutions where the unsplit tiled bf16x3 kernel has the layer")
     return p.parse_args(argv)
 
 
@@ -39,7 +43,7 @@ def run(args):
     if not torch.cuda.is_available():
         raise RuntimeError('neuroquant_amd needs an AMD GPU (no CPU path)')
     t0 = time.time()
-    dec = StreamDecoder(args.stream)
+    dec = StreamDecoder(args.stream, arithmetic=args.arithmetic)
     open_s = time.time() - t0
     n, B = dec.frames, max(1, args.batch_size)
     gt = None
@@ -75,7 +79,8 @@ def run(args):
                 acc['ssim'].append(ops.ms_ssim(img, ref))
                 acc['ssim_u8'].append(ops.ms_ssim(img8, ref))
     res = dict(frames=n, batch_size=B, open_seconds=open_s, fps=n / dec_time, file_bytes=os.path.getsize(args.stream),
-               level_bytes=dec.level_bytes, level_tensors=dec.level_tensors)
+               level_bytes=dec.level_bytes, level_tensors=dec.level_tensors, arithmetic=dec.arithmetic,
+               levels_used={b: list(v) for b, v in dec.levels_used.items()})
     for k, v in acc.items():
         if v:
             res[k] = torch.cat(v).cpu().mean()
@@ -89,6 +94,9 @@ def main(argv):
         args.stream, res['file_bytes'], res['frames'], res['open_seconds'], round(res['fps'], 1), res['batch_size']))
     print('levels: rans {} bytes in {} tensors, packed {} bytes in {} tensors'.format(
         res['level_bytes']['rans'], res['level_tensors']['rans'], res['level_bytes']['packed'], res['level_tensors']['packed']))
+    if res['arithmetic'] == 'levels':
+        print('arithmetic levels: ' + '; '.join('batch {}: layers {}'.format(b, v if v else 'none')
+                                                for b, v in sorted(res['levels_used'].items())))
     if 'psnr' in res:
         fmt = lambda k, d: RoundTensor(res[k], d) if k in res else 'n/a'
         print('float: PSNR {} | MS-SSIM {}'.format(fmt('psnr', 2), fmt('ssim', 4)))

@@ -662,6 +662,48 @@ def conv3_forward_raw(x, wt3, bias, cout, k, epilogue, r, zprev=None, fmt=0):
     return y, z
 
 
+def conv3_levels_supported(B, cin, H, W, cout, k):
+    """True where conv3_forward_levels_raw serves the shape: the unsplit tiled bf16x3 kernel has it (nq_conv_forward3_plan)."""
+    return bool(_q("nq_conv3_levels_supported", B, cin, H, W, cout, k))
+
+
+def levels_representable(n):
+    """True when every entry of the float tensor n is an integer of magnitude <= 256 that bf16 holds exactly
+    (n == n.bfloat16().float()): what level - zero_point of a quantiser of up to 8 bits with an integer zero point gives.
+    Checked on the device; one synchronisation."""
+    n = _dev(n.detach(), "n")
+    return bool(((n == n.bfloat16().float()) & (n == n.round()) & (n.abs() <= 256)).all())
+
+
+def levels_operand(n, checked=False):
+    """operand of conv3_forward_levels_raw from the OIHW float tensor n = level - zero_point of a stored weight.  The kernel
+    reads the bf16 hi halves only, so n must satisfy levels_representable: ValueError otherwise (checked=True: the caller has
+    asked levels_representable already).  The bytes are weight_layout3's: the lo plane is all zeros and never read."""
+    n = _dev(n.detach(), "n")
+    if n.dim() != 4 or n.shape[2] != n.shape[3] or n.shape[2] not in (3, 5):
+        raise ValueError(f"levels_operand takes an OIHW float32 tensor with k = 3 or 5, got {tuple(n.shape)}")
+    if not checked and not levels_representable(n):
+        raise ValueError("levels_operand: every entry must be an integer of magnitude <= 256 that bf16 holds exactly "
+                         "(level - zero_point of an integer zero point)")
+    return weight_layout3(n.contiguous())
+
+
+def conv3_forward_levels_raw(x, wt, scale, bias, cout, k, epilogue, r):
+    """Levels counterpart of conv3_forward_raw: y = scale[co] * conv(x, n) + bias[co] with wt = levels_operand(n), two MFMAs
+    per product (include/nq_hip.h).  Forward epilogues only; returns (y, z) as conv3_forward_raw does."""
+    B, cin, H, W = x.shape
+    scale = _dev(scale, "scale")
+    if scale.numel() != cout or scale.dtype != torch.float32 or not scale.is_contiguous():
+        raise ValueError(f"conv3_forward_levels_raw: scale must hold one float32 per output channel ({cout}), got {tuple(scale.shape)}")
+    if epilogue == EPI_DGRAD_GELU:
+        raise ValueError("conv3_forward_levels_raw serves forward epilogues only")
+    y, z = _conv_outputs(x, cout, epilogue, r)
+    _timed(("conv_igemm3_levels", k, cin, cout, H, W, B, epilogue),
+           lambda: L.check(L.lib().nq_conv_forward3_levels(_p(x), _p(wt), _p(scale), _p(bias), _p(y), _p(z), B, cin, H, W, cout, k,
+                                                           r, epilogue, _stream()), "conv_forward3_levels"))
+    return y, z
+
+
 def conv_wgrad3_supported(B, cin, H, W, cout, k):
     return bool(_q("nq_conv_wgrad3_supported", B, cin, H, W, cout, k))
 
