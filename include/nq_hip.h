@@ -337,6 +337,24 @@ NQ_API int nq_conv_forward3(const float* x, const void* wt3, const float* bias, 
 NQ_API int nq_conv3_levels_supported(int B, int Cin, int H, int W, int Cout, int k);
 NQ_API int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z, int B,
                                    int Cin, int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream);
+/* ---- "half" forward for decoded bit streams: the same integers against HALF-PRECISION activations, one F16 MFMA per product
+ * (additive to ABI v7).  An APPROXIMATION, about ten times outside the bf16x3 bounds; opt-in.
+ *     y[co] = scale[co] * sum_k n[co][k] * f16(x[k]) + bias[co]
+ * n is exact in IEEE half as it is in bf16 (|n| <= 256 < 2048); x is rounded ONCE to half, round-to-nearest-even; fp32
+ * accumulation, scale, bias and epilogues as nq_conv_forward3_levels.
+ *   nq_weight_layout3_f16       : the operand: the byte layout, slots and size (nq_conv3_weight_bytes) of nq_weight_layout3
+ *                                 (transposed = 0) with the hi plane holding IEEE halves and an all-zero lo plane.  NQ_ERR_INVALID
+ *                                 as nq_weight_layout3.  Every entry of w must be an integer of magnitude <= 256.
+ *   nq_conv_forward3_levels_f16 : the launch; the arguments, their checks (made before any device call) and their codes are
+ *                                 nq_conv_forward3_levels', plus sat_flag, one device word (NQ_ERR_INVALID when null): a finite
+ *                                 activation of magnitude > 65504 is clamped to +-65504 instead of becoming an infinity and the
+ *                                 launch then stores 1 to *sat_flag; it never stores 0 (the caller clears the word).  NaN and
+ *                                 infinite activations pass unchanged and leave the flag alone.
+ * Eligibility is exactly nq_conv3_levels_supported: there is no second query. */
+NQ_API int nq_weight_layout3_f16(const float* w, void* wt, int Cin, int Cout, int k, nq_stream_t stream);
+NQ_API int nq_conv_forward3_levels_f16(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z,
+                                       unsigned* sat_flag, int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue,
+                                       nq_stream_t stream);
 
 /* Weight + bias gradient of the same convolution: dw (Cout,Cin,k,k), db (Cout) (db may be NULL), from x (B,Cin,H,W) and
  * dy (B,Cout,H,W).  ws: scratch of >= nq_conv_wgrad_ws_floats(...) floats.  Deterministic (fixed split-K order).

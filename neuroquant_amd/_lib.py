@@ -138,6 +138,8 @@ def _load():
     sig("nq_conv_forward3", I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P)
     sig("nq_conv3_levels_supported", I, I, I, I, I, I, I)
     sig("nq_conv_forward3_levels", I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P)
+    sig("nq_weight_layout3_f16", I, P, P, I, I, I, P)
+    sig("nq_conv_forward3_levels_f16", I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P)
     sig("nq_conv_wgrad3_supported", I, I, I, I, I, I, I)
     sig("nq_conv_wgrad3_ws_floats", L, I, I, I, I, I, I)
     sig("nq_conv_wgrad3_plan", I, I, I, I, I, I, I, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int))
@@ -193,6 +195,7 @@ EXPORTS = (
     "nq_rans_chunks", "nq_rans_decode",
     "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",
     "nq_conv3_levels_supported", "nq_conv_forward3_levels",
+    "nq_weight_layout3_f16", "nq_conv_forward3_levels_f16",
 )
 
 _lib = None

@@ -329,9 +329,15 @@ class StreamDecoder:
     layers the unsplit tiled bf16x3 kernel has on the stored integers instead: y = delta[co] * conv(x, level - zero_point) +
     bias, two MFMAs per product, no rounding of the weights at all; every other layer takes exactly the 'exact' launch.
     `levels_used[B]` lists the layers that took that path at batch size B (filled the first time a B is decoded),
-    `levels_ineligible` says why a layer never can."""
+    `levels_ineligible` says why a layer never can.
 
-    ARITHMETICS = ("exact", "levels")
+    arithmetic='half'  runs exactly those layers, with the same records and refusals, as
+    y = delta[co] * conv(f16(x), level - zero_point) + bias: the activations rounded once to IEEE half, one F16 MFMA per
+    product.  An approximation, about ten times outside the bounds the other two keep and two orders of magnitude below one
+    8-bit output step.  A finite activation beyond +-65504 is clamped and raises the decoder's one sticky flag word: `decode`
+    never synchronises for it, `saturated()` reads it (one synchronise) and returns a bool."""
+
+    ARITHMETICS = ("exact", "levels", "half")
 
     def __init__(self, path, device="cuda", arithmetic="exact"):
         if arithmetic not in self.ARITHMETICS:
@@ -339,11 +345,12 @@ class StreamDecoder:
         if not torch.cuda.is_available():
             raise RuntimeError("neuroquant_amd needs an AMD GPU (no CPU path)")
         header, sec = read_container(path)
-        if arithmetic == "levels" and header.get("hadamard"):
+        on_levels = arithmetic in ("levels", "half")
+        if on_levels and header.get("hadamard"):
             raise ValueError(f"{path}: a Hadamard-domain file stores the levels of the TRANSFORMED weights, not the convolution's: "
-                             "arithmetic='levels' does not apply")
+                             f"arithmetic={arithmetic!r} does not apply")
         self.arithmetic, self.levels_used = arithmetic, {}
-        self.levels_ineligible = {}    # arithmetic='levels': layer -> why it can never take the path (whatever the batch size)
+        self.levels_ineligible = {}    # 'levels' / 'half': layer -> why it can never take the path (whatever the batch size)
         self.header, self.device = header, torch.device(device)
         self.arch, self.cfg, self.frames = header["arch"], header["cfg"], int(header["frames"])
         _check_decoder_shape(self.arch, self.cfg)
@@ -401,8 +408,8 @@ class StreamDecoder:
         with torch.no_grad():
             for i, lay in enumerate(header["layers"]):
                 co, ci, k, k2 = lay["shape"]
-                w = levels("w", i, lay, "", (co, lay["c_in_stored"], k, k2), lay["n_bits"], integers=arithmetic == "levels")
-                if arithmetic == "levels":
+                w = levels("w", i, lay, "", (co, lay["c_in_stored"], k, k2), lay["n_bits"], integers=on_levels)
+                if on_levels:
                     w, n, delta = w
                     # eligible: a 3 x 3 / 5 x 5 layer with integer n that bf16 holds exactly and finite steps; the reason a
                     # layer is not stays on the decoder.  (The operand is then built without a second look at n: whatever
@@ -411,7 +418,8 @@ class StreamDecoder:
                            "a step that is not finite" if not bool(torch.isfinite(delta).all()) else
                            "level - zero_point is not an integer of magnitude <= 256" if not ops.levels_representable(n) else None)
                     if why is None:
-                        self._levels[i] = (ops.levels_operand(n, checked=True), delta.reshape(-1).expand(co).contiguous())
+                        self._levels[i] = (ops.levels_operand(n, checked=True, dtype="f16" if arithmetic == "half" else "bf16"),
+                                           delta.reshape(-1).expand(co).contiguous())
                     else:
                         self.levels_ineligible[i] = why
                     del n
@@ -435,6 +443,8 @@ class StreamDecoder:
             raise ValueError(f"{path}: {self.embeddings.shape[0]} embeddings for {self.frames} frames")
         self._emb = list(self.embeddings.split(1))   # per-frame views: a decode gathers without a host -> device copy
         self._operands = [dict() for _ in self.weights]   # per layer: 'bf16x3' / 'fp32' operand, built once
+        # 'half': the one sticky word every f16 launch of this decoder may raise and none clears
+        self._sat = torch.zeros(1, dtype=torch.int32, device=self.device) if arithmetic == "half" else None
         torch.cuda.synchronize(self.device)
 
     def _takes_levels(self, i, x):
@@ -451,6 +461,8 @@ class StreamDecoder:
         ops_ = self._operands[i]
         if self._takes_levels(i, x):
             lv = self._levels[i]
+            if self.arithmetic == "half":
+                return ops.conv3_forward_levels_f16_raw(x, lv[0], lv[1], b, cout, k, self._epi[i], self._r[i], self._sat)[0]
             return ops.conv3_forward_levels_raw(x, lv[0], lv[1], b, cout, k, self._epi[i], self._r[i])[0]
         if ops._use3(None) and ops.conv3_supported(B, cin, H, W, cout, k):
             if "bf16x3" not in ops_:
@@ -460,6 +472,11 @@ class StreamDecoder:
             ops_["fp32"] = ops.weight_layouts(w, False)[:2]
         wt, dims = ops_["fp32"]
         return ops.conv_forward_raw(x, wt, dims, b, cout, k, self._epi[i], self._r[i])[0]
+
+    def saturated(self):
+        """arithmetic='half': True once any launch of this decoder clamped a finite activation beyond the range of IEEE half
+        (+-65504); the frames decoded since open are then not the file's.  One synchronise.  Always False otherwise."""
+        return self._sat is not None and bool(self._sat.item())
 
     @torch.no_grad()
     def decode(self, indices, out="float", layout="chw"):

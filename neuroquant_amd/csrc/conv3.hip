@@ -13,6 +13,10 @@ int nq_conv_igemm3l_k3(const float*, const void*, const float*, const float*, fl
                        hipStream_t);
 int nq_conv_igemm3l_k5(const float*, const void*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int,
                        hipStream_t);
+int nq_conv_igemm3h_k3(const float*, const void*, const float*, const float*, float*, float*, unsigned*, int, int, int, int, int, int,
+                       int, int, hipStream_t);
+int nq_conv_igemm3h_k5(const float*, const void*, const float*, const float*, float*, float*, unsigned*, int, int, int, int, int, int,
+                       int, int, hipStream_t);
 int nq_conv_splitk_finish(const float*, const float*, float*, float*, const float*, int, int, int, int, int, int, int, hipStream_t);
 int nq_conv_flat3_plan(int, int, int, int, int, int, NqFlat3Plan*);
 int nq_conv3_waves_k3(int, int, int, int, int);
@@ -75,7 +79,8 @@ struct WL3 {
 constexpr int WL3_KKMAX = 25;
 // (KK is a template parameter: the index arithmetic -- e / (16*KK), rem / KK per loaded float, eight (channel, tap) pairs per
 // slot -- was most of the kernel's time with a run-time divisor)
-template <int KK>
+// F16 (nq_weight_layout3_f16, the half build of the tiled forward): the hi plane holds the values as IEEE halves, the lo plane zeros
+template <int KK, bool F16 = false>
 __device__ __forceinline__ void wl3_tile(const WL3& p, int c, int g16, float* __restrict__ T /* [16][16*KK (+1)] */) {
   constexpr int RS = 16 * KK + 1;   // row stride: odd -> the 16 rows of a column land in different banks
   const int tid = threadIdx.x;
@@ -126,6 +131,12 @@ __device__ __forceinline__ void wl3_tile(const WL3& p, int c, int g16, float* __
         if (tap < KK) x = p.transposed ? T[ch * RS + col * KK + (KK - 1 - tap)] : T[col * RS + ch * KK + tap];
         v[t] = x;
       }
+      if constexpr (F16) {
+        const _Float16 h0 = (_Float16)v[0], h1 = (_Float16)v[1];
+        hi[j] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+        lo[j] = 0u;
+        continue;
+      }
       __bf16 h0 = (__bf16)v[0], h1 = (__bf16)v[1];
       __bf16 l0 = (__bf16)(v[0] - (float)h0), l1 = (__bf16)(v[1] - (float)h1);
       hi[j] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
@@ -145,6 +156,13 @@ __device__ __forceinline__ void wl3_seg_tile(const WL3& p, int blk, float* T) {
 __global__ __launch_bounds__(256) void weight_layout3_kernel(WL3 p) {
   __shared__ float T[16 * (16 * WL3_KKMAX + 1)];
   wl3_seg_tile(p, (int)blockIdx.x, T);
+}
+
+__global__ __launch_bounds__(256) void weight_layout3_f16_kernel(WL3 p) {
+  __shared__ float T[16 * (16 * WL3_KKMAX + 1)];
+  const int blk = (int)blockIdx.x;
+  if (p.KK == 25) wl3_tile<25, true>(p, blk / p.co16, blk % p.co16, T);
+  else wl3_tile<9, true>(p, blk / p.co16, blk % p.co16, T);
 }
 
 // all layers' operands (forward and data-gradient) in ONE launch: the table travels as a kernel argument
@@ -510,6 +528,14 @@ int nq_weight_layout3(const float* w, void* wt3, int Cin, int Cout, int k, int t
   return nq_launch_status();
 }
 
+// Same byte layout, size and slots; the hi plane as IEEE halves, the lo plane zero (forward operand only: transposed = 0)
+int nq_weight_layout3_f16(const float* w, void* wt, int Cin, int Cout, int k, nq_stream_t stream) {
+  WL3 p;
+  if (!wl3_fill(p, w, wt, Cin, Cout, k, 0)) return NQ_ERR_INVALID;
+  hipLaunchKernelGGL(weight_layout3_f16_kernel, dim3((unsigned)(p.nchunk * p.co16)), dim3(256), 0, nq_s(stream), p);
+  return nq_launch_status();
+}
+
 // table segment of one bf16x3 operand: its workgroups or NQ_ERR_INVALID
 static int64_t wl3_seg_fill(const nq_wl3_seg& h, WL3& d) {
   return wl3_fill(d, h.w, h.wt3, h.Cin, h.Cout, h.k, h.transposed) ? d.nchunk * d.co16 : NQ_ERR_INVALID;
@@ -616,8 +642,9 @@ int nq_conv3_levels_supported(int B, int Cin, int H, int W, int Cout, int k) {
   return shape_ok3(B, Cin, H, W, Cout, k) && levels_route_ok(route_fwd3(B, Cin, H, W, Cout, k)) ? 1 : 0;
 }
 
-int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z, int B, int Cin,
-                            int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream) {
+// the argument checks of both levels launches, made before any device call: NQ_OK and the route, or the code to return
+static int levels_args(const float* x, const void* wt, const float* scale, float* y, float* z, int B, int Cin, int H, int W, int Cout,
+                       int k, int r, int& epilogue, Fwd3Route& rt) {
   const int fmt = epilogue & (NQ_EPI_X_SPLIT | NQ_EPI_Y_SPLIT);
   epilogue &= ~(NQ_EPI_X_SPLIT | NQ_EPI_Y_SPLIT);
   if (!x || !wt || !scale || (!y && epilogue != NQ_EPI_PS) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
@@ -627,9 +654,26 @@ int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, 
   if (fmt) return NQ_ERR_UNSUPPORTED;        // floats in, floats out: the player passes no split words
   if (B > 65535) return NQ_ERR_UNSUPPORTED;
   // the one resolution of this call: the same the plan query and nq_conv3_levels_supported read
-  const Fwd3Route rt = route_fwd3(B, Cin, H, W, Cout, k);
-  if (!levels_route_ok(rt)) return NQ_ERR_UNSUPPORTED;
+  rt = route_fwd3(B, Cin, H, W, Cout, k);
+  return levels_route_ok(rt) ? NQ_OK : NQ_ERR_UNSUPPORTED;
+}
+
+int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z, int B, int Cin,
+                            int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream) {
+  Fwd3Route rt;
+  if (int rc = levels_args(x, wt, scale, y, z, B, Cin, H, W, Cout, k, r, epilogue, rt)) return rc;
   return (k == 3 ? nq_conv_igemm3l_k3 : nq_conv_igemm3l_k5)(x, wt, scale, bias, y, z, B, Cin, H, W, Cout, r, epilogue, rt.mi,
+                                                            nq_s(stream));
+}
+
+// Half build (template parameter XH): the same checks, the same shapes (nq_conv3_levels_supported), and the flag word
+int nq_conv_forward3_levels_f16(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z,
+                                unsigned* sat_flag, int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue,
+                                nq_stream_t stream) {
+  if (!sat_flag) return NQ_ERR_INVALID;
+  Fwd3Route rt;
+  if (int rc = levels_args(x, wt, scale, y, z, B, Cin, H, W, Cout, k, r, epilogue, rt)) return rc;
+  return (k == 3 ? nq_conv_igemm3h_k3 : nq_conv_igemm3h_k5)(x, wt, scale, bias, y, z, sat_flag, B, Cin, H, W, Cout, r, epilogue, rt.mi,
                                                             nq_s(stream));
 }
 

@@ -39,6 +39,7 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef f32x4 f32x4_u __attribute__((aligned(4)));
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
 struct Conv3Args {
   const float* x;
@@ -46,7 +47,10 @@ struct Conv3Args {
   const float* bias;
   float* y;
   float* z;
-  const float* zprev;
+  union {
+    const float* zprev;
+    unsigned* sat;        // half build (template parameter XH; forward only, no zprev): the saturation flag word
+  };
   int B, Cin, H, W, Cout, r, epi, tiles_x, tiles, nchunk, co_tiles;
   int nsplit, per_split;  // split-K over channel chunks: blockIdx.z = b*nsplit + split, chunks [split*per, +per)
   union {
@@ -119,6 +123,24 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo
   }
 }
 
+// 8 floats -> 8 packed IEEE halves, round-to-nearest-even (the conversion follows the wave's rounding mode, which the build never
+// changes; cvt_pkrtz would truncate).  A finite value of magnitude > 65504 would round to infinity: it is clamped to +-65504 and
+// `sat` is raised; infinities and NaNs pass unchanged (65504.f = 0x477FE000: one unsigned compare selects 65504 < |v| < inf).
+__device__ __forceinline__ void half8(const float (&v)[8], u32x4& hi, bool& sat) {
+  using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
+  using f32x2 = __attribute__((ext_vector_type(2))) float;
+  float c[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const unsigned u = __builtin_bit_cast(unsigned, v[j]);
+    const bool over = (u & 0x7FFFFFFFu) - 0x477FE001u < 0x7F800000u - 0x477FE001u;
+    sat |= over;
+    c[j] = over ? __builtin_bit_cast(float, (u & 0x80000000u) | 0x477FE000u) : v[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) hi[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{c[2 * j], c[2 * j + 1]}, f16x2));
+}
+
 // WPE = waves per SIMD the register allocation aims at: 2 for the long K loops (the MFMA-bound layers: a third wave only
 // queues for the same matrix pipe), 3 for the tiles of <= 48 channels on short K loops (NeRV's last blocks: <= 30 k-steps
 // between a prologue and an epilogue of global-memory latency -- bound by latency, not by issue slots; tools/bench_nerv_tail.py).
@@ -130,8 +152,14 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo
 // a_hi*b_lo only (two MFMAs per product, no LDS read of the weight lo fragment) and the epilogue multiplies the sum by
 // a.scale[co] (the quantiser step of the output channel) before the bias: y = scale * sum n * (x_hi + x_lo) + bias.
 // Everything else -- staging, the ring, the counted waits, LDS -- is the bf16x3 kernel's.  Forward, unsplit, float input only.
-template <int MI, int WPE = 2, bool XS = false, bool WX = false>
+// XH ("activations half", only with WX; the half build): the operand's hi plane holds the same integers as IEEE halves
+// (nq_weight_layout3_f16) and the patch is converted ONCE, to halves (half8 above), into the hi plane of the patch; the lo plane
+// of the patch is neither written nor read.  One v_mfma_f32_16x16x32_f16 per product: y = scale * sum n * f16(x) + bias.  A lane
+// whose conversion clamped a value stores 1 to *a.sat behind the K loop (every writer stores the same word: no atomic).  LDS
+// size and layout, the ring and every counted wait are unchanged.
+template <int MI, int WPE = 2, bool XS = false, bool WX = false, bool XH = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void conv_igemm3_kernel(Conv3Args a) {
+  static_assert(!XH || (WX && !XS), "the half build is a levels build with float input");
   constexpr int MT = 16 * MI;
   constexpr int W_U4 = 2 * 4 * MT;            // 16-byte units per weight buffer: [plane][kq][MT]
   constexpr int WPT = (W_U4 + 255) / 256;     // per thread
@@ -212,6 +240,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   const bool x_edge = (x0 == 0) || (x0 + TW + PAD > W);   // block-uniform: some halo columns are outside the image
   f32x4 pv[8];
   u32x4 wvA[WPT], wvB[WPT];
+  bool sat = false;   // XH: this lane clamped a value
 #define NQ3_LOAD_PATCH_J(CH, J)                                                                       \
   {                                                                                                   \
     /* channels of this item's octet that exist (0 for a thread without an item / a row outside the image): the   \
@@ -238,7 +267,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       if (4 * QP == PW || 4 * it_q + e_ < PW) {                                                       \
         const float c_[8] = {pv[0][e_], pv[1][e_], pv[2][e_], pv[3][e_], pv[4][e_], pv[5][e_], pv[6][e_], pv[7][e_]}; \
         u32x4 hi_, lo_;                                                                               \
-        if constexpr (XS) {                                                                           \
+        if constexpr (XH) {                                                                           \
+          half8(c_, hi_, sat);                                                                        \
+        } else if constexpr (XS) {                                                                    \
           _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                          \
             const unsigned w0_ = __builtin_bit_cast(unsigned, c_[2 * j_]), w1_ = __builtin_bit_cast(unsigned, c_[2 * j_ + 1]); \
             hi_[j_] = __builtin_amdgcn_perm(w1_, w0_, 0x07060302u);                                   \
@@ -248,7 +279,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
           split8(c_, hi_, lo_);                                                                       \
         }                                                                                             \
         (DST)[it_oct * PP + it_r * PW + 4 * it_q + e_] = hi_;                                         \
-        (DST)[2 * PP + it_oct * PP + it_r * PW + 4 * it_q + e_] = lo_;                                \
+        if constexpr (!XH) (DST)[2 * PP + it_oct * PP + it_r * PW + 4 * it_q + e_] = lo_;             \
       }                                                                                               \
     }                                                                                                 \
   }
@@ -411,9 +442,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         for (int nb = 0; nb < 4; ++nb) {
           const int o = 2 * ((nb >> 1) * PW + (nb & 1) * 16);
           const uint2 h0 = p2[o0 + o], h1 = p2[o1 + o];
-          const uint2 l0 = p2[4 * PP + o0 + o], l1 = p2[4 * PP + o1 + o];   // lo plane: 2 * PP units of 16 bytes further
+          uint2 l0{}, l1{};
+          if constexpr (!XH) {   // lo plane: 2 * PP units of 16 bytes further
+            l0 = p2[4 * PP + o0 + o];
+            l1 = p2[4 * PP + o1 + o];
+          }
           bh[nb] = __builtin_bit_cast(bf16x8, u32x4{h0.x, h0.y, h1.x, h1.y});
-          bl[nb] = __builtin_bit_cast(bf16x8, u32x4{l0.x, l0.y, l1.x, l1.y});
+          if constexpr (!XH) bl[nb] = __builtin_bit_cast(bf16x8, u32x4{l0.x, l0.y, l1.x, l1.y});
         }
       } else {
       const u32x4* __restrict__ pbt;
@@ -436,7 +471,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       for (int nb = 0; nb < 4; ++nb) {
         const int o = (NQ_IG3_ABL == 6) ? 0 : (nb >> 1) * PW + (nb & 1) * 16;   // ablation 6: one fragment pair for all four
         bh[nb] = __builtin_bit_cast(bf16x8, pbt[o]);
-        bl[nb] = __builtin_bit_cast(bf16x8, pbt[2 * PP + o]);
+        if constexpr (!XH) bl[nb] = __builtin_bit_cast(bf16x8, pbt[2 * PP + o]);
       }
       }
       const u32x4* __restrict__ wb = wl0 + (g & WMASK) * WS + a_lane;
@@ -458,6 +493,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                         t3 = __builtin_bit_cast(u32x4, al);
             acc[mi][nb][0] += __builtin_bit_cast(float, t0[0] ^ t1[0] ^ t2[0] ^ t3[0]);
           }
+        } else if constexpr (XH) {   // one MFMA per product: the four of a channel block go to four different accumulators
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+          acc[mi][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh[nb]), acc[mi][nb], 0, 0, 0);
         } else {
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) acc[mi][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[nb], acc[mi][nb], 0, 0, 0);
@@ -544,6 +583,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   if constexpr (WDMA) {   // the pieces issued past the end of the split must not land in LDS the epilogue re-uses
     NQ3_WAIT_VM(0)
     NQ3_BARRIER_LDS()
+  }
+  if constexpr (XH) {
+    if (sat) *a.sat = 1u;
   }
 #undef NQ3_DMA_W
 #undef NQ3_DMA_PIECE
@@ -825,8 +867,13 @@ int launch_igemm3(const Conv3Args& a_in, int tiles, hipStream_t st) {
   return nq_launch_status();
 }
 
-#ifdef NQ_IG3_LEVELS
-// the levels build of tile MI: same grid, same LDS, same choice between the 2- and 3-waves build as launch_igemm3
+#if defined(NQ_IG3_LEVELS) || defined(NQ_IG3_HALF)
+#ifdef NQ_IG3_HALF
+constexpr bool LV_XH = true;    // translation units conv_igemm3h_k{3,5}.hip: the half builds (WX and XH)
+#else
+constexpr bool LV_XH = false;
+#endif
+// the levels / half build of tile MI: same grid, same LDS, same choice between the 2- and 3-waves build as launch_igemm3
 template <int MI>
 int launch_igemm3_levels(const Conv3Args& a_in, int tiles, hipStream_t st) {
   Conv3Args a = a_in;
@@ -835,13 +882,13 @@ int launch_igemm3_levels(const Conv3Args& a_in, int tiles, hipStream_t st) {
   a.tiles = tiles;
   if constexpr (MI <= 3) {
     if (igemm3_waves(MI, a.nchunk, a.tail, 1, a.per_split) == 3) {   // short K loop
-      if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 3, false, true>>(lds)) return rc;
-      hipLaunchKernelGGL((conv_igemm3_kernel<MI, 3, false, true>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
+      if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 3, false, true, LV_XH>>(lds)) return rc;
+      hipLaunchKernelGGL((conv_igemm3_kernel<MI, 3, false, true, LV_XH>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
       return nq_launch_status();
     }
   }
-  if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 2, false, true>>(lds)) return rc;
-  hipLaunchKernelGGL((conv_igemm3_kernel<MI, 2, false, true>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
+  if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 2, false, true, LV_XH>>(lds)) return rc;
+  hipLaunchKernelGGL((conv_igemm3_kernel<MI, 2, false, true, LV_XH>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
   return nq_launch_status();
 }
 #endif
@@ -851,17 +898,27 @@ int launch_igemm3_levels(const Conv3Args& a_in, int tiles, hipStream_t st) {
 #define NQ_CAT2(a, b) a##b
 #define NQ_CAT(a, b) NQ_CAT2(a, b)
 
-#ifdef NQ_IG3_LEVELS
+#if defined(NQ_IG3_LEVELS) || defined(NQ_IG3_HALF)
 // Translation units conv_igemm3l_k{3,5}.hip: the 8 levels builds (WX) of this kernel size and nothing else.  wt3 is the
 // nq_weight_layout3 image of the integer tensor n (its lo plane is zero and never read), scale the quantiser step per output
 // channel.  Unsplit forward with float input and output only: the caller (nq_conv_forward3_levels, conv3.hip) has checked that.
+// Translation units conv_igemm3h_k{3,5}.hip: the 8 half builds (WX, XH) likewise; wt3 is the nq_weight_layout3_f16 image, sat
+// the flag word (nq_conv_forward3_levels_f16).
+#ifdef NQ_IG3_HALF
+extern "C" int NQ_CAT(nq_conv_igemm3h_k, NQ_KS)(const float* x, const void* wt3, const float* scale, const float* bias, float* y,
+                                                 float* z, unsigned* sat, int B, int Cin, int H, int W, int Cout, int r, int epi,
+                                                 int mi_sel, hipStream_t st) {
+  if (!sat) return NQ_ERR_INVALID;
+#else
 extern "C" int NQ_CAT(nq_conv_igemm3l_k, NQ_KS)(const float* x, const void* wt3, const float* scale, const float* bias, float* y,
                                                  float* z, int B, int Cin, int H, int W, int Cout, int r, int epi, int mi_sel,
                                                  hipStream_t st) {
+  unsigned* const sat = nullptr;   // the slot is zprev's, which these builds compile out
+#endif
   if ((int64_t)B * Cin * H * W * 4 >= 0xFFFFFF00ll) return NQ_ERR_UNSUPPORTED;   // 32-bit buffer offsets into x
   if (!scale || epi < 0 || epi > NQ_EPI_PS) return NQ_ERR_INVALID;
   Conv3Args a;
-  a.x = x; a.wt3 = wt3; a.bias = bias; a.y = y; a.z = z; a.zprev = nullptr; a.scale = scale;
+  a.x = x; a.wt3 = wt3; a.bias = bias; a.y = y; a.z = z; a.sat = sat; a.scale = scale;
   a.y_split = 0;
   a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.r = r; a.epi = epi;
   a.tiles_x = (W + TW - 1) / TW;

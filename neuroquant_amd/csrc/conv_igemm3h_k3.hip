@@ -1,0 +1,3 @@
+#define NQ_KS 3
+#define NQ_IG3_HALF 1
+#include "conv_igemm3_impl.h"

@@ -1,7 +1,7 @@
 """Player driver: decode every frame of a bit stream (`.nqv`, packed or entropy-coded levels; neuroquant_amd/bitstream.py) on the GPU.
 
     python -m neuroquant_amd.methods.decode_stream --stream model.nqv [--out DIR] [--frames DIR | --synthetic N]
-        [--batch_size B] [--arithmetic exact|levels]
+        [--batch_size B] [--arithmetic exact|levels|half]
 
 The file is all it needs: no checkpoint, no QuantModel, no configuration.  --out writes frame%05d.png through the 8-bit
 interleaved path (ops.frames_to_u8).  --frames (sorted PNGs, centre-cropped as the calibration driver crops them) or
@@ -10,7 +10,9 @@ ops.ms_ssim) of the float output and of the 8-bit frames.  FPS covers decode onl
 With --batch_size 1 (the default, and what calibrate_network's evaluation uses) the float PSNR is the one that driver logged
 for 'Weight quantization w/ opt'.  --arithmetic levels runs the big 3 x 3 / 5 x 5 layers on the stored integer levels with two
 MFMAs per product (not bit-identical to the live model, within its float64 bounds) and names the layers that
-took that path.
+took that path.  --arithmetic half runs the same layers on half-precision activations with one MFMA per product (DESIGN.md
+§15: an approximation, about ten times outside those bounds), names them likewise, and exits non-zero if an activation left the
+range of IEEE half.
 """
 import argparse
 import os
@@ -34,7 +36,8 @@ def parse_args(argv):
     p.add_argument('--seed', default=903, type=int)
     p.add_argument('--batch_size', default=1, type=int)
     p.add_argument('--arithmetic', default='exact', choices=StreamDecoder.ARITHMETICS,
-                   help="'levels': integer-level convolutions where the unsplit tiled bf16x3 kernel has the layer")
+                   help="'levels': integer-level convolutions where the unsplit tiled bf16x3 kernel has the layer; "
+                        "'half': those layers on half-precision activations (an approximation)")
     return p.parse_args(argv)
 
 
@@ -80,6 +83,7 @@ def run(args):
                 acc['ssim_u8'].append(ops.ms_ssim(img8, ref))
     res = dict(frames=n, batch_size=B, open_seconds=open_s, fps=n / dec_time, file_bytes=os.path.getsize(args.stream),
                level_bytes=dec.level_bytes, level_tensors=dec.level_tensors, arithmetic=dec.arithmetic,
+               saturated=dec.saturated(),     # once, after the last frame
                levels_used={b: list(v) for b, v in dec.levels_used.items()})
     for k, v in acc.items():
         if v:
@@ -94,17 +98,20 @@ def main(argv):
         args.stream, res['file_bytes'], res['frames'], res['open_seconds'], round(res['fps'], 1), res['batch_size']))
     print('levels: rans {} bytes in {} tensors, packed {} bytes in {} tensors'.format(
         res['level_bytes']['rans'], res['level_tensors']['rans'], res['level_bytes']['packed'], res['level_tensors']['packed']))
-    if res['arithmetic'] == 'levels':
-        print('arithmetic levels: ' + '; '.join('batch {}: layers {}'.format(b, v if v else 'none')
-                                                for b, v in sorted(res['levels_used'].items())))
+    if res['arithmetic'] in ('levels', 'half'):
+        print('arithmetic {}: '.format(res['arithmetic']) + '; '.join('batch {}: layers {}'.format(b, v if v else 'none')
+                                                           for b, v in sorted(res['levels_used'].items())))
     if 'psnr' in res:
         fmt = lambda k, d: RoundTensor(res[k], d) if k in res else 'n/a'
         print('float: PSNR {} | MS-SSIM {}'.format(fmt('psnr', 2), fmt('ssim', 4)))
         print('8-bit: PSNR {} | MS-SSIM {}'.format(fmt('psnr_u8', 2), fmt('ssim_u8', 4)))
     if args.out:
         print('wrote {} PNGs to {}'.format(res['frames'], args.out))
+    if res['saturated']:
+        print('arithmetic half: an activation left the range of IEEE half (|x| > 65504) and was clamped: '
+              'the frames are NOT the stream\'s; decode it with --arithmetic levels or exact')
     return res
 
 
 if __name__ == '__main__':
-    main(sys.argv[1:])
+    sys.exit(1 if main(sys.argv[1:])['saturated'] else 0)

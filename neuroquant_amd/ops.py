@@ -675,32 +675,64 @@ def levels_representable(n):
     return bool(((n == n.bfloat16().float()) & (n == n.round()) & (n.abs() <= 256)).all())
 
 
-def levels_operand(n, checked=False):
-    """operand of conv3_forward_levels_raw from the OIHW float tensor n = level - zero_point of a stored weight.  The kernel
-    reads the bf16 hi halves only, so n must satisfy levels_representable: ValueError otherwise (checked=True: the caller has
-    asked levels_representable already).  The bytes are weight_layout3's: the lo plane is all zeros and never read."""
+def levels_operand(n, checked=False, dtype="bf16"):
+    """operand of conv3_forward_levels_raw (dtype='bf16') or conv3_forward_levels_f16_raw (dtype='f16') from the OIHW float tensor
+    n = level - zero_point of a stored weight.  The kernels read the hi halves only, so n must satisfy levels_representable:
+    ValueError otherwise (checked=True: the caller has asked levels_representable already).  'bf16': the bytes are
+    weight_layout3's.  'f16': the same layout and size with the integers as IEEE halves (nq_weight_layout3_f16), which hold them
+    exactly too.  Either way the lo plane is all zeros and never read."""
     n = _dev(n.detach(), "n")
+    if dtype not in ("bf16", "f16"):
+        raise ValueError(f"levels_operand: dtype must be 'bf16' or 'f16', got {dtype!r}")
     if n.dim() != 4 or n.shape[2] != n.shape[3] or n.shape[2] not in (3, 5):
         raise ValueError(f"levels_operand takes an OIHW float32 tensor with k = 3 or 5, got {tuple(n.shape)}")
     if not checked and not levels_representable(n):
         raise ValueError("levels_operand: every entry must be an integer of magnitude <= 256 that bf16 holds exactly "
                          "(level - zero_point of an integer zero point)")
-    return weight_layout3(n.contiguous())
+    if dtype == "bf16":
+        return weight_layout3(n.contiguous())
+    (sg,), (buf,), (n,) = _wl3_segs([(n.contiguous(), False)])
+    L.check(L.lib().nq_weight_layout3_f16(_p(n), _p(buf), sg.Cin, sg.Cout, sg.k, _stream()), "weight_layout3_f16")
+    return buf
+
+
+def _levels_scale(scale, cout, who):
+    scale = _dev(scale, "scale")
+    if scale.numel() != cout or scale.dtype != torch.float32 or not scale.is_contiguous():
+        raise ValueError(f"{who}: scale must hold one float32 per output channel ({cout}), got {tuple(scale.shape)}")
+    return scale
 
 
 def conv3_forward_levels_raw(x, wt, scale, bias, cout, k, epilogue, r):
     """Levels counterpart of conv3_forward_raw: y = scale[co] * conv(x, n) + bias[co] with wt = levels_operand(n), two MFMAs
     per product (include/nq_hip.h).  Forward epilogues only; returns (y, z) as conv3_forward_raw does."""
     B, cin, H, W = x.shape
-    scale = _dev(scale, "scale")
-    if scale.numel() != cout or scale.dtype != torch.float32 or not scale.is_contiguous():
-        raise ValueError(f"conv3_forward_levels_raw: scale must hold one float32 per output channel ({cout}), got {tuple(scale.shape)}")
+    scale = _levels_scale(scale, cout, "conv3_forward_levels_raw")
     if epilogue == EPI_DGRAD_GELU:
         raise ValueError("conv3_forward_levels_raw serves forward epilogues only")
     y, z = _conv_outputs(x, cout, epilogue, r)
     _timed(("conv_igemm3_levels", k, cin, cout, H, W, B, epilogue),
            lambda: L.check(L.lib().nq_conv_forward3_levels(_p(x), _p(wt), _p(scale), _p(bias), _p(y), _p(z), B, cin, H, W, cout, k,
                                                            r, epilogue, _stream()), "conv_forward3_levels"))
+    return y, z
+
+
+def conv3_forward_levels_f16_raw(x, wt, scale, bias, cout, k, epilogue, r, sat_flag):
+    """Half-precision counterpart of conv3_forward_levels_raw: y = scale[co] * conv(f16(x), n) + bias[co] with
+    wt = levels_operand(n, dtype='f16'), one F16 MFMA per product (include/nq_hip.h; an approximation).
+    sat_flag: one int32 on the device; the launch stores 1 to it when it clamped a finite |x| > 65504 and never clears it.  No
+    synchronisation here.  Serves the shapes of conv3_levels_supported."""
+    B, cin, H, W = x.shape
+    scale = _levels_scale(scale, cout, "conv3_forward_levels_f16_raw")
+    if epilogue == EPI_DGRAD_GELU:
+        raise ValueError("conv3_forward_levels_f16_raw serves forward epilogues only")
+    sat_flag = _dev_as(sat_flag, torch.int32, "sat_flag")
+    if sat_flag.numel() != 1:
+        raise ValueError("conv3_forward_levels_f16_raw: sat_flag must be one int32 on the device")
+    y, z = _conv_outputs(x, cout, epilogue, r)
+    _timed(("conv_igemm3_levels_f16", k, cin, cout, H, W, B, epilogue),
+           lambda: L.check(L.lib().nq_conv_forward3_levels_f16(_p(x), _p(wt), _p(scale), _p(bias), _p(y), _p(z), _p(sat_flag), B, cin,
+                                                               H, W, cout, k, r, epilogue, _stream()), "conv_forward3_levels_f16"))
     return y, z
 
 

@@ -6,8 +6,8 @@ neuroquant_amd/csrc/Makefile -- to show, without a GPU, that a source change lef
 
 One line per kernel: demangled name, VGPRs, SGPRs, bytes of scratch, spilled VGPRs, instruction count and the SHA-256 (first 16
 hex digits) of its disassembly with addresses and encodings removed.  Two builds agree on a kernel when their lines agree: run it on
-the objects of two checkouts and diff the outputs.  --strip-arg X drops a trailing template argument X from the printed
-names, for comparing against a build from before a defaulted template parameter was added.
+the objects of two checkouts and diff the outputs.  --strip-arg X drops every trailing template argument X from the printed
+names, for comparing against a build from before defaulted template parameters were added (give it to both builds).
 Uses llvm-objcopy, clang-offload-bundler, llvm-objdump and llvm-readelf of $ROCM_PATH/lib/llvm/bin (default /opt/rocm) and
 c++filt from the PATH."""
 import argparse
@@ -65,7 +65,7 @@ def main(argv):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("files", nargs="+")
     ap.add_argument("--match", default="", help="only kernels whose demangled name contains this")
-    ap.add_argument("--strip-arg", default=None, help="drop this trailing template argument from the names")
+    ap.add_argument("--strip-arg", default=None, help="drop every trailing occurrence of this template argument from the names")
     a = ap.parse_args(argv)
     for path in a.files:
         ks = kernels(path)
@@ -77,7 +77,7 @@ def main(argv):
             nm = nm[5:] if nm.startswith("void ") else nm
             nm = nm[:nm.rindex(">(") + 1] if ">(" in nm else nm.split("(")[0]      # without the argument list
             if a.strip_arg:
-                nm = re.sub(r",\s*" + re.escape(a.strip_arg) + r">$", ">", nm)
+                nm = re.sub(r"(,\s*" + re.escape(a.strip_arg) + r")+>$", ">", nm)
             if a.match in nm and "n" in k:
                 rows.append(f"{nm}  vgpr {k['vgpr']} sgpr {k['sgpr']} scratch {k['scratch']} spill {k['spill']} "
                             f"insts {k['n']} sha {k['sha']}")
