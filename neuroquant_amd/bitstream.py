@@ -345,7 +345,9 @@ class StreamDecoder:
         if not torch.cuda.is_available():
             raise RuntimeError("neuroquant_amd needs an AMD GPU (no CPU path)")
         header, sec = read_container(path)
-        on_levels = arithmetic in ("levels", "half")
+        # the operand dtype of the levels path (ops.levels_operand / conv3_forward_levels_raw); None: no such path ('exact')
+        self._lv_dtype = {"exact": None, "levels": "bf16", "half": "f16"}[arithmetic]
+        on_levels = self._lv_dtype is not None
         if on_levels and header.get("hadamard"):
             raise ValueError(f"{path}: a Hadamard-domain file stores the levels of the TRANSFORMED weights, not the convolution's: "
                              f"arithmetic={arithmetic!r} does not apply")
@@ -382,24 +384,23 @@ class StreamDecoder:
                 self.level_bytes["packed"] += sec[f"{name}.levels"].nbytes
                 self.level_tensors["packed"] += 1
                 packed = up(f"{name}.levels")
-                w = ops.unpack_dequant(packed, delta, zp, shape, n_bits)
-                return (w, ops.unpack_dequant(packed, torch.ones_like(delta), zp, shape, n_bits), delta) if integers else w
-            *parts, chunk = coded[name]
-            self.level_bytes["rans"] += sum(a.nbytes for a in parts)
-            self.level_tensors["rans"] += 1
-            # one host buffer, one upload: the four arrays side by side at 4-byte boundaries, viewed by type on the device
-            starts = np.cumsum([0] + [_align4(a.nbytes) for a in parts])
-            host = np.zeros(int(starts[-1]), dtype=np.uint8)
-            for a, o in zip(parts, starts):
-                host[o:o + a.nbytes] = a.view(np.uint8)
-            dev = torch.from_numpy(host).to(self.device)
-            freq, states, offsets, words = (dev[o:o + a.nbytes].view(torch.int16 if a.dtype.itemsize == 2 else torch.int32)
-                                            for a, o in zip(parts, starts))
-            w = ops.rans_decode_dequant(words, states, offsets, freq, delta, zp, shape, n_bits, chunk, trusted=True)
-            if not integers:
-                return w
-            return w, ops.rans_decode_dequant(words, states, offsets, freq, torch.ones_like(delta), zp, shape, n_bits, chunk,
-                                              trusted=True), delta
+                dequant = lambda step: ops.unpack_dequant(packed, step, zp, shape, n_bits)  # noqa: E731
+            else:
+                *parts, chunk = coded[name]
+                self.level_bytes["rans"] += sum(a.nbytes for a in parts)
+                self.level_tensors["rans"] += 1
+                # one host buffer, one upload: the four arrays side by side at 4-byte boundaries, viewed by type on the device
+                starts = np.cumsum([0] + [_align4(a.nbytes) for a in parts])
+                host = np.zeros(int(starts[-1]), dtype=np.uint8)
+                for a, o in zip(parts, starts):
+                    host[o:o + a.nbytes] = a.view(np.uint8)
+                dev = torch.from_numpy(host).to(self.device)
+                freq, states, offsets, words = (dev[o:o + a.nbytes].view(torch.int16 if a.dtype.itemsize == 2 else torch.int32)
+                                                for a, o in zip(parts, starts))
+                dequant = lambda step: ops.rans_decode_dequant(words, states, offsets, freq, step, zp, shape, n_bits,  # noqa: E731
+                                                               chunk, trusted=True)
+            w = dequant(delta)
+            return (w, dequant(torch.ones_like(delta)), delta) if integers else w
 
         self.weights, self.biases = [], []
         self._levels = [None] * len(header["layers"])   # per layer: (levels operand, delta per output channel) where eligible
@@ -418,7 +419,7 @@ class StreamDecoder:
                            "a step that is not finite" if not bool(torch.isfinite(delta).all()) else
                            "level - zero_point is not an integer of magnitude <= 256" if not ops.levels_representable(n) else None)
                     if why is None:
-                        self._levels[i] = (ops.levels_operand(n, checked=True, dtype="f16" if arithmetic == "half" else "bf16"),
+                        self._levels[i] = (ops.levels_operand(n, checked=True, dtype=self._lv_dtype),
                                            delta.reshape(-1).expand(co).contiguous())
                     else:
                         self.levels_ineligible[i] = why
@@ -444,7 +445,7 @@ class StreamDecoder:
         self._emb = list(self.embeddings.split(1))   # per-frame views: a decode gathers without a host -> device copy
         self._operands = [dict() for _ in self.weights]   # per layer: 'bf16x3' / 'fp32' operand, built once
         # 'half': the one sticky word every f16 launch of this decoder may raise and none clears
-        self._sat = torch.zeros(1, dtype=torch.int32, device=self.device) if arithmetic == "half" else None
+        self._sat = torch.zeros(1, dtype=torch.int32, device=self.device) if self._lv_dtype == "f16" else None
         torch.cuda.synchronize(self.device)
 
     def _takes_levels(self, i, x):
@@ -461,9 +462,7 @@ class StreamDecoder:
         ops_ = self._operands[i]
         if self._takes_levels(i, x):
             lv = self._levels[i]
-            if self.arithmetic == "half":
-                return ops.conv3_forward_levels_f16_raw(x, lv[0], lv[1], b, cout, k, self._epi[i], self._r[i], self._sat)[0]
-            return ops.conv3_forward_levels_raw(x, lv[0], lv[1], b, cout, k, self._epi[i], self._r[i])[0]
+            return ops.conv3_forward_levels_raw(x, lv[0], lv[1], b, cout, k, self._epi[i], self._r[i], self._lv_dtype, self._sat)[0]
         if ops._use3(None) and ops.conv3_supported(B, cin, H, W, cout, k):
             if "bf16x3" not in ops_:
                 ops_["bf16x3"] = ops.weight_layout3(w)

@@ -9,14 +9,10 @@ int nq_conv_igemm3_k3(const float*, const void*, const float*, float*, float*, c
                       int, int, int, float*, hipStream_t);
 int nq_conv_igemm3_k5(const float*, const void*, const float*, float*, float*, const float*, int, int, int, int, int, int, int,
                       int, int, int, float*, hipStream_t);
-int nq_conv_igemm3l_k3(const float*, const void*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int,
-                       hipStream_t);
-int nq_conv_igemm3l_k5(const float*, const void*, const float*, const float*, float*, float*, int, int, int, int, int, int, int, int,
-                       hipStream_t);
-int nq_conv_igemm3h_k3(const float*, const void*, const float*, const float*, float*, float*, unsigned*, int, int, int, int, int, int,
-                       int, int, hipStream_t);
-int nq_conv_igemm3h_k5(const float*, const void*, const float*, const float*, float*, float*, unsigned*, int, int, int, int, int, int,
-                       int, int, hipStream_t);
+// levels (l) and half (h) units: one signature; the unsigned* is the half builds' flag word and null for the levels builds
+typedef int nq_igemm3_levels_fn(const float*, const void*, const float*, const float*, float*, float*, unsigned*, int, int, int, int,
+                                int, int, int, int, hipStream_t);
+nq_igemm3_levels_fn nq_conv_igemm3l_k3, nq_conv_igemm3l_k5, nq_conv_igemm3h_k3, nq_conv_igemm3h_k5;
 int nq_conv_splitk_finish(const float*, const float*, float*, float*, const float*, int, int, int, int, int, int, int, hipStream_t);
 int nq_conv_flat3_plan(int, int, int, int, int, int, NqFlat3Plan*);
 int nq_conv3_waves_k3(int, int, int, int, int);
@@ -149,9 +145,10 @@ __device__ __forceinline__ void wl3_tile(const WL3& p, int c, int g16, float* __
   }
 }
 
+template <bool F16 = false>
 __device__ __forceinline__ void wl3_seg_tile(const WL3& p, int blk, float* T) {
-  if (p.KK == 25) wl3_tile<25>(p, blk / p.co16, blk % p.co16, T);
-  else wl3_tile<9>(p, blk / p.co16, blk % p.co16, T);
+  if (p.KK == 25) wl3_tile<25, F16>(p, blk / p.co16, blk % p.co16, T);
+  else wl3_tile<9, F16>(p, blk / p.co16, blk % p.co16, T);
 }
 __global__ __launch_bounds__(256) void weight_layout3_kernel(WL3 p) {
   __shared__ float T[16 * (16 * WL3_KKMAX + 1)];
@@ -160,9 +157,7 @@ __global__ __launch_bounds__(256) void weight_layout3_kernel(WL3 p) {
 
 __global__ __launch_bounds__(256) void weight_layout3_f16_kernel(WL3 p) {
   __shared__ float T[16 * (16 * WL3_KKMAX + 1)];
-  const int blk = (int)blockIdx.x;
-  if (p.KK == 25) wl3_tile<25, true>(p, blk / p.co16, blk % p.co16, T);
-  else wl3_tile<9, true>(p, blk / p.co16, blk % p.co16, T);
+  wl3_seg_tile<true>(p, (int)blockIdx.x, T);
 }
 
 // all layers' operands (forward and data-gradient) in ONE launch: the table travels as a kernel argument
@@ -658,23 +653,26 @@ static int levels_args(const float* x, const void* wt, const float* scale, float
   return levels_route_ok(rt) ? NQ_OK : NQ_ERR_UNSUPPORTED;
 }
 
-int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z, int B, int Cin,
-                            int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream) {
+// Both public entries: f16 selects the half build (template parameter XH), which takes the same checks and the same shapes
+// (nq_conv3_levels_supported) and, in front of them, asks for its flag word
+static int forward3_levels(bool f16, const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z,
+                           unsigned* sat_flag, int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream) {
+  static nq_igemm3_levels_fn* const entry[2][2] = {{nq_conv_igemm3l_k3, nq_conv_igemm3l_k5}, {nq_conv_igemm3h_k3, nq_conv_igemm3h_k5}};
+  if (f16 && !sat_flag) return NQ_ERR_INVALID;
   Fwd3Route rt;
   if (int rc = levels_args(x, wt, scale, y, z, B, Cin, H, W, Cout, k, r, epilogue, rt)) return rc;
-  return (k == 3 ? nq_conv_igemm3l_k3 : nq_conv_igemm3l_k5)(x, wt, scale, bias, y, z, B, Cin, H, W, Cout, r, epilogue, rt.mi,
-                                                            nq_s(stream));
+  return entry[f16][k == 5](x, wt, scale, bias, y, z, sat_flag, B, Cin, H, W, Cout, r, epilogue, rt.mi, nq_s(stream));
 }
 
-// Half build (template parameter XH): the same checks, the same shapes (nq_conv3_levels_supported), and the flag word
+int nq_conv_forward3_levels(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z, int B, int Cin,
+                            int H, int W, int Cout, int k, int r, int epilogue, nq_stream_t stream) {
+  return forward3_levels(false, x, wt, scale, bias, y, z, nullptr, B, Cin, H, W, Cout, k, r, epilogue, stream);
+}
+
 int nq_conv_forward3_levels_f16(const float* x, const void* wt, const float* scale, const float* bias, float* y, float* z,
                                 unsigned* sat_flag, int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue,
                                 nq_stream_t stream) {
-  if (!sat_flag) return NQ_ERR_INVALID;
-  Fwd3Route rt;
-  if (int rc = levels_args(x, wt, scale, y, z, B, Cin, H, W, Cout, k, r, epilogue, rt)) return rc;
-  return (k == 3 ? nq_conv_igemm3h_k3 : nq_conv_igemm3h_k5)(x, wt, scale, bias, y, z, sat_flag, B, Cin, H, W, Cout, r, epilogue, rt.mi,
-                                                            nq_s(stream));
+  return forward3_levels(true, x, wt, scale, bias, y, z, sat_flag, B, Cin, H, W, Cout, k, r, epilogue, stream);
 }
 
 int nq_conv_wgrad3_supported(int B, int Cin, int H, int W, int Cout, int k) {

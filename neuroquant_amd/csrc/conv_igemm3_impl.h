@@ -32,6 +32,10 @@
 #ifndef NQ_KS
 #error "define NQ_KS before including conv_igemm3_impl.h"
 #endif
+// what the including translation unit builds: 0 the bf16x3 kernels and their entry, 1 the levels builds, 2 the half builds
+#ifndef NQ_IG3_BUILD
+#define NQ_IG3_BUILD 0
+#endif
 
 namespace {
 
@@ -849,93 +853,76 @@ inline size_t igemm3_lds_bytes(int mi, bool wide_epi) {
 // the wide data-gradient epilogue: tiles of <= 64 channels that write their own output (the kernel also wants W % 4 == 0)
 inline bool igemm3_wide_epi(int mi, int epi, int nsplit) { return epi == NQ_EPI_DGRAD_GELU && nsplit == 1 && mi <= 4; }
 
-template <int MI, bool XS = false>
+// The launch of one tile: XS split input (bf16x3 units), WX the levels build, WX and XH the half build.  The levels and half
+// builds are never split over K and have no data-gradient epilogue (their entries below), so the rules above give them the
+// plain LDS size and the unsplit grid.
+template <int MI, bool XS = false, bool WX = false, bool XH = false>
 int launch_igemm3(const Conv3Args& a_in, int tiles, hipStream_t st) {
   Conv3Args a = a_in;
   a.lds_epi = igemm3_wide_epi(MI, a.epi, a.nsplit) ? 1 : 0;
   const size_t lds = igemm3_lds_bytes(MI, a.lds_epi != 0);
   a.tiles = tiles;
+  const dim3 grid((unsigned)(tiles * a.co_tiles * a.B * a.nsplit));
   if constexpr (MI <= 3) {
     if (igemm3_waves(MI, a.nchunk, a.tail, a.nsplit, a.per_split) == 3) {   // short K loop
-      if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 3, XS>>(lds)) return rc;
-      hipLaunchKernelGGL((conv_igemm3_kernel<MI, 3, XS>), dim3((unsigned)(tiles * a.co_tiles * a.B * a.nsplit)), dim3(256), lds, st, a);
+      if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 3, XS, WX, XH>>(lds)) return rc;
+      hipLaunchKernelGGL((conv_igemm3_kernel<MI, 3, XS, WX, XH>), grid, dim3(256), lds, st, a);
       return nq_launch_status();
     }
   }
-  if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 2, XS>>(lds)) return rc;
-  hipLaunchKernelGGL((conv_igemm3_kernel<MI, 2, XS>), dim3((unsigned)(tiles * a.co_tiles * a.B * a.nsplit)), dim3(256), lds, st, a);
+  if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 2, XS, WX, XH>>(lds)) return rc;
+  hipLaunchKernelGGL((conv_igemm3_kernel<MI, 2, XS, WX, XH>), grid, dim3(256), lds, st, a);
   return nq_launch_status();
 }
 
-#if defined(NQ_IG3_LEVELS) || defined(NQ_IG3_HALF)
-#ifdef NQ_IG3_HALF
-constexpr bool LV_XH = true;    // translation units conv_igemm3h_k{3,5}.hip: the half builds (WX and XH)
-#else
-constexpr bool LV_XH = false;
-#endif
-// the levels / half build of tile MI: same grid, same LDS, same choice between the 2- and 3-waves build as launch_igemm3
-template <int MI>
-int launch_igemm3_levels(const Conv3Args& a_in, int tiles, hipStream_t st) {
-  Conv3Args a = a_in;
-  a.lds_epi = 0;
-  const size_t lds = igemm3_lds_bytes(MI, false);
-  a.tiles = tiles;
-  if constexpr (MI <= 3) {
-    if (igemm3_waves(MI, a.nchunk, a.tail, 1, a.per_split) == 3) {   // short K loop
-      if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 3, false, true, LV_XH>>(lds)) return rc;
-      hipLaunchKernelGGL((conv_igemm3_kernel<MI, 3, false, true, LV_XH>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
-      return nq_launch_status();
-    }
-  }
-  if (int rc = nq_lds_optin<&conv_igemm3_kernel<MI, 2, false, true, LV_XH>>(lds)) return rc;
-  hipLaunchKernelGGL((conv_igemm3_kernel<MI, 2, false, true, LV_XH>), dim3((unsigned)(tiles * a.co_tiles * a.B)), dim3(256), lds, st, a);
-  return nq_launch_status();
+// the fields of `a` that follow from the shape and the tile alone (16*mi_sel channels); returns the pixel tiles of one frame
+inline int igemm3_geometry(Conv3Args& a, int B, int Cin, int H, int W, int Cout, int mi_sel) {
+  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout;
+  a.tiles_x = (W + TW - 1) / TW;
+  a.nchunk = (Cin + CC - 1) / CC;
+  a.tail = wl3_tail_kind(Cin);
+  a.co_tiles = (Cout + 16 * mi_sel - 1) / (16 * mi_sel);
+  a.w_bytes = (unsigned)wl3_bytes(Cin, KK, a.co_tiles, 16 * mi_sel);
+  return a.tiles_x * ((H + TH - 1) / TH);
 }
-#endif
+
+// mi_sel -> MI: f(std::integral_constant<int, MI>) for the tiles LO..5 (only those are instantiated), else unsupported
+template <int LO, class F>
+int igemm3_with_mi(int mi_sel, F&& f) {
+  if constexpr (LO > 5) return NQ_ERR_UNSUPPORTED;
+  else return mi_sel == LO ? f(std::integral_constant<int, LO>{}) : igemm3_with_mi<LO + 1>(mi_sel, f);
+}
 
 }  // namespace
 
 #define NQ_CAT2(a, b) a##b
 #define NQ_CAT(a, b) NQ_CAT2(a, b)
 
-#if defined(NQ_IG3_LEVELS) || defined(NQ_IG3_HALF)
-// Translation units conv_igemm3l_k{3,5}.hip: the 8 levels builds (WX) of this kernel size and nothing else.  wt3 is the
-// nq_weight_layout3 image of the integer tensor n (its lo plane is zero and never read), scale the quantiser step per output
-// channel.  Unsplit forward with float input and output only: the caller (nq_conv_forward3_levels, conv3.hip) has checked that.
-// Translation units conv_igemm3h_k{3,5}.hip: the 8 half builds (WX, XH) likewise; wt3 is the nq_weight_layout3_f16 image, sat
-// the flag word (nq_conv_forward3_levels_f16).
-#ifdef NQ_IG3_HALF
-extern "C" int NQ_CAT(nq_conv_igemm3h_k, NQ_KS)(const float* x, const void* wt3, const float* scale, const float* bias, float* y,
-                                                 float* z, unsigned* sat, int B, int Cin, int H, int W, int Cout, int r, int epi,
-                                                 int mi_sel, hipStream_t st) {
-  if (!sat) return NQ_ERR_INVALID;
+#if NQ_IG3_BUILD != 0
+// Translation units conv_igemm3l_k{3,5}.hip (NQ_IG3_BUILD 1): the 8 levels builds (WX) of this kernel size and nothing else.
+// wt3 is the nq_weight_layout3 image of the integer tensor n (its lo plane is zero and never read), scale the quantiser step per
+// output channel; sat must be null (the slot is zprev's, which these builds compile out).  Unsplit forward with float input and
+// output only: the caller (forward3_levels, conv3.hip) has checked that.
+// Translation units conv_igemm3h_k{3,5}.hip (NQ_IG3_BUILD 2): the 8 half builds (WX, XH) likewise; wt3 is the
+// nq_weight_layout3_f16 image, sat the flag word.
+#if NQ_IG3_BUILD == 2
+#define NQ_IG3_ENTRY nq_conv_igemm3h_k
 #else
-extern "C" int NQ_CAT(nq_conv_igemm3l_k, NQ_KS)(const float* x, const void* wt3, const float* scale, const float* bias, float* y,
-                                                 float* z, int B, int Cin, int H, int W, int Cout, int r, int epi, int mi_sel,
-                                                 hipStream_t st) {
-  unsigned* const sat = nullptr;   // the slot is zprev's, which these builds compile out
+#define NQ_IG3_ENTRY nq_conv_igemm3l_k
 #endif
+extern "C" int NQ_CAT(NQ_IG3_ENTRY, NQ_KS)(const float* x, const void* wt3, const float* scale, const float* bias, float* y,
+                                            float* z, unsigned* sat, int B, int Cin, int H, int W, int Cout, int r, int epi,
+                                            int mi_sel, hipStream_t st) {
+  constexpr bool XH = NQ_IG3_BUILD == 2;
+  if ((sat != nullptr) != XH) return NQ_ERR_INVALID;
   if ((int64_t)B * Cin * H * W * 4 >= 0xFFFFFF00ll) return NQ_ERR_UNSUPPORTED;   // 32-bit buffer offsets into x
   if (!scale || epi < 0 || epi > NQ_EPI_PS) return NQ_ERR_INVALID;
   Conv3Args a;
   a.x = x; a.wt3 = wt3; a.bias = bias; a.y = y; a.z = z; a.sat = sat; a.scale = scale;
-  a.y_split = 0;
-  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.r = r; a.epi = epi;
-  a.tiles_x = (W + TW - 1) / TW;
-  a.nchunk = (Cin + CC - 1) / CC;
+  a.y_split = 0; a.r = r; a.epi = epi;
+  const int tiles = igemm3_geometry(a, B, Cin, H, W, Cout, mi_sel);
   a.nsplit = 1; a.per_split = a.nchunk;
-  a.tail = wl3_tail_kind(Cin);
-  a.co_tiles = (Cout + 16 * mi_sel - 1) / (16 * mi_sel);
-  a.w_bytes = (unsigned)wl3_bytes(Cin, KK, a.co_tiles, 16 * mi_sel);
-  const int tiles = a.tiles_x * ((H + TH - 1) / TH);
-  switch (mi_sel) {
-    case 1: return launch_igemm3_levels<1>(a, tiles, st);
-    case 2: return launch_igemm3_levels<2>(a, tiles, st);
-    case 3: return launch_igemm3_levels<3>(a, tiles, st);
-    case 4: return launch_igemm3_levels<4>(a, tiles, st);
-    case 5: return launch_igemm3_levels<5>(a, tiles, st);
-    default: return NQ_ERR_UNSUPPORTED;
-  }
+  return igemm3_with_mi<1>(mi_sel, [&](auto mi) { return launch_igemm3<decltype(mi)::value, false, true, XH>(a, tiles, st); });
 }
 #else
 extern "C" int NQ_CAT(nq_conv_igemm3_k, NQ_KS)(const float* x, const void* wt3, const float* bias, float* y, float* z,
@@ -950,30 +937,11 @@ extern "C" int NQ_CAT(nq_conv_igemm3_k, NQ_KS)(const float* x, const void* wt3, 
   a.y_split = (epi & 0x200) ? 1 : 0;
   epi &= 0xFF;
   if (a.y_split && nsplit > 1) return NQ_ERR_UNSUPPORTED;   // (the slabs are finished by another kernel)
-  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.r = r; a.epi = epi;
-  a.tiles_x = (W + TW - 1) / TW;
-  a.nchunk = (Cin + CC - 1) / CC;
-  a.tail = wl3_tail_kind(Cin);
-  a.co_tiles = (Cout + 16 * mi_sel - 1) / (16 * mi_sel);
-  a.w_bytes = (unsigned)wl3_bytes(Cin, KK, a.co_tiles, 16 * mi_sel);
-  const int tiles = a.tiles_x * ((H + TH - 1) / TH);
-  if (xs) {   // (the 16-channel tile is not offered with split input: no layer of the shipped models pairs them)
-    switch (mi_sel) {
-      case 2: return launch_igemm3<2, true>(a, tiles, st);
-      case 3: return launch_igemm3<3, true>(a, tiles, st);
-      case 4: return launch_igemm3<4, true>(a, tiles, st);
-      case 5: return launch_igemm3<5, true>(a, tiles, st);
-      default: return NQ_ERR_UNSUPPORTED;
-    }
-  }
-  switch (mi_sel) {
-    case 1: return launch_igemm3<1>(a, tiles, st);
-    case 2: return launch_igemm3<2>(a, tiles, st);
-    case 3: return launch_igemm3<3>(a, tiles, st);
-    case 4: return launch_igemm3<4>(a, tiles, st);
-    case 5: return launch_igemm3<5>(a, tiles, st);
-    default: return NQ_ERR_UNSUPPORTED;
-  }
+  a.r = r; a.epi = epi;
+  const int tiles = igemm3_geometry(a, B, Cin, H, W, Cout, mi_sel);
+  if (xs)   // (the 16-channel tile is not offered with split input: no layer of the shipped models pairs them)
+    return igemm3_with_mi<2>(mi_sel, [&](auto mi) { return launch_igemm3<decltype(mi)::value, true>(a, tiles, st); });
+  return igemm3_with_mi<1>(mi_sel, [&](auto mi) { return launch_igemm3<decltype(mi)::value>(a, tiles, st); });
 }
 
 // launch rules of this kernel size for the plan query (conv3.hip): waves per SIMD of the build, dynamic LDS bytes

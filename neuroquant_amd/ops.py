@@ -634,10 +634,16 @@ def split_words(x):
     return y
 
 
-def weight_layout3(w, transposed=False):
-    """pre-split (bf16 hi/lo) operand of the bf16x3 conv kernels; transposed=True -> operand of the data gradient."""
+def weight_layout3(w, transposed=False, dtype="bf16"):
+    """pre-split (bf16 hi/lo) operand of the bf16x3 conv kernels; transposed=True -> operand of the data gradient.
+    dtype='f16' (forward operand only): the same layout and size, the hi plane as IEEE halves, the lo plane zero."""
     (sg,), (buf,), (w,) = _wl3_segs([(w, transposed)])
-    L.check(L.lib().nq_weight_layout3(_p(w), _p(buf), sg.Cin, sg.Cout, sg.k, sg.transposed, _stream()), "weight_layout3")
+    if dtype == "f16":
+        if transposed:
+            raise ValueError("weight_layout3: dtype='f16' builds forward operands only")
+        L.check(L.lib().nq_weight_layout3_f16(_p(w), _p(buf), sg.Cin, sg.Cout, sg.k, _stream()), "weight_layout3_f16")
+    else:
+        L.check(L.lib().nq_weight_layout3(_p(w), _p(buf), sg.Cin, sg.Cout, sg.k, sg.transposed, _stream()), "weight_layout3")
     return buf
 
 
@@ -676,11 +682,9 @@ def levels_representable(n):
 
 
 def levels_operand(n, checked=False, dtype="bf16"):
-    """operand of conv3_forward_levels_raw (dtype='bf16') or conv3_forward_levels_f16_raw (dtype='f16') from the OIHW float tensor
-    n = level - zero_point of a stored weight.  The kernels read the hi halves only, so n must satisfy levels_representable:
-    ValueError otherwise (checked=True: the caller has asked levels_representable already).  'bf16': the bytes are
-    weight_layout3's.  'f16': the same layout and size with the integers as IEEE halves (nq_weight_layout3_f16), which hold them
-    exactly too.  Either way the lo plane is all zeros and never read."""
+    """operand of conv3_forward_levels_raw with the same dtype from the OIHW float tensor n = level - zero_point of a stored
+    weight: weight_layout3(n, dtype=dtype), whose lo plane is all zeros and never read.  n must satisfy levels_representable
+    (bf16 and half both hold such integers exactly): ValueError otherwise; checked=True: the caller has asked already."""
     n = _dev(n.detach(), "n")
     if dtype not in ("bf16", "f16"):
         raise ValueError(f"levels_operand: dtype must be 'bf16' or 'f16', got {dtype!r}")
@@ -689,11 +693,7 @@ def levels_operand(n, checked=False, dtype="bf16"):
     if not checked and not levels_representable(n):
         raise ValueError("levels_operand: every entry must be an integer of magnitude <= 256 that bf16 holds exactly "
                          "(level - zero_point of an integer zero point)")
-    if dtype == "bf16":
-        return weight_layout3(n.contiguous())
-    (sg,), (buf,), (n,) = _wl3_segs([(n.contiguous(), False)])
-    L.check(L.lib().nq_weight_layout3_f16(_p(n), _p(buf), sg.Cin, sg.Cout, sg.k, _stream()), "weight_layout3_f16")
-    return buf
+    return weight_layout3(n.contiguous(), dtype=dtype)
 
 
 def _levels_scale(scale, cout, who):
@@ -703,37 +703,37 @@ def _levels_scale(scale, cout, who):
     return scale
 
 
-def conv3_forward_levels_raw(x, wt, scale, bias, cout, k, epilogue, r):
-    """Levels counterpart of conv3_forward_raw: y = scale[co] * conv(x, n) + bias[co] with wt = levels_operand(n), two MFMAs
-    per product (include/nq_hip.h).  Forward epilogues only; returns (y, z) as conv3_forward_raw does."""
+def conv3_forward_levels_raw(x, wt, scale, bias, cout, k, epilogue, r, dtype="bf16", sat_flag=None):
+    """Levels counterpart of conv3_forward_raw: y = scale[co] * conv(x, n) + bias[co] with wt = levels_operand(n, dtype=dtype).
+    Forward epilogues only; returns (y, z) as conv3_forward_raw does; serves the shapes of conv3_levels_supported.
+    dtype='bf16': two BF16 MFMAs per product (include/nq_hip.h); takes no flag word.
+    dtype='f16': conv(f16(x), n), one F16 MFMA per product (an approximation); sat_flag: one int32 on the
+    device, the launch stores 1 to it when it clamped a finite |x| > 65504 and never clears it.  No synchronisation here."""
+    who = "conv3_forward_levels_raw"
+    if dtype not in ("bf16", "f16"):
+        raise ValueError(f"{who}: dtype must be 'bf16' or 'f16', got {dtype!r}")
     B, cin, H, W = x.shape
-    scale = _levels_scale(scale, cout, "conv3_forward_levels_raw")
+    scale = _levels_scale(scale, cout, who)
     if epilogue == EPI_DGRAD_GELU:
-        raise ValueError("conv3_forward_levels_raw serves forward epilogues only")
+        raise ValueError(f"{who} serves forward epilogues only")
+    if dtype == "f16":
+        sat_flag = _dev_as(sat_flag, torch.int32, "sat_flag")
+        if sat_flag.numel() != 1:
+            raise ValueError(f"{who}: sat_flag must be one int32 on the device")
+    elif sat_flag is not None:
+        raise ValueError(f"{who}: dtype='bf16' takes no sat_flag")
     y, z = _conv_outputs(x, cout, epilogue, r)
-    _timed(("conv_igemm3_levels", k, cin, cout, H, W, B, epilogue),
-           lambda: L.check(L.lib().nq_conv_forward3_levels(_p(x), _p(wt), _p(scale), _p(bias), _p(y), _p(z), B, cin, H, W, cout, k,
-                                                           r, epilogue, _stream()), "conv_forward3_levels"))
+    sfx, flag = ("_f16", [_p(sat_flag)]) if dtype == "f16" else ("", [])     # the two entries differ by the flag word alone
+    fn = getattr(L.lib(), "nq_conv_forward3_levels" + sfx)
+    _timed(("conv_igemm3_levels" + sfx, k, cin, cout, H, W, B, epilogue),
+           lambda: L.check(fn(_p(x), _p(wt), _p(scale), _p(bias), _p(y), _p(z), *flag, B, cin, H, W, cout, k, r, epilogue, _stream()),
+                           "conv_forward3_levels" + sfx))
     return y, z
 
 
 def conv3_forward_levels_f16_raw(x, wt, scale, bias, cout, k, epilogue, r, sat_flag):
-    """Half-precision counterpart of conv3_forward_levels_raw: y = scale[co] * conv(f16(x), n) + bias[co] with
-    wt = levels_operand(n, dtype='f16'), one F16 MFMA per product (include/nq_hip.h; an approximation).
-    sat_flag: one int32 on the device; the launch stores 1 to it when it clamped a finite |x| > 65504 and never clears it.  No
-    synchronisation here.  Serves the shapes of conv3_levels_supported."""
-    B, cin, H, W = x.shape
-    scale = _levels_scale(scale, cout, "conv3_forward_levels_f16_raw")
-    if epilogue == EPI_DGRAD_GELU:
-        raise ValueError("conv3_forward_levels_f16_raw serves forward epilogues only")
-    sat_flag = _dev_as(sat_flag, torch.int32, "sat_flag")
-    if sat_flag.numel() != 1:
-        raise ValueError("conv3_forward_levels_f16_raw: sat_flag must be one int32 on the device")
-    y, z = _conv_outputs(x, cout, epilogue, r)
-    _timed(("conv_igemm3_levels_f16", k, cin, cout, H, W, B, epilogue),
-           lambda: L.check(L.lib().nq_conv_forward3_levels_f16(_p(x), _p(wt), _p(scale), _p(bias), _p(y), _p(z), _p(sat_flag), B, cin,
-                                                               H, W, cout, k, r, epilogue, _stream()), "conv_forward3_levels_f16"))
-    return y, z
+    """the half launch under its first name, which callers outside this package hold: conv3_forward_levels_raw(dtype='f16')"""
+    return conv3_forward_levels_raw(x, wt, scale, bias, cout, k, epilogue, r, "f16", sat_flag)
 
 
 def conv_wgrad3_supported(B, cin, H, W, cout, k):

@@ -2,23 +2,17 @@
 the layers `levels` takes, those layers are right against float64 on the file's own integers at the derived bound of
 tests/test_half_conv_gpu.py (check 3), whole frames stay within a cap computed from that bound, and the `exact` and `levels`
 players are what they were."""
-import os
-import subprocess
-import sys
-
-import numpy as np
 import pytest
 import torch
 
-import bitstream_ref as R
 import conv3_cases as C
-from conftest import BITS, ROOT, T, TINY_HNERV, TINY_NERV, state_dict_from_npz
+from conftest import BITS, T, TINY_HNERV
+from levels_cases import (DEV, all_frames, check_driver_names_the_layers, file_layer, hadamard_nerv_file, hnerv_file, nerv_file,
+                          quant_model, spy)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-N = 8
-U = 2.0 ** -11                  # unit roundoff of IEEE half
+U =2.0 ** -11                  # unit roundoff of IEEE half
 GELU_SLOPE = 1.13               # max gelu' = 1.129
 
 
@@ -32,61 +26,6 @@ def ops():
 @pytest.fixture(scope="module")
 def frames(golden):
     return (T(golden("frames_320x640.npz")["frames"]).float() / 255.0).to(DEV)
-
-
-def _quant_model(golden, name, arch, had, bits=BITS, channel_wise=True):
-    """a tiny model of tests/golden under uncalibrated 'max' scales, one quantised forward done"""
-    from neuroquant_amd.models import HNeRV, NeRV
-    from neuroquant_amd.quantization import QuantModel
-    z = golden(name)
-    model = (HNeRV if arch == "hnerv" else NeRV)(TINY_HNERV if arch == "hnerv" else TINY_NERV)
-    missing, unexpected = model.load_state_dict(state_dict_from_npz(z, "sd:"), strict=False)
-    assert not unexpected and not missing, (missing, unexpected)
-    qnn = QuantModel(model.to(DEV).eval(), hadamard=had,
-                     weight_quant_params=dict(n_bits=8, channel_wise=channel_wise, scale_method="max"))
-    qnn.set_bitwidth(bits)
-    qnn.eval()
-    qnn.set_quant_state(True)
-    emb = T(z["emb"]).to(DEV)
-    with torch.no_grad():
-        qnn(emb[:2])
-    return qnn, emb
-
-
-def _hnerv_file(golden, tmp_path, name="m.nqv", bits=BITS, channel_wise=True, **kw):
-    from neuroquant_amd.bitstream import write_stream
-    qnn, emb = _quant_model(golden, "traj_hnerv.npz", "hnerv", False, bits=bits, channel_wise=channel_wise)
-    path = str(tmp_path / name)
-    write_stream(qnn, path, "hnerv", dict(TINY_HNERV), embeddings=emb, **kw)
-    return path
-
-
-def _spy(dec):
-    """record every layer's input on its way through dec._conv: {(B, layer): x}"""
-    seen, orig = {}, dec._conv
-
-    def conv(i, x):
-        seen[(x.shape[0], i)] = x
-        return orig(i, x)
-
-    dec._conv = conv
-    return seen
-
-
-def _all_frames(dec, B, **kw):
-    return torch.cat([dec.decode(list(range(j, j + B)), **kw) for j in range(0, N, B)])
-
-
-def _file_layer(path, i):
-    """(n = level - zero_point, delta per channel, bias) of layer i in float64, read with tests/bitstream_ref.py alone"""
-    header, sec, _ = R.read(path)
-    lay = header["layers"][i]
-    co, ci, k, k2 = lay["shape"]
-    lv = R.unpack(sec[f"w{i}.levels"], co * ci * k * k2, lay["n_bits"]).astype(np.float64).reshape(co, ci, k, k2)
-    zp = sec[f"w{i}.zero_point"].astype(np.float64).reshape(-1, 1, 1, 1)
-    delta = np.broadcast_to(sec[f"w{i}.delta"].astype(np.float64).reshape(-1), (co,))     # one step per channel or one in all
-    assert header["bias"] == "soft"
-    return T(lv - zp), T(np.ascontiguousarray(delta)), T(sec[f"b{i}.soft"].astype(np.float64))
 
 
 def _layer_reference(x, n, delta, b, k, r):
@@ -109,22 +48,22 @@ def _layer_reference(x, n, delta, b, k, r):
 @pytest.mark.parametrize("bits", (BITS, [2] * 7, [8] * 7), ids=("mixed", "2bit", "8bit"))
 def test_half_player(ops, golden, frames, tmp_path, bits, channel_wise):
     from neuroquant_amd.bitstream import StreamDecoder
-    path = _hnerv_file(golden, tmp_path, bits=bits, channel_wise=channel_wise)
+    path = hnerv_file(golden, tmp_path, bits=bits, channel_wise=channel_wise)
     exact, lev = StreamDecoder(path, arithmetic="exact"), StreamDecoder(path, arithmetic="levels")
-    before = {B: (_all_frames(exact, B), _all_frames(lev, B)) for B in (1, 2)}      # before any half decoder exists
+    before = {B: (all_frames(exact, B), all_frames(lev, B)) for B in (1, 2)}      # before any half decoder exists
     half = StreamDecoder(path, arithmetic="half")
     assert half.arithmetic == "half" and half.levels_used == {} and half.saturated() is False
     assert half.levels_ineligible == lev.levels_ineligible and sorted(half.levels_ineligible) == [0, 1]
-    seen = _spy(half)
+    seen = spy(half)
     out, E = {}, {}
     for B in (1, 2):
-        out[B] = _all_frames(half, B)
+        out[B] = all_frames(half, B)
         # the path taken: exactly the layers `levels` takes
         assert half.levels_used[B] == lev.levels_used[B] == [len(half.weights) - 2], (B, half.levels_used, lev.levels_used)
         for i in half.levels_used[B]:
             x = seen[(B, i)]
             cout, cin, k, _ = half.weights[i].shape
-            n, delta, b = _file_layer(path, i)
+            n, delta, b = file_layer(path, i)
             ref, bound, E[B] = _layer_reference(x, n, delta, b, k, half._r[i])
             assert half._takes_levels(i, x) and not exact._takes_levels(i, x)
             err = (half._conv(i, x).cpu().double() - ref).abs()
@@ -143,7 +82,7 @@ def test_half_player(ops, golden, frames, tmp_path, bits, channel_wise):
         assert diff <= cap
         assert abs(ph - pe) < 0.02
         for layout in ("chw", "hwc"):
-            ue, uh = _all_frames(exact, B, out="u8", layout=layout), _all_frames(half, B, out="u8", layout=layout)
+            ue, uh = all_frames(exact, B, out="u8", layout=layout), all_frames(half, B, out="u8", layout=layout)
             d8 = (ue.int() - uh.int()).abs()
             print(f"B {B} u8 {layout}: {float((d8 != 0).float().mean()) * 100:.4f} % of the bytes differ")
             assert int(d8.max()) <= 1
@@ -151,20 +90,20 @@ def test_half_player(ops, golden, frames, tmp_path, bits, channel_wise):
     # the other two arithmetics, decoders opened before and after the half decoder ran: the same bits
     exact2, lev2 = StreamDecoder(path), StreamDecoder(path, arithmetic="levels")
     for B in (1, 2):
-        assert torch.equal(_all_frames(exact, B), before[B][0]) and torch.equal(_all_frames(exact2, B), before[B][0])
-        assert torch.equal(_all_frames(lev, B), before[B][1]) and torch.equal(_all_frames(lev2, B), before[B][1])
-    assert torch.equal(_all_frames(half, 1), out[1])
+        assert torch.equal(all_frames(exact, B), before[B][0]) and torch.equal(all_frames(exact2, B), before[B][0])
+        assert torch.equal(all_frames(lev, B), before[B][1]) and torch.equal(all_frames(lev2, B), before[B][1])
+    assert torch.equal(all_frames(half, 1), out[1])
 
 
 def test_entropy_coded_files_give_the_same_half_decoder(ops, golden, tmp_path):
     from neuroquant_amd.bitstream import StreamDecoder, write_stream
-    qnn, emb = _quant_model(golden, "traj_hnerv.npz", "hnerv", False)
+    qnn, emb = quant_model(golden, "traj_hnerv.npz", "hnerv", False)
     outs = {}
     for coding in ("packed", "rans", "auto"):
         path = str(tmp_path / f"{coding}.nqv")
         write_stream(qnn, path, "hnerv", dict(TINY_HNERV), embeddings=emb, coding=coding)
         dec = StreamDecoder(path, arithmetic="half")
-        outs[coding] = (_all_frames(dec, 1), _all_frames(dec, 2), dec)
+        outs[coding] = (all_frames(dec, 1), all_frames(dec, 2), dec)
     assert outs["rans"][2].level_tensors["rans"] == 7 and outs["packed"][2].level_tensors["rans"] == 0
     for coding in ("rans", "auto"):
         assert outs[coding][2].levels_used == outs["packed"][2].levels_used and outs[coding][2].levels_used[1]
@@ -174,26 +113,15 @@ def test_entropy_coded_files_give_the_same_half_decoder(ops, golden, tmp_path):
 
 def test_nerv_last_block_takes_the_3x3_build(ops, tmp_path):
     """a NeRV file outside the Hadamard domain (randomly initialised: no fixture holds one): the last block, k = 3"""
-    from neuroquant_amd.bitstream import StreamDecoder, write_stream
-    from neuroquant_amd.models import NeRV
-    from neuroquant_amd.quantization import QuantModel
-    torch.manual_seed(7)
-    qnn = QuantModel(NeRV(TINY_NERV).to(DEV).eval(), hadamard=False,
-                     weight_quant_params=dict(n_bits=8, channel_wise=True, scale_method="max"))
-    qnn.set_bitwidth(BITS)
-    qnn.eval()
-    qnn.set_quant_state(True)
-    with torch.no_grad():
-        qnn(qnn.encode(torch.tensor([0.0, 0.125], device=DEV)))
-    path = str(tmp_path / "nerv.nqv")
-    write_stream(qnn, path, "nerv", dict(TINY_NERV), frames=N)
+    from neuroquant_amd.bitstream import StreamDecoder
+    path = nerv_file(tmp_path)
     exact, half = StreamDecoder(path), StreamDecoder(path, arithmetic="half")
-    seen = _spy(half)
+    seen = spy(half)
     gain = float(half.weights[-1].abs().sum(dim=(1, 2, 3)).max())
     for B in (1, 2):
-        fe, fh = _all_frames(exact, B), _all_frames(half, B)
+        fe, fh = all_frames(exact, B), all_frames(half, B)
         assert half.levels_used[B] == [5] and half.weights[5].shape[2] == 3
-        n, delta, b = _file_layer(path, 5)
+        n, delta, b = file_layer(path, 5)
         _, _, E = _layer_reference(seen[(B, 5)], n, delta, b, 3, half._r[5])
         cap = 2 * (C.ATOL + C.RTOL * float(fe.abs().max())) + 0.5 * GELU_SLOPE * gain * E
         diff = float((fe - fh).abs().max())
@@ -206,11 +134,11 @@ def test_saturated_reports_a_clamped_activation_and_stays_set(ops, golden, tmp_p
     """embeddings scaled by 1e8 drive the last block's input far beyond 65504 (the layers in front of it are GELU-linear at that
     size and stay finite in fp32): the flag goes up, stays up on clean frames, and belongs to that decoder alone"""
     from neuroquant_amd.bitstream import StreamDecoder
-    path = _hnerv_file(golden, tmp_path)
+    path = hnerv_file(golden, tmp_path)
     half, other, exact = StreamDecoder(path, arithmetic="half"), StreamDecoder(path, arithmetic="half"), StreamDecoder(path)
     clean = half.decode([0])
     assert half.saturated() is False
-    seen = _spy(half)
+    seen = spy(half)
     half._emb = [e * 1e8 for e in half._emb]
     half.decode([0])
     x = seen[(1, 5)]
@@ -222,27 +150,17 @@ def test_saturated_reports_a_clamped_activation_and_stays_set(ops, golden, tmp_p
 
 
 def test_refusals(ops, golden, tmp_path):
-    from neuroquant_amd.bitstream import StreamDecoder, write_stream
+    from neuroquant_amd.bitstream import StreamDecoder
     assert StreamDecoder.ARITHMETICS == ("exact", "levels", "half")
-    path = _hnerv_file(golden, tmp_path)
+    path = hnerv_file(golden, tmp_path)
     for bad in ("fast", "f16", "Half", None):
         with pytest.raises(ValueError):
             StreamDecoder(path, arithmetic=bad)
-    # Hadamard-domain files store the levels of the transformed weights
-    qnn, emb = _quant_model(golden, "traj_nerv_had.npz", "nerv", True)
-    had = str(tmp_path / "n.nqv")
-    write_stream(qnn, had, "nerv", dict(TINY_NERV), frames=N)
+    had = hadamard_nerv_file(golden, tmp_path)
     with pytest.raises(ValueError):
         StreamDecoder(had, arithmetic="half")
     assert StreamDecoder(had).decode([0]).shape == (1, 3, 320, 640)
 
 
 def test_driver_names_the_layers(golden, tmp_path):
-    path = _hnerv_file(golden, tmp_path)
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    p = subprocess.run([sys.executable, "-m", "neuroquant_amd.methods.decode_stream", "--stream", path, "--arithmetic", "half",
-                        "--synthetic", str(N)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    print(p.stdout)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "arithmetic half: batch 1: layers [5]" in p.stdout and "float: PSNR" in p.stdout and "decode FPS" in p.stdout
-    assert "clamped" not in p.stdout
+    assert "clamped" not in check_driver_names_the_layers(golden, tmp_path, "half")

@@ -1,22 +1,16 @@
 """The player's opt-in `levels` arithmetic (StreamDecoder(arithmetic="levels")) on the tiny models: which
 layers take the integer-level convolution, that those layers are right against float64 on the file's own integers, and how far
 whole frames move from the default (`exact`) player, which stays bit-identical to what it was."""
-import os
-import subprocess
-import sys
-
-import numpy as np
 import pytest
 import torch
 
-import bitstream_ref as R
 import conv3_cases as C
-from conftest import BITS, ROOT, T, TINY_HNERV, TINY_NERV, state_dict_from_npz
+from conftest import BITS, T, TINY_HNERV
+from levels_cases import (DEV, all_frames, check_driver_names_the_layers, file_layer, hadamard_nerv_file, hnerv_file, nerv_file,
+                          quant_model, spy)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-N = 8
 CAP = 2 * (C.ATOL + C.RTOL)     # both players are within ATOL + RTOL * |ref| (|ref| <= 1: frames) of ONE float64 value at the
 #                                 last block; the head behind it is the same launch on inputs that far apart
 
@@ -33,75 +27,20 @@ def frames(golden):
     return (T(golden("frames_320x640.npz")["frames"]).float() / 255.0).to(DEV)
 
 
-def _quant_model(golden, name, arch, had, bits=BITS, channel_wise=True):
-    """a tiny model of tests/golden under uncalibrated 'max' scales, one quantised forward done"""
-    from neuroquant_amd.models import HNeRV, NeRV
-    from neuroquant_amd.quantization import QuantModel
-    z = golden(name)
-    model = (HNeRV if arch == "hnerv" else NeRV)(TINY_HNERV if arch == "hnerv" else TINY_NERV)
-    missing, unexpected = model.load_state_dict(state_dict_from_npz(z, "sd:"), strict=False)
-    assert not unexpected and not missing, (missing, unexpected)
-    qnn = QuantModel(model.to(DEV).eval(), hadamard=had,
-                     weight_quant_params=dict(n_bits=8, channel_wise=channel_wise, scale_method="max"))
-    qnn.set_bitwidth(bits)
-    qnn.eval()
-    qnn.set_quant_state(True)
-    emb = T(z["emb"]).to(DEV)
-    with torch.no_grad():
-        qnn(emb[:2])
-    return qnn, emb
-
-
-def _hnerv_file(golden, tmp_path, name="m.nqv", bits=BITS, channel_wise=True, **kw):
-    from neuroquant_amd.bitstream import write_stream
-    qnn, emb = _quant_model(golden, "traj_hnerv.npz", "hnerv", False, bits=bits, channel_wise=channel_wise)
-    path = str(tmp_path / name)
-    write_stream(qnn, path, "hnerv", dict(TINY_HNERV), embeddings=emb, **kw)
-    return path
-
-
-def _spy(dec):
-    """record every layer's input on its way through dec._conv: {(B, layer): x}"""
-    seen, orig = {}, dec._conv
-
-    def conv(i, x):
-        seen[(x.shape[0], i)] = x
-        return orig(i, x)
-
-    dec._conv = conv
-    return seen
-
-
-def _all_frames(dec, B, **kw):
-    return torch.cat([dec.decode(list(range(j, j + B)), **kw) for j in range(0, N, B)])
-
-
-def _file_layer(path, i):
-    """(n = level - zero_point, delta per channel, bias) of layer i in float64, read with tests/bitstream_ref.py alone"""
-    header, sec, _ = R.read(path)
-    lay = header["layers"][i]
-    co, ci, k, k2 = lay["shape"]
-    lv = R.unpack(sec[f"w{i}.levels"], co * ci * k * k2, lay["n_bits"]).astype(np.float64).reshape(co, ci, k, k2)
-    zp = sec[f"w{i}.zero_point"].astype(np.float64).reshape(-1, 1, 1, 1)
-    delta = np.broadcast_to(sec[f"w{i}.delta"].astype(np.float64).reshape(-1), (co,))     # one step per channel or one in all
-    assert header["bias"] == "soft"
-    return T(lv - zp), T(np.ascontiguousarray(delta)), T(sec[f"b{i}.soft"].astype(np.float64))
-
-
 @pytest.mark.parametrize("channel_wise", (True, False), ids=("channelwise", "layerwise"))
 @pytest.mark.parametrize("bits", (BITS, [2] * 7, [8] * 7), ids=("mixed", "2bit", "8bit"))
 def test_levels_player(ops, golden, frames, tmp_path, bits, channel_wise):
     from neuroquant_amd.bitstream import StreamDecoder
-    path = _hnerv_file(golden, tmp_path, bits=bits, channel_wise=channel_wise)
+    path = hnerv_file(golden, tmp_path, bits=bits, channel_wise=channel_wise)
     exact, lev = StreamDecoder(path, arithmetic="exact"), StreamDecoder(path, arithmetic="levels")
     assert exact.arithmetic == "exact" and lev.arithmetic == "levels" and lev.levels_used == {}
     # only the 1 x 1 layers (the stem and the first block) can never take the path, and the decoder says why
     assert [i for i, w in enumerate(lev.weights) if w.shape[2] == 1] == [0, 1] == sorted(lev.levels_ineligible)
     assert all("1 x 1" in why for why in lev.levels_ineligible.values()) and exact.levels_ineligible == {}
-    seen = _spy(lev)
+    seen = spy(lev)
     out = {}
     for B in (1, 2):
-        out[B] = (_all_frames(exact, B), _all_frames(lev, B))
+        out[B] = (all_frames(exact, B), all_frames(lev, B))
         # the path taken: exactly the layers the library offers it for, here the last block
         want = []
         for i, w in enumerate(lev.weights):
@@ -115,7 +54,7 @@ def test_levels_player(ops, golden, frames, tmp_path, bits, channel_wise):
         for i in want:
             x = seen[(B, i)]
             cout, cin, k, _ = lev.weights[i].shape
-            n, delta, b = _file_layer(path, i)
+            n, delta, b = file_layer(path, i)
             conv = C.forward_conv(x.cpu(), n * delta.view(-1, 1, 1, 1), k)
             ref, _ = C.forward_reference(conv, b, ("psgelu", lev._r[i], True))
             assert lev._takes_levels(i, x) and not exact._takes_levels(i, x)
@@ -132,24 +71,24 @@ def test_levels_player(ops, golden, frames, tmp_path, bits, channel_wise):
         assert diff <= CAP
         assert abs(pl - pe) < 0.02
         for layout in ("chw", "hwc"):
-            ue, ul = _all_frames(exact, B, out="u8", layout=layout), _all_frames(lev, B, out="u8", layout=layout)
+            ue, ul = all_frames(exact, B, out="u8", layout=layout), all_frames(lev, B, out="u8", layout=layout)
             d8 = (ue.int() - ul.int()).abs()
             print(f"B {B} u8 {layout}: {float((d8 != 0).float().mean()) * 100:.4f} % of the bytes differ")
             assert int(d8.max()) <= 1
     # one batch size's result does not depend on which was decoded first, and the record of the path is written once
     used = {B: list(v) for B, v in lev.levels_used.items()}
-    assert torch.equal(_all_frames(lev, 1), out[1][1]) and lev.levels_used == used
+    assert torch.equal(all_frames(lev, 1), out[1][1]) and lev.levels_used == used
 
 
 def test_entropy_coded_files_give_the_same_levels_decoder(ops, golden, tmp_path):
     from neuroquant_amd.bitstream import StreamDecoder, write_stream
-    qnn, emb = _quant_model(golden, "traj_hnerv.npz", "hnerv", False)
+    qnn, emb = quant_model(golden, "traj_hnerv.npz", "hnerv", False)
     outs = {}
     for coding in ("packed", "rans", "auto"):
         path = str(tmp_path / f"{coding}.nqv")
         write_stream(qnn, path, "hnerv", dict(TINY_HNERV), embeddings=emb, coding=coding)
         dec = StreamDecoder(path, arithmetic="levels")
-        outs[coding] = (_all_frames(dec, 1), _all_frames(dec, 2), dec)
+        outs[coding] = (all_frames(dec, 1), all_frames(dec, 2), dec)
     assert outs["rans"][2].level_tensors["rans"] == 7 and outs["packed"][2].level_tensors["rans"] == 0
     for coding in ("rans", "auto"):
         assert outs[coding][2].levels_used == outs["packed"][2].levels_used and outs[coding][2].levels_used[1]
@@ -158,32 +97,21 @@ def test_entropy_coded_files_give_the_same_levels_decoder(ops, golden, tmp_path)
 
 def test_hard_bias_file(ops, golden, tmp_path):
     from neuroquant_amd.bitstream import StreamDecoder
-    path = _hnerv_file(golden, tmp_path, name="h.nqv", bias="hard")
+    path = hnerv_file(golden, tmp_path, name="h.nqv", bias="hard")
     exact, lev = StreamDecoder(path), StreamDecoder(path, arithmetic="levels")
     for B in (1, 2):
-        diff = float((_all_frames(exact, B) - _all_frames(lev, B)).abs().max())
+        diff = float((all_frames(exact, B) - all_frames(lev, B)).abs().max())
         print(f"hard biases, B {B}: largest |levels - exact| {diff:.3e}")
         assert lev.levels_used[B] == [5] and diff <= CAP
 
 
 def test_nerv_last_block_takes_the_3x3_build(ops, tmp_path):
     """a NeRV file outside the Hadamard domain (randomly initialised: no fixture holds one): the last block, k = 3"""
-    from neuroquant_amd.bitstream import StreamDecoder, write_stream
-    from neuroquant_amd.models import NeRV
-    from neuroquant_amd.quantization import QuantModel
-    torch.manual_seed(7)
-    qnn = QuantModel(NeRV(TINY_NERV).to(DEV).eval(), hadamard=False,
-                     weight_quant_params=dict(n_bits=8, channel_wise=True, scale_method="max"))
-    qnn.set_bitwidth(BITS)
-    qnn.eval()
-    qnn.set_quant_state(True)
-    with torch.no_grad():
-        qnn(qnn.encode(torch.tensor([0.0, 0.125], device=DEV)))
-    path = str(tmp_path / "nerv.nqv")
-    write_stream(qnn, path, "nerv", dict(TINY_NERV), frames=N)
+    from neuroquant_amd.bitstream import StreamDecoder
+    path = nerv_file(tmp_path)
     exact, lev = StreamDecoder(path), StreamDecoder(path, arithmetic="levels")
     for B in (1, 2):
-        fe, fl = _all_frames(exact, B), _all_frames(lev, B)
+        fe, fl = all_frames(exact, B), all_frames(lev, B)
         diff = float((fe - fl).abs().max())
         print(f"NeRV, B {B}: layers {lev.levels_used[B]}, largest |levels - exact| {diff:.3e}")
         assert lev.levels_used[B] == [5] and lev.weights[5].shape[2] == 3
@@ -191,28 +119,19 @@ def test_nerv_last_block_takes_the_3x3_build(ops, tmp_path):
 
 
 def test_refusals_and_the_default(ops, golden, tmp_path):
-    from neuroquant_amd.bitstream import StreamDecoder, write_stream
-    path = _hnerv_file(golden, tmp_path)
+    from neuroquant_amd.bitstream import StreamDecoder
+    path = hnerv_file(golden, tmp_path)
     with pytest.raises(ValueError):
         StreamDecoder(path, arithmetic="fast")
     plain, exact = StreamDecoder(path), StreamDecoder(path, arithmetic="exact")
     for B in (1, 2):
-        assert torch.equal(_all_frames(plain, B), _all_frames(exact, B))
+        assert torch.equal(all_frames(plain, B), all_frames(exact, B))
     assert plain.arithmetic == "exact"
-    # Hadamard-domain files store the levels of the transformed weights
-    qnn, emb = _quant_model(golden, "traj_nerv_had.npz", "nerv", True)
-    had = str(tmp_path / "n.nqv")
-    write_stream(qnn, had, "nerv", dict(TINY_NERV), frames=N)
+    had = hadamard_nerv_file(golden, tmp_path)
     with pytest.raises(ValueError):
         StreamDecoder(had, arithmetic="levels")
     assert StreamDecoder(had).decode([0]).shape == (1, 3, 320, 640)
 
 
 def test_driver_names_the_layers(golden, tmp_path):
-    path = _hnerv_file(golden, tmp_path)
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    p = subprocess.run([sys.executable, "-m", "neuroquant_amd.methods.decode_stream", "--stream", path, "--arithmetic", "levels",
-                        "--synthetic", str(N)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    print(p.stdout)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "arithmetic levels: batch 1: layers [5]" in p.stdout and "float: PSNR" in p.stdout and "decode FPS" in p.stdout
+    check_driver_names_the_layers(golden, tmp_path, "levels")
