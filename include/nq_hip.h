@@ -265,6 +265,31 @@ NQ_API int64_t nq_conv_forward_ws_floats(int B, int Cin, int H, int W, int Cout,
 NQ_API int nq_conv_split_out(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int has_bias);
 NQ_API int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y, float* z, float* ws, int B, int Cin, int H,
                     int W, int Cout, int k, int krows, int ld, int r, int epilogue, const float* zprev, nq_stream_t stream);
+/* The launch plan nq_conv_forward will use for this call (additive to ABI v7; pure host function): which kernel family and which
+ * of its builds.  Not a second derivation: the launch, this query, nq_conv_forward_ws_floats and nq_conv_split_out read ONE
+ * resolution of the call (route_fwd, csrc/conv.hip, with the head's choices resolved in csrc/conv_head.hip); the head's environment
+ * knobs (NQ_HEAD_FWD, NQ_HEAD_RD, NQ_HEAD_DGRAD, NQ_HEAD_DG_R) are read per call, by the query as by the launch.  `epilogue`
+ * without the split-word bits.  NQ_ERR_INVALID for whatever arguments nq_conv_forward rejects as invalid by their values (sizes,
+ * epilogue, r) or out == NULL, NQ_ERR_UNSUPPORTED for k outside {1,3,5}, B > 65535 or a knob that names a build that is not compiled. */
+#define NQ_CONV_IGEMM 1          /* conv_igemm: 4 x 32-pixel tiles x 16*mi channels per workgroup, fp32 MFMA */
+#define NQ_CONV_TINY 2           /* tiny_pw_fwd: 1x1 over <= 256 pixels, a thread (or ksl threads) per output */
+#define NQ_CONV_HEAD_FWD 3       /* head_fwd2: streaming head forward (3x3, 3 channels, W % 4 == 0) */
+#define NQ_CONV_HEAD_FWD_LDS 4   /* head_fwd: LDS-staged head forward (<= 4 output channels) */
+#define NQ_CONV_HEAD_DGRAD 5     /* head_dgrad2: streaming head data gradient (3x3, 3 channels, r == 2) */
+#define NQ_CONV_HEAD_DGRAD_LDS 6 /* head_dgrad: LDS-staged head data gradient (<= 4 input channels, no bias) */
+typedef struct nq_conv_plan {
+  int kernel;     /* NQ_CONV_* */
+  int mi;         /* implicit GEMM: 16*mi = channel tile; 0 for the other families, like the next three */
+  int ncg;        /* channel groups of its K loop: Cin / CI rounded up, CI = 16 / 8 / 4 for k = 1 / 3 / 5 */
+  int nsplit;     /* splits of the K loop over workgroups; > 1: slabs in ws, nq_conv_splitk_finish writes y / z */
+  int finish;     /* build of the finish kernel: 0 none, 1 a thread per output, 8 eight threads per output */
+  int ksl;        /* tiny: threads per output; else 0 */
+  int rows;       /* streaming head kernels: output rows per wave (the compiled R); else 0 */
+  int hd_ks, hd_r2, hd_co, hd_px; /* LDS-staged head kernels: kernel size (both), and of head_dgrad_kernel<KS, R2, CO, PX> the rest */
+  int split_out;  /* nq_conv_split_out of this call */
+  int64_t ws_floats; /* nq_conv_forward_ws_floats of the shape: what ws must hold whatever the epilogue */
+} nq_conv_plan;
+NQ_API int nq_conv_forward_plan(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int has_bias, nq_conv_plan* out);
 
 /* ---- "bf16x3" variant of nq_conv_forward: fp32-equivalent accuracy on the BF16 matrix pipe ------------------------
  * Every fp32 operand is split into bf16 hi + lo and each product formed as hi*hi + hi*lo + lo*hi with fp32
@@ -375,6 +400,21 @@ typedef struct nq_wgr_seg {
 NQ_API int64_t nq_conv_wgrad_ws_floats(int B, int Cin, int H, int W, int Cout, int k);
 NQ_API int nq_conv_wgrad(const float* x, const float* dy, float* dw, float* db, float* ws, int B, int Cin, int H, int W, int Cout,
                   int k, nq_wgr_seg* seg, nq_stream_t stream);
+/* The launch plan nq_conv_wgrad will use for this shape (additive to ABI v7; pure host function; the launch and
+ * nq_conv_wgrad_ws_floats read the same resolution, route_wgrad in csrc/conv.hip).  NQ_ERR_INVALID for a non-positive size or
+ * out == NULL, NQ_ERR_UNSUPPORTED for k outside {1,3,5}. */
+#define NQ_CONV_WGRAD_MFMA 1 /* conv_wgrad<mi, ni>: 16*mi channels x 64*ni columns per workgroup, K split over nsplit workgroups */
+#define NQ_CONV_WGRAD_TINY 2 /* tiny_pw_wgrad: 1x1 over <= 256 pixels, a thread per weight, writes dw / db itself */
+typedef struct nq_conv_wgrad_plan_t {
+  int kernel;     /* NQ_CONV_WGRAD_* */
+  int mi, ni;     /* the build; 0 for the tiny kernel, like the next five */
+  int co_pad, n_pad; /* slab dimensions: Cout and Cin*k*k rounded up to whole tiles */
+  int nsplit;     /* K splits = slabs */
+  int nseg;       /* 32-pixel row segments the splits divide among themselves */
+  int tiny_px8;   /* tiny: 1 where H*W % 8 == 0 (its eight-pixel loop); else 0 */
+  int64_t ws_floats; /* nq_conv_wgrad_ws_floats */
+} nq_conv_wgrad_plan_t;
+NQ_API int nq_conv_wgrad_plan(int B, int Cin, int H, int W, int Cout, int k, nq_conv_wgrad_plan_t* out);
 
 /* bf16x3 variant of nq_conv_wgrad, k in {3,5}: */
 NQ_API int nq_conv_wgrad3_supported(int B, int Cin, int H, int W, int Cout, int k);

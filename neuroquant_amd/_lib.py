@@ -60,6 +60,17 @@ class Conv3Plan(Structure):
                                      "per_split", "tail", "lds_bytes", "lds_bytes_dgrad")]
 
 
+class ConvPlan(Structure):
+    """nq_conv_plan (include/nq_hip.h): what nq_conv_forward launches for a call."""
+    _fields_ = [(n, c_int) for n in ("kernel", "mi", "ncg", "nsplit", "finish", "ksl", "rows", "hd_ks", "hd_r2", "hd_co", "hd_px",
+                                     "split_out")] + [("ws_floats", c_int64)]
+
+
+class ConvWgradPlan(Structure):
+    """nq_conv_wgrad_plan_t (include/nq_hip.h): what nq_conv_wgrad launches for a shape."""
+    _fields_ = [(n, c_int) for n in ("kernel", "mi", "ni", "co_pad", "n_pad", "nsplit", "nseg", "tiny_px8")] + [("ws_floats", c_int64)]
+
+
 class FqFwhtSeg(Structure):
     """nq_fq_fwht_seg (include/nq_hip.h): one tensor of a launch that fuses the AdaRound fake-quant with the Hadamard transform."""
     _fields_ = [("x", c_void_p), ("alpha", c_void_p), ("delta", c_void_p), ("zp", c_void_p), ("m", c_void_p), ("v", c_void_p),
@@ -123,6 +134,7 @@ def _load():
     sig("nq_conv_operand_dims", I, I, I, I, POINTER(c_int), POINTER(c_int))
     sig("nq_conv_forward_ws_floats", L, I, I, I, I, I, I)
     sig("nq_conv_forward", I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, P)
+    sig("nq_conv_forward_plan", I, I, I, I, I, I, I, I, I, I, POINTER(ConvPlan))
     sig("nq_conv3_supported", I, I, I, I, I, I, I)
     sig("nq_conv3_split_io", I, I, I, I, I, I, I)
     sig("nq_conv_split_out", I, I, I, I, I, I, I, I, I, I)
@@ -150,6 +162,7 @@ def _load():
     sig("nq_wgrad_reduce_multi", I, POINTER(WgrSeg), I, P)
     sig("nq_conv_wgrad_ws_floats", L, I, I, I, I, I, I)
     sig("nq_conv_wgrad", I, P, P, P, P, P, I, I, I, I, I, I, POINTER(WgrSeg), P)
+    sig("nq_conv_wgrad_plan", I, I, I, I, I, I, I, POINTER(ConvWgradPlan))
     sig("nq_ps_gelu_backward", I, P, P, P, I, I, I, I, I, P)
     sig("nq_tanh_out_backward", I, P, P, P, L, P)
     sig("nq_l2_loss", I, P, P, P, P, P, L, L, F, P)
@@ -196,6 +209,7 @@ EXPORTS = (
     "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",
     "nq_conv3_levels_supported", "nq_conv_forward3_levels",
     "nq_weight_layout3_f16", "nq_conv_forward3_levels_f16",
+    "nq_conv_forward_plan", "nq_conv_wgrad_plan",
 )
 
 _lib = None

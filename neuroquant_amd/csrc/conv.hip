@@ -7,6 +7,7 @@
 
 extern "C" {
 int nq_tiny_pw_supported(int B, int Cin, int H, int W, int Cout, int k);
+int nq_tiny_pw_ksl(int Cin);
 int nq_tiny_pw_forward(const float* x, const float* wt, const float* bias, float* y, float* z, const float* zprev, int B,
                        int Cin, int H, int W, int Cout, int ld, int r, int epi, hipStream_t st);
 int nq_tiny_pw_wgrad(const float* x, const float* dy, float* dw, float* db, int B, int Cin, int H, int W, int Cout,
@@ -22,10 +23,12 @@ int nq_conv_igemm_k5(const float*, const float*, const float*, float*, float*, i
                      int, float*, const float*, hipStream_t);
 int nq_conv_splitk_finish(const float*, const float*, float*, float*, const float*, int, int, int, int, int, int, int,
                           hipStream_t);
+int nq_conv_splitk_finish_sg(int64_t, int);
 int nq_head_supported(int, int);
+int nq_head_forward_route(int, int, int, int, int, int, int, int*);
+int nq_head_dgrad_route(int, int, int, int, int, int, int, int, int*, int*, int*, int*);
 int nq_head_forward(const float*, const float*, int, const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 int nq_head_dgrad(const float*, const float*, int, const float*, float*, int, int, int, int, int, int, int, int, hipStream_t);
-int nq_head_dgrad_streams(int, int, int, int, int, int, int, int);
 int nq_conv_wgrad_k1(const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int, int,
                      hipStream_t);
 int nq_conv_wgrad_k3(const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int, int,
@@ -76,12 +79,10 @@ inline bool use_head_dgrad(int Cin, int k, int epi, bool has_bias) {
 
 inline int wgrad_ni(int mi, int k) { return k == 1 ? 2 : (mi <= 3 ? 6 : (mi <= 6 ? 4 : 3)); }
 
-struct WgradPlan {
-  int mi, ni, co_pad, n_pad, nsplit;
-};
-
-inline WgradPlan plan_wgrad(int B, int Cin, int H, int W, int Cout, int k) {
-  WgradPlan p{};
+// ONE resolution of a weight-gradient shape: nq_conv_wgrad, nq_conv_wgrad_ws_floats and nq_conv_wgrad_plan read it.  The slab
+// dimensions are resolved for the tiny shapes too: their workspace keeps its size although tiny_pw_wgrad never writes it.
+inline nq_conv_wgrad_plan_t route_wgrad(int B, int Cin, int H, int W, int Cout, int k) {
+  nq_conv_wgrad_plan_t p{};
   int64_t best_cost = INT64_MAX;
   const int N = Cin * k * k;
   for (int mi : kMiOptions) {
@@ -107,7 +108,80 @@ inline WgradPlan plan_wgrad(int B, int Cin, int H, int W, int Cout, int k) {
   if (ns > 256) ns = 256;
   if (ns < 1) ns = 1;
   p.nsplit = ns;
+  p.nseg = nseg;
+  p.ws_floats = (int64_t)p.nsplit * p.co_pad * ((int64_t)p.n_pad + 1);
+  p.kernel = NQ_CONV_WGRAD_MFMA;
+  if (nq_tiny_pw_supported(B, Cin, H, W, Cout, k)) {
+    p.kernel = NQ_CONV_WGRAD_TINY;
+    p.mi = p.ni = p.co_pad = p.n_pad = p.nsplit = p.nseg = 0;
+    p.tiny_px8 = ((int64_t)H * W) % 8 == 0;
+  }
   return p;
+}
+
+// The implicit-GEMM side of a forward shape, whatever the epilogue: tile, K-loop groups, split, workspace.  A shape the tiny kernel
+// owns never reaches the implicit-GEMM kernel (the head kernels come before it, nothing after): no workspace.
+struct FwdShape {
+  int tiny, mi, ncg, nsplit;
+  int64_t ws_floats;
+};
+inline FwdShape route_fwd_shape(int B, int Cin, int H, int W, int Cout, int k) {
+  FwdShape s{};
+  s.tiny = nq_tiny_pw_supported(B, Cin, H, W, Cout, k);
+  s.mi = pick_mi_fwd(Cout);
+  s.ncg = (Cin + ci_per_slice(k) - 1) / ci_per_slice(k);
+  s.nsplit = pick_nsplit(B, Cin, H, W, Cout, k);
+  s.ws_floats = (!s.tiny && s.nsplit > 1) ? (int64_t)s.nsplit * B * Cout * H * W : 0;
+  return s;
+}
+
+// ONE resolution of a forward call (sizes and epilogue already validated): nq_conv_forward, nq_conv_forward_plan and
+// nq_conv_split_out read it.  NQ_ERR_UNSUPPORTED where a head knob names a build that is not compiled.
+inline int route_fwd(int B, int Cin, int H, int W, int Cout, int k, int ld, int r, int epi, bool has_bias, nq_conv_plan& p) {
+  p = nq_conv_plan{};
+  const FwdShape s = route_fwd_shape(B, Cin, H, W, Cout, k);
+  p.ws_floats = s.ws_floats;
+  // <= 4 output channels (the decoder head) / <= 4 input channels (its data gradient): HBM-bound vector kernels
+  if (use_head_fwd(Cout, k, epi)) {
+    const int route = nq_head_forward_route(B, Cin, H, W, Cout, k, ld, &p.rows);
+    if (route < 0) return NQ_ERR_UNSUPPORTED;
+    p.kernel = route ? NQ_CONV_HEAD_FWD : NQ_CONV_HEAD_FWD_LDS;
+    if (!route) p.hd_ks = k;
+    return NQ_OK;
+  }
+  if (use_head_dgrad(Cin, k, epi, has_bias)) {
+    const bool gelu = epi == NQ_EPI_DGRAD_GELU;
+    const int route = nq_head_dgrad_route(B, Cout, H, W, Cin, k, gelu ? r : 1, gelu, &p.rows, &p.hd_r2, &p.hd_co, &p.hd_px);
+    if (route < 0) return NQ_ERR_UNSUPPORTED;
+    p.kernel = route ? NQ_CONV_HEAD_DGRAD : NQ_CONV_HEAD_DGRAD_LDS;
+    p.split_out = route;
+    if (!route) p.hd_ks = k;
+    return NQ_OK;
+  }
+  // 1x1 convolutions over a handful of pixels (decoder stem / first block): compact thread-per-output kernel
+  if (s.tiny) {
+    p.kernel = NQ_CONV_TINY;
+    p.ksl = nq_tiny_pw_ksl(Cin);
+    return NQ_OK;
+  }
+  p.kernel = NQ_CONV_IGEMM;
+  p.mi = s.mi;
+  p.ncg = s.ncg;
+  p.nsplit = s.nsplit;
+  p.finish = s.nsplit > 1 ? nq_conv_splitk_finish_sg((int64_t)B * Cout * H * W, s.nsplit) : 0;
+  if ((int64_t)B * s.nsplit > 65535) return NQ_ERR_UNSUPPORTED;
+  return NQ_OK;
+}
+
+// the argument checks of nq_conv_forward that depend on values alone (no pointers); epilogue without the split-word bits
+inline int check_fwd_args(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue) {
+  if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
+  if (!ks_ok(k)) return NQ_ERR_UNSUPPORTED;
+  if (epilogue < 0 || epilogue > NQ_EPI_DGRAD_GELU) return NQ_ERR_INVALID;
+  if ((epilogue == NQ_EPI_PS_GELU || epilogue == NQ_EPI_PS) && (r <= 0 || Cout % (r * r) != 0)) return NQ_ERR_INVALID;
+  if (epilogue == NQ_EPI_DGRAD_GELU && (r <= 0 || H % r != 0 || W % r != 0)) return NQ_ERR_INVALID;
+  if (B > 65535) return NQ_ERR_UNSUPPORTED;
+  return NQ_OK;
 }
 
 __global__ __launch_bounds__(256) void weight_fwd_layout_kernel(const float* __restrict__ w, float* __restrict__ wt,
@@ -210,16 +284,21 @@ int nq_weight_layouts_multi(const nq_wl_seg* segs, int nseg, nq_stream_t stream)
 
 int64_t nq_conv_forward_ws_floats(int B, int Cin, int H, int W, int Cout, int k) {
   if (!ks_ok(k) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  if (nq_head_supported(Cout, k) || nq_head_supported(Cin, k)) return 0;
-  int ns = pick_nsplit(B, Cin, H, W, Cout, k);
-  return ns > 1 ? (int64_t)ns * B * Cout * H * W : 0;
+  return route_fwd_shape(B, Cin, H, W, Cout, k).ws_floats;
 }
 
 // 1 when nq_conv_forward can write its output y as split {hi | lo} words for this call (include/nq_hip.h)
 int nq_conv_split_out(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int has_bias) {
-  if (!ks_ok(k) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  if (use_head_fwd(Cout, k, epilogue) || !use_head_dgrad(Cin, k, epilogue, has_bias != 0)) return 0;
-  return nq_head_dgrad_streams(B, Cout, H, W, Cin, k, epilogue == NQ_EPI_DGRAD_GELU ? r : 1, epilogue == NQ_EPI_DGRAD_GELU);
+  nq_conv_plan p;
+  if (check_fwd_args(B, Cin, H, W, Cout, k, r, epilogue) != NQ_OK) return 0;
+  if (route_fwd(B, Cin, H, W, Cout, k, 0, r, epilogue, has_bias != 0, p) != NQ_OK) return 0;
+  return p.split_out;
+}
+
+int nq_conv_forward_plan(int B, int Cin, int H, int W, int Cout, int k, int r, int epilogue, int has_bias, nq_conv_plan* out) {
+  if (!out) return NQ_ERR_INVALID;
+  if (int rc = check_fwd_args(B, Cin, H, W, Cout, k, r, epilogue)) return rc;
+  return route_fwd(B, Cin, H, W, Cout, k, 0, r, epilogue, has_bias != 0, *out);
 }
 
 int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y, float* z, float* ws, int B, int Cin, int H,
@@ -233,27 +312,27 @@ int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y
   epilogue &= ~NQ_EPI_Y_SPLIT;
   if (y_split && !nq_conv_split_out(B, Cin, H, W, Cout, k, r, epilogue, bias != nullptr)) return NQ_ERR_UNSUPPORTED;
   if (epilogue < 0 || epilogue > NQ_EPI_DGRAD_GELU) return NQ_ERR_INVALID;
-  if ((epilogue == NQ_EPI_PS_GELU || epilogue == NQ_EPI_PS) && (!z || r <= 0 || Cout % (r * r) != 0)) return NQ_ERR_INVALID;
-  if (epilogue == NQ_EPI_DGRAD_GELU && (!zprev || r <= 0 || H % r != 0 || W % r != 0)) return NQ_ERR_INVALID;
+  if ((epilogue == NQ_EPI_PS_GELU || epilogue == NQ_EPI_PS) && !z) return NQ_ERR_INVALID;
+  if (epilogue == NQ_EPI_DGRAD_GELU && !zprev) return NQ_ERR_INVALID;
   int need_rows, need_ld;
   nq_conv_operand_dims(Cin, Cout, k, &need_rows, &need_ld);
   if (krows < need_rows || ld < need_ld || (ld & 3)) return NQ_ERR_INVALID;
-  if (B > 65535) return NQ_ERR_UNSUPPORTED;
-  hipStream_t st0 = nq_s(stream);
-  // <= 4 output channels (the decoder head) / <= 4 input channels (its data gradient): HBM-bound vector kernels
-  if (use_head_fwd(Cout, k, epilogue))
-    return nq_head_forward(x, wt, ld, bias, y, B, Cin, H, W, Cout, k, epilogue, st0);
-  if (use_head_dgrad(Cin, k, epilogue, bias != nullptr))
-    return nq_head_dgrad(x, wt, ld, epilogue == NQ_EPI_DGRAD_GELU ? zprev : nullptr, y, B, Cout, H, W, Cin, k,
-                         epilogue == NQ_EPI_DGRAD_GELU ? r : 1, y_split, st0);
-  // 1x1 convolutions over a handful of pixels (decoder stem / first block): compact thread-per-output kernel
-  if (nq_tiny_pw_supported(B, Cin, H, W, Cout, k))
-    return nq_tiny_pw_forward(x, wt, bias, y, z, zprev, B, Cin, H, W, Cout, ld, r, epilogue, st0);
-  const int mi = pick_mi_fwd(Cout);
-  const int ns = pick_nsplit(B, Cin, H, W, Cout, k);
-  if (ns > 1 && !ws) return NQ_ERR_INVALID;
-  if ((int64_t)B * ns > 65535) return NQ_ERR_UNSUPPORTED;
+  if (int rc = check_fwd_args(B, Cin, H, W, Cout, k, r, epilogue)) return rc;
+  nq_conv_plan p;
+  if (int rc = route_fwd(B, Cin, H, W, Cout, k, ld, r, epilogue, bias != nullptr, p)) return rc;
   hipStream_t st = nq_s(stream);
+  switch (p.kernel) {
+    case NQ_CONV_HEAD_FWD:
+    case NQ_CONV_HEAD_FWD_LDS: return nq_head_forward(x, wt, ld, bias, y, B, Cin, H, W, Cout, k, epilogue, st);
+    case NQ_CONV_HEAD_DGRAD:
+    case NQ_CONV_HEAD_DGRAD_LDS:
+      return nq_head_dgrad(x, wt, ld, epilogue == NQ_EPI_DGRAD_GELU ? zprev : nullptr, y, B, Cout, H, W, Cin, k,
+                           epilogue == NQ_EPI_DGRAD_GELU ? r : 1, y_split, st);
+    case NQ_CONV_TINY: return nq_tiny_pw_forward(x, wt, bias, y, z, zprev, B, Cin, H, W, Cout, ld, r, epilogue, st);
+    default: break;
+  }
+  const int mi = p.mi, ns = p.nsplit;
+  if (ns > 1 && !ws) return NQ_ERR_INVALID;
   int rc;
   switch (k) {
     case 1: rc = nq_conv_igemm_k1(x, wt, bias, y, z, B, Cin, H, W, Cout, ld, r, epilogue, mi, ns, ws, zprev, st); break;
@@ -266,8 +345,14 @@ int nq_conv_forward(const float* x, const float* wt, const float* bias, float* y
 
 int64_t nq_conv_wgrad_ws_floats(int B, int Cin, int H, int W, int Cout, int k) {
   if (!ks_ok(k) || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  WgradPlan p = plan_wgrad(B, Cin, H, W, Cout, k);
-  return (int64_t)p.nsplit * p.co_pad * ((int64_t)p.n_pad + 1);
+  return route_wgrad(B, Cin, H, W, Cout, k).ws_floats;
+}
+
+int nq_conv_wgrad_plan(int B, int Cin, int H, int W, int Cout, int k, nq_conv_wgrad_plan_t* out) {
+  if (!out || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
+  if (!ks_ok(k)) return NQ_ERR_UNSUPPORTED;
+  *out = route_wgrad(B, Cin, H, W, Cout, k);
+  return NQ_OK;
 }
 
 // seg == NULL: split kernel + reduction; seg != NULL: the split kernel only, *seg describes the pending reduction
@@ -276,9 +361,8 @@ int nq_conv_wgrad(const float* x, const float* dy, float* dw, float* db, float* 
   if (!x || !dy || !dw || !ws || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return NQ_ERR_INVALID;
   if (!ks_ok(k)) return NQ_ERR_UNSUPPORTED;
   if (seg) *seg = nq_wgr_seg{nullptr, nullptr, dw, db, Cout, Cin * k * k, 0, 0, 0, 0, 1};
-  if (nq_tiny_pw_supported(B, Cin, H, W, Cout, k))
-    return nq_tiny_pw_wgrad(x, dy, dw, db, B, Cin, H, W, Cout, nq_s(stream));
-  WgradPlan p = plan_wgrad(B, Cin, H, W, Cout, k);
+  const nq_conv_wgrad_plan_t p = route_wgrad(B, Cin, H, W, Cout, k);
+  if (p.kernel == NQ_CONV_WGRAD_TINY) return nq_tiny_pw_wgrad(x, dy, dw, db, B, Cin, H, W, Cout, nq_s(stream));
   float* slab = ws;
   float* slab_db = ws + (int64_t)p.nsplit * p.co_pad * p.n_pad;
   hipStream_t st = nq_s(stream);

@@ -691,15 +691,27 @@ extern "C" {
 // Selection rule shared with conv.hip: the vector path serves C_out <= 4.
 int nq_head_supported(int Cout, int k) { return Cout <= MAXCO && (k == 1 || k == 3 || k == 5); }
 
-int nq_head_forward(const float* x, const float* wt, int ld, const float* bias, float* y, int B, int Cin, int H, int W,
-                    int Cout, int k, int epi, hipStream_t st) {
-  // 3x3 heads with whole 16-byte quads per row and a tensor below 4 GiB (32-bit buffer offsets): the streaming kernel
+// ONE resolution of a head forward call, read by the launch below and by nq_conv_forward_plan (conv.hip): 1 the streaming kernel
+// with *rows output rows per wave, 0 the LDS-staged kernel, -1 NQ_HEAD_RD names a value that is not compiled.
+// 3x3 heads with whole 16-byte quads per row and a tensor below 4 GiB (32-bit buffer offsets) stream.
+int nq_head_forward_route(int B, int Cin, int H, int W, int Cout, int k, int ld, int* rows) {
   const char* hv = getenv("NQ_HEAD_FWD");   // NQ_HEAD_FWD=1: the LDS-staged kernel (A/B runs; read per call)
   const bool v1 = hv && hv[0] == '1';
-  if (k == 3 && Cout == 3 && (W & 3) == 0 && (ld & 3) == 0 && (int64_t)B * Cin * H * W * 4 < 0xFFFFFF00ll && !v1) {
-    // R output rows per wave; NQ_HEAD_RD=r picks another compiled value (timing runs)
-    int R = 4;
-    if (const char* rd = getenv("NQ_HEAD_RD")) R = atoi(rd);
+  *rows = 0;
+  if (!(k == 3 && Cout == 3 && (W & 3) == 0 && (ld & 3) == 0 && (int64_t)B * Cin * H * W * 4 < 0xFFFFFF00ll && !v1)) return 0;
+  // R output rows per wave; NQ_HEAD_RD=r picks another compiled value (timing runs)
+  int R = 4;
+  if (const char* rd = getenv("NQ_HEAD_RD")) R = atoi(rd);
+  *rows = R;
+  return (R == 4 || R == 5) ? 1 : -1;
+}
+
+int nq_head_forward(const float* x, const float* wt, int ld, const float* bias, float* y, int B, int Cin, int H, int W,
+                    int Cout, int k, int epi, hipStream_t st) {
+  int R;
+  const int route = nq_head_forward_route(B, Cin, H, W, Cout, k, ld, &R);
+  if (route < 0) return NQ_ERR_UNSUPPORTED;
+  if (route == 1) {
     HeadFwd2Args a;
     a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.ld = ld;
     a.strips = (W + 255) / 256; a.rblocks = (H + R - 1) / R;
@@ -759,24 +771,39 @@ int nq_head_forward_loss(const float* x, const float* wt, int ld, const float* b
 }
 
 // dy (B,Cout,H,W) -> out = d/dx (B,Cin,H,W) [* gelu'(zprev)] stored PixelUnshuffle(r)-ed
+// ONE resolution of a head data-gradient call, read by the launch below, nq_conv_split_out and nq_conv_forward_plan (conv.hip):
+// 1 the streaming kernel with *rows rows per wave, -1 NQ_HEAD_DG_R names a value that is not compiled, 0 the LDS-staged kernel
+// head_dgrad_kernel<k, *r2, *co, *px>.  The shipped head (3x3, 3 image channels, GELU + PixelShuffle(2) below it) streams; 32-bit
+// buffer offsets; its weights (Cin x 28 floats) must fit 64 KiB of LDS.
+int nq_head_dgrad_route(int B, int Cin, int H, int W, int Cout, int k, int r, int has_z, int* rows, int* r2, int* co, int* px) {
+  const char* hv = getenv("NQ_HEAD_DGRAD");   // NQ_HEAD_DGRAD=1: the LDS-staged kernel (A/B runs; read per call)
+  *rows = *r2 = *co = *px = 0;
+  if (k == 3 && Cout == 3 && r == 2 && has_z && (W % 4 == 0) && (H % 2 == 0) && (int64_t)B * Cin * H * W * 4 < 0xFFFFFF00ll &&
+      !(hv && hv[0] == '1') && (size_t)Cin * 28 * 4 <= 64 * 1024) {
+    int R = 4;
+    if (const char* rd = getenv("NQ_HEAD_DG_R")) R = atoi(rd);
+    *rows = R;
+    return (R == 2 || R == 4) ? 1 : -1;
+  }
+  // r == 2 fast path: 8 pixels per thread (tile 32 x 64) when W % 8 == 0 and k <= 3, else 4 (tile 16 x 64)
+  *r2 = (r == 2) && (W % 4 == 0) && (H % 2 == 0);
+  *px = (*r2 && (W % 8 == 0) && k <= 3) ? 8 : 4;
+  *co = Cout <= 3 ? 3 : 4;
+  return 0;
+}
+
 // 1 when nq_head_dgrad runs the streaming kernel for this call (the only one that can write split {hi | lo} words)
 int nq_head_dgrad_streams(int B, int Cin, int H, int W, int Cout, int k, int r, int has_z) {
-  const char* hv = getenv("NQ_HEAD_DGRAD");
-  const char* rd = getenv("NQ_HEAD_DG_R");
-  const int R = rd ? atoi(rd) : 4;
-  return k == 3 && Cout == 3 && r == 2 && has_z && (W % 4 == 0) && (H % 2 == 0) && (int64_t)B * Cin * H * W * 4 < 0xFFFFFF00ll &&
-         !(hv && hv[0] == '1') && (size_t)Cin * 28 * 4 <= 64 * 1024 && (R == 2 || R == 4);
+  int rows, r2, co, px;
+  return nq_head_dgrad_route(B, Cin, H, W, Cout, k, r, has_z, &rows, &r2, &co, &px) == 1;
 }
 
 int nq_head_dgrad(const float* dy, const float* wt, int ld, const float* zprev, float* out, int B, int Cin, int H, int W,
                   int Cout, int k, int r, int out_split, hipStream_t st) {
-  if (out_split && !nq_head_dgrad_streams(B, Cin, H, W, Cout, k, r, zprev != nullptr)) return NQ_ERR_UNSUPPORTED;
-  // the shipped head (3x3, 3 image channels, GELU + PixelShuffle(2) below it): the streaming kernel; 32-bit buffer offsets
-  const char* hv = getenv("NQ_HEAD_DGRAD");   // NQ_HEAD_DGRAD=1: the LDS-staged kernel (A/B runs; read per call)
-  if (k == 3 && Cout == 3 && r == 2 && zprev && (W % 4 == 0) && (H % 2 == 0) && (int64_t)B * Cin * H * W * 4 < 0xFFFFFF00ll &&
-      !(hv && hv[0] == '1')) {
-    int R = 4;
-    if (const char* rd = getenv("NQ_HEAD_DG_R")) R = atoi(rd);
+  int R, r2_, co_, px_;
+  const int route = nq_head_dgrad_route(B, Cin, H, W, Cout, k, r, zprev != nullptr, &R, &r2_, &co_, &px_);
+  if (route < 0 || (out_split && route != 1)) return NQ_ERR_UNSUPPORTED;
+  if (route == 1) {
     HeadDg2Args a;
     a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.ld = ld;
     a.strips = (W + 255) / 256; a.rblocks = (H + R - 1) / R;
@@ -786,22 +813,17 @@ int nq_head_dgrad(const float* dy, const float* wt, int ld, const float* zprev, 
     const int waves = B * a.strips * a.rblocks;
     dim3 g2((unsigned)((waves + 3) / 4)), blk2(256);
     const size_t lds = (size_t)Cin * 28 * 4;
-    if (lds <= 64 * 1024) {
-      if (R == 2) hipLaunchKernelGGL((head_dgrad2_kernel<2, 3>), g2, blk2, lds, st, dy, wt, zprev, out, a);
-      else if (R == 4) hipLaunchKernelGGL((head_dgrad2_kernel<4, 3>), g2, blk2, lds, st, dy, wt, zprev, out, a);
-      else return NQ_ERR_UNSUPPORTED;
-      return nq_launch_status();
-    }
+    if (R == 2) hipLaunchKernelGGL((head_dgrad2_kernel<2, 3>), g2, blk2, lds, st, dy, wt, zprev, out, a);
+    else hipLaunchKernelGGL((head_dgrad2_kernel<4, 3>), g2, blk2, lds, st, dy, wt, zprev, out, a);
+    return nq_launch_status();
   }
-  // r == 2 fast path: 8 pixels per thread (tile 32 x 64) when W % 8 == 0 and k <= 3, else 4 (tile 16 x 64)
-  const bool r2 = (r == 2) && (W % 4 == 0) && (H % 2 == 0);
-  const bool px8 = r2 && (W % 8 == 0) && k <= 3;
+  const bool r2 = r2_ != 0, px8 = px_ == 8;
   const int th = px8 ? 32 : 16;
   const int tiles_x = (W + 63) / 64, tiles = tiles_x * ((H + th - 1) / th);
   dim3 g((unsigned)(tiles * B)), blk(256);
 #define NQ_HD(KS_, R2_, PX_)                                                                                          \
   do {                                                                                                                \
-    if (Cout <= 3)                                                                                                    \
+    if (co_ == 3)                                                                                                     \
       hipLaunchKernelGGL((head_dgrad_kernel<KS_, R2_, 3, PX_>), g, blk, 0, st, dy, wt, ld, zprev, out, Cin, H, W, Cout, r, \
                          tiles_x);                                                                                    \
     else                                                                                                              \

@@ -431,13 +431,17 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(ConvArgs a) {
   }
 }
 
+// build of the finish kernel for `total` outputs behind nsplit slabs (8: small outputs with many slabs); read by the launch below and
+// by nq_conv_forward_plan (conv.hip)
+extern "C" int nq_conv_splitk_finish_sg(int64_t total, int nsplit) { return (total < 131072 && nsplit >= 16) ? 8 : 1; }
+
 extern "C" int nq_conv_splitk_finish(const float* slab, const float* bias, float* y, float* z, const float* zprev, int B,
                                      int H, int W, int Cout, int r, int epi, int nsplit, hipStream_t st) {
   ConvArgs a{};
   a.slab = const_cast<float*>(slab); a.bias = bias; a.y = y; a.z = z; a.zprev = zprev;
   a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.r = r; a.epi = epi; a.nsplit = nsplit;
   int64_t total = (int64_t)B * Cout * H * W;
-  if (total < 131072 && nsplit >= 16)
+  if (nq_conv_splitk_finish_sg(total, nsplit) == 8)
     hipLaunchKernelGGL(conv_splitk_finish_kernel<8>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(conv_splitk_finish_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
