@@ -546,6 +546,39 @@ NQ_API int nq_unpack_dequant(const uint32_t* words, const float* delta, const fl
                       int n_bits, nq_stream_t stream);
 NQ_API int nq_frames_to_u8(const float* src, uint8_t* dst, int64_t n, int C, int64_t HW, int layout, nq_stream_t stream);
 
+/* ---- 8-bit YUV 4:2:0 frames (additive: nq_abi_version() stays 7) ----
+ * A frame is I420: the Y plane H x W, then U (H/2) x (W/2), then V, one byte per sample: the payload of a .y4m / .yuv frame.
+ * matrix 0 is BT.601 (Kr = 0.299, Kb = 0.114), 1 is BT.709 (Kr = 0.2126, Kb = 0.0722); Kg = 1 - Kr - Kb.  full_range 0 is
+ * limited ("video") range, Y in 16..235 and chroma in 16..240; 1 is full range.  All arithmetic is fp32 in the order written
+ * here, uncontracted; every derived constant (icb = 1/(2(1-Kb)), icr = 1/(2(1-Kr)), c_r = 2(1-Kr), c_b = 2(1-Kb),
+ * c_gb = Kb c_b / Kg, c_gr = Kr c_r / Kg, 1/219, 1/224, 1/255) is formed in double and rounded once to float.
+ *   nq_yuv420_frame_bytes  H * W * 3 / 2; 0 for non-positive or odd H or W and for a product past int64.  Pure host function.
+ *   nq_frames_to_yuv420    src: (n, 3, H, W) fp32 planar RGB; dst: n frames.  Per pixel NaN -> 0, then clamp to [0, 1] (the rule
+ *                          of nq_frames_to_u8); y = (Kr r + Kg g) + Kb b; cb = (b - y) icb; cr = (r - y) icr.  The chroma of a
+ *                          2 x 2 block is ((c00 + c01) + (c10 + c11)) * 0.25, row 0 first, left before right.  Limited range:
+ *                          Y = rint(16 + 219 y), U = rint(128 + 224 cb), V likewise from cr; full range: Y = rint(255 y),
+ *                          U = rint(128 + 255 cb).  Product, then sum, then round to nearest even, then clamp to [0, 255].
+ *                          With W % 8 == 0, src 16-byte and dst 8-byte aligned a thread takes 2 rows x 8 columns (16-byte
+ *                          loads, 8-byte Y stores, dword chroma stores); otherwise one thread per 2 x 2 block, scalar loads,
+ *                          byte stores.  Every byte has one writer: bit-identical from call to call.
+ *   nq_yuv420_to_rgb_u8    the inverse, for ground truth: src n frames (any byte is legal), dst uint8 (n, 3, H, W) planar.  Each
+ *                          chroma sample serves its 2 x 2 block.  Limited range: y = (Y - 16) (1/219), cb = (U - 128) (1/224);
+ *                          full range: y = Y (1/255), cb = (U - 128) (1/255); cr from V as cb from U.  r = y + c_r cr;
+ *                          b = y + c_b cb; g = (y - c_gb cb) - c_gr cr; code = rint(min(max(., 0), 1) * 255).  Vector path
+ *                          with W % 8 == 0 and both pointers 8-byte aligned.
+ *   nq_yuv420_sse          a, b: n frames each; sse: uint64 (n, 3), the exact sum of squared code differences per frame and
+ *                          plane (Y, U, V).  The entry zeroes sse on the stream; workgroups reduce in registers and LDS and
+ *                          add one 64-bit partial per plane with a global atomic add.  Integer sums do not depend on the
+ *                          order: bit-identical from call to call.  sse is 8-byte aligned.
+ * NQ_ERR_INVALID, before the device is touched, for null pointers, n <= 0, non-positive or odd H or W, matrix or full_range
+ * outside {0, 1} and n * H * W * 3 past int64; NQ_ERR_UNSUPPORTED for more than 2^31 - 1 workgroups. */
+NQ_API int64_t nq_yuv420_frame_bytes(int64_t H, int64_t W);
+NQ_API int nq_frames_to_yuv420(const float* src, uint8_t* dst, int64_t n, int H, int W, int matrix, int full_range,
+                        nq_stream_t stream);
+NQ_API int nq_yuv420_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t n, int H, int W, int matrix, int full_range,
+                        nq_stream_t stream);
+NQ_API int nq_yuv420_sse(const uint8_t* a, const uint8_t* b, uint64_t* sse, int64_t n, int H, int W, nq_stream_t stream);
+
 /* Entropy-coded levels: 64-lane interleaved rANS, one frequency table per tensor (probabilities in units of
  * 1 / 4096), 32-bit states >= 2^16, 16-bit words.  The n levels (flat, C order) are cut into chunks of `chunk` symbols (a
  * multiple of 64, the last may be short); lane l of a chunk owns its symbols l, l + 64, ...  One wavefront decodes one chunk.

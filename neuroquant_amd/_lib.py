@@ -183,6 +183,10 @@ def _load():
     sig("nq_pack_levels", I, P, P, L, I, P)
     sig("nq_unpack_dequant", I, P, P, P, P, L, L, I, P)
     sig("nq_frames_to_u8", I, P, P, L, I, L, I, P)
+    sig("nq_yuv420_frame_bytes", L, L, L)
+    sig("nq_frames_to_yuv420", I, P, P, L, I, I, I, I, P)
+    sig("nq_yuv420_to_rgb_u8", I, P, P, L, I, I, I, I, P)
+    sig("nq_yuv420_sse", I, P, P, P, L, I, I, P)
     sig("nq_rans_chunks", L, L, L)
     sig("nq_rans_decode", I, P, P, P, P, L, I, L, P, P, L, P, P, P)
     sig("nq_rows_dot_ws_bytes", L, I, L)
@@ -205,6 +209,7 @@ EXPORTS = (
     "nq_conv_wgrad3_split_io", "nq_head_forward_loss_ws_floats", "nq_head_forward_loss",
     "nq_adaround_fwht_multi", "nq_fwht_adaround_adam_multi", "nq_weight_layouts_all",
     "nq_packed_words", "nq_pack_levels", "nq_unpack_dequant", "nq_frames_to_u8",
+    "nq_yuv420_frame_bytes", "nq_frames_to_yuv420", "nq_yuv420_to_rgb_u8", "nq_yuv420_sse",
     "nq_rans_chunks", "nq_rans_decode",
     "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",
     "nq_conv3_levels_supported", "nq_conv_forward3_levels",

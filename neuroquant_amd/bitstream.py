@@ -478,14 +478,17 @@ class StreamDecoder:
         return self._sat is not None and bool(self._sat.item())
 
     @torch.no_grad()
-    def decode(self, indices, out="float", layout="chw"):
-        """frames `indices` (sequence or tensor of ints) -> (B, 3, H, W) fp32 in [0, 1] (`out='float'`) or uint8
-        (`out='u8'`; layout 'chw' or 'hwc').  One call is one batch: the batch size selects the kernels as it does in the
-        live model."""
-        if out not in ("float", "u8"):
-            raise ValueError(f"out must be 'float' or 'u8', got {out!r}")
-        if out == "float" and layout != "chw":
-            raise ValueError("float frames are planar; layout applies to out='u8'")
+    def decode(self, indices, out="float", layout="chw", matrix="bt709", full_range=False):
+        """frames `indices` (sequence or tensor of ints) -> (B, 3, H, W) fp32 in [0, 1] (`out='float'`), uint8
+        (`out='u8'`; layout 'chw' or 'hwc') or uint8 (B, H * W * 3 / 2) I420 video frames (`out='yuv420'`; `matrix` 'bt709' or
+        'bt601', `full_range`: converted from the float frame, so there is one rounding).  One call is one batch: the batch
+        size selects the kernels as it does in the live model."""
+        if out not in ("float", "u8", "yuv420"):
+            raise ValueError(f"out must be 'float', 'u8' or 'yuv420', got {out!r}")
+        if out != "u8" and layout != "chw":
+            raise ValueError("float and yuv420 frames are planar; layout applies to out='u8'")
+        if out == "yuv420" and matrix not in ops.YUV_MATRICES:   # before any launch
+            raise ValueError(f"matrix must be one of {sorted(ops.YUV_MATRICES)}, got {matrix!r}")
         idx = [int(i) for i in (indices.reshape(-1).tolist() if isinstance(indices, torch.Tensor) else indices)]
         if not idx or min(idx) < 0 or max(idx) >= self.frames:
             raise IndexError(f"frame indices must lie in [0, {self.frames})")
@@ -499,4 +502,6 @@ class StreamDecoder:
                 x = ops._space_from_channels(x, *self.fc_hw).contiguous()
         if taken is not None:
             self.levels_used[len(idx)] = taken
+        if out == "yuv420":
+            return ops.frames_to_yuv420(x, matrix, full_range)
         return x if out == "float" else ops.frames_to_u8(x, layout)

@@ -50,7 +50,7 @@ from ..quantization.quant_block import specials
 from ..quantization.quantizer import StraightThrough
 from ..utils import FrameCache, data_split, get_config, setup_logger
 from .. import ops
-from .calibrate_network import evaluate, load_frames, report_line
+from .calibrate_network import add_yuv_args, evaluate, load_frames, report_line
 
 # toy example (bit_assign.py:26-35)
 hnerv_candidate = {
@@ -512,6 +512,7 @@ def parse_args(argv):
     p.add_argument('-p', '--print-freq', default=50, type=int)
     p.add_argument('--data_path', type=str)
     p.add_argument('--synthetic', type=int, default=0, help='use N synthetic frames instead of --data_path')
+    add_yuv_args(p)
     p.add_argument('--vid', type=str, default='Bunny')
     p.add_argument('--data_split', type=str, default='1_1_1')
     p.add_argument('--batch_size', default=12, type=int)

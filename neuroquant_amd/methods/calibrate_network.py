@@ -10,9 +10,11 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
         --ckpt epoch300.pth --batch_size 2 --channel_wise --init max --iters_w 21000 --weight 0.01 --b_start 20 \
         --b_end 2 --warmup 0.2 --lr 0.003 --precision 6 5 4 5 5 6 6
     (--precision_file bits.json takes the bit-widths from `bit_assign --budget_bytes N --out bits.json`;
-    --synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --export_stream FILE.nqv also writes the
-    calibrated model as a bit stream that `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding
-    packed | rans | auto chooses between levels packed at their bit-width and entropy-coded levels)
+    --synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --data_path clip.y4m / clip.yuv reads an 8-bit
+    YUV 4:2:0 clip instead of a directory of PNGs (--yuv_size, --yuv_matrix, --yuv_range, --yuv_frames; DESIGN.md §16);
+    --export_stream FILE.nqv also writes the calibrated model as a bit stream that
+    `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
+    packed at their bit-width and entropy-coded levels)
 """
 import argparse
 import logging
@@ -40,6 +42,7 @@ def parse_args(argv):
     p.add_argument('-p', '--print-freq', default=50, type=int)
     p.add_argument('--data_path', type=str)
     p.add_argument('--synthetic', type=int, default=0, help='use N synthetic frames instead of --data_path')
+    add_yuv_args(p)
     p.add_argument('--vid', type=str, default='Bunny')
     p.add_argument('--data_split', type=str, default='1_1_1')
     p.add_argument('--batch_size', default=12, type=int)
@@ -113,11 +116,55 @@ def dist_setup():
     return rank, world, f'cuda:{local}'
 
 
+def add_yuv_args(p):
+    """The flags that describe a .y4m / .yuv --data_path (load_frames reads them with getattr defaults)."""
+    p.add_argument('--yuv_size', type=str, default=None, help='WxH of a raw .yuv clip whose name does not carry _<W>x<H>')
+    p.add_argument('--yuv_matrix', type=str, default='bt709', choices=['bt709', 'bt601'], help='colour matrix of a YUV clip')
+    p.add_argument('--yuv_range', type=str, default=None, choices=['limited', 'full'],
+                   help="range of a YUV clip's codes (default: the file's XCOLORRANGE, else limited)")
+    p.add_argument('--yuv_frames', type=int, default=None, help='use the first N frames of a YUV clip')
+
+
+def open_yuv_clip(args, path):
+    """The clip at `path` as the yuv_* attributes of args describe it -> (YuvFile, frames to use, matrix, full_range)."""
+    from ..videoio import open_yuv, parse_size
+    size = getattr(args, 'yuv_size', None)
+    clip = open_yuv(path, size=parse_size(size) if isinstance(size, str) else size)
+    rng = getattr(args, 'yuv_range', None)
+    if rng not in (None, 'limited', 'full'):
+        raise ValueError(f"yuv_range must be 'limited' or 'full', got {rng!r}")
+    full = bool(clip.full_range) if rng is None else rng == 'full'
+    n = getattr(args, 'yuv_frames', None)
+    n = clip.frames if n is None else int(n)
+    if not 0 < n <= clip.frames:
+        raise ValueError(f'{path} holds {clip.frames} frames, yuv_frames asks for {n}')
+    return clip, n, getattr(args, 'yuv_matrix', None) or 'bt709', full
+
+
+def load_yuv_frames(args, cfg, device, batch=16):
+    """-> uint8 (N,3,crop_h,crop_w) on `device` from a .y4m / .yuv clip: ops.yuv420_to_rgb_u8 on at most `batch` frames at a
+    time, then the centre crop of the PNG path."""
+    from ..videoio import centre_crop_offsets
+    h, w = cfg['crop_h'], cfg['crop_w']
+    clip, n, matrix, full = open_yuv_clip(args, args.data_path)
+    top, left = centre_crop_offsets(clip.H, clip.W, h, w)
+    out = torch.empty((n, 3, h, w), dtype=torch.uint8, device=device)
+    for j in range(0, n, batch):
+        k = min(batch, n - j)
+        rgb = ops.yuv420_to_rgb_u8(torch.from_numpy(clip.read(j, k)).to(device), clip.H, clip.W, matrix, full)
+        out[j:j + k] = rgb[:, :, top:top + h, left:left + w]
+    return out
+
+
 def load_frames(args, cfg, device):
-    """-> uint8 (N,3,crop_h,crop_w) on `device`: sorted PNGs, center crop (reference videosets/datasets.py:8-30)."""
+    """-> uint8 (N,3,crop_h,crop_w) on `device`: sorted PNGs, center crop (reference videosets/datasets.py:8-30), or the
+    frames of a .y4m / .yuv clip (8-bit 4:2:0; optional args.yuv_size / yuv_matrix / yuv_range / yuv_frames)."""
     h, w = cfg['crop_h'], cfg['crop_w']
     if args.synthetic:
         return synthetic_frames(args.synthetic, h, w, seed=args.seed, device=device)
+    from ..videoio import is_video_file
+    if is_video_file(args.data_path):
+        return load_yuv_frames(args, cfg, device)
     from PIL import Image
     files = [os.path.join(args.data_path, x) for x in sorted(os.listdir(args.data_path))]
     out = torch.empty((len(files), 3, h, w), dtype=torch.uint8)

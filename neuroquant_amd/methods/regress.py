@@ -21,7 +21,7 @@ import torch
 from ..models import HNeRV, NeRV
 from ..utils import CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger
 from .. import ops
-from .calibrate_network import evaluate, load_frames, report_line, seed_all
+from .calibrate_network import add_yuv_args, evaluate, load_frames, report_line, seed_all
 
 
 def parse_args(argv):
@@ -32,6 +32,7 @@ def parse_args(argv):
     p.add_argument('--arch', type=str)
     p.add_argument('--data_path', type=str)
     p.add_argument('--synthetic', type=int, default=0)
+    add_yuv_args(p)
     p.add_argument('--vid', type=str, default='Bunny')
     p.add_argument('--data_split', type=str, default='1_1_1')
     p.add_argument('-p', '--print-freq', default=50, type=int)

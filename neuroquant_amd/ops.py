@@ -1852,6 +1852,81 @@ def frames_to_u8(x: torch.Tensor, layout: str = "chw") -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------ 8-bit YUV 4:2:0 frames
+YUV_MATRICES = {"bt601": 0, "bt709": 1}
+
+
+def yuv420_frame_bytes(H: int, W: int) -> int:
+    """bytes of one I420 frame, H * W * 3 / 2 (0 for non-positive or odd sizes)."""
+    return int(L.lib().nq_yuv420_frame_bytes(int(H), int(W)))
+
+
+def _yuv_args(what, H, W, matrix, full_range=False):
+    """-> (frame bytes, matrix code, range code); ValueError naming `what` for odd / non-positive sizes or an unknown matrix"""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"{what}: matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}")
+    H, W = int(H), int(W)
+    fb = H * W * 3 // 2 if H > 0 and W > 0 and not (H | W) & 1 else 0    # nq_yuv420_frame_bytes, without the call
+    if fb <= 0:
+        raise ValueError(f"{what}: 4:2:0 frames need positive even H and W, got {H} x {W}")
+    return fb, YUV_MATRICES[matrix], 1 if full_range else 0
+
+
+def _yuv_frames(what, buf, fb, H, W):
+    """a (n, frame bytes) uint8 tensor (one frame may come flat) -> (n, frame bytes); ValueError otherwise"""
+    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8:
+        raise ValueError(f"{what} takes uint8 I420 frames, got {getattr(buf, 'dtype', type(buf))}")
+    if buf.dim() == 1:
+        buf = buf[None]
+    if buf.dim() != 2 or buf.shape[0] == 0 or buf.shape[1] != fb:
+        raise ValueError(f"{what}: {H} x {W} frames are (n, {fb}) bytes, got {tuple(buf.shape)}")
+    return buf
+
+
+def frames_to_yuv420(x: torch.Tensor, matrix: str = "bt709", full_range: bool = False) -> torch.Tensor:
+    """(n, 3, H, W) fp32 RGB -> uint8 (n, H * W * 3 / 2): I420 frames (Y, U, V planes), the payload of a .y4m / .yuv frame.
+    NaN -> 0 and clamp to [0, 1] as frames_to_u8; chroma is the mean of each 2 x 2 block; one rounding (include/nq_hip.h)."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape[0] == 0:
+        raise ValueError("frames_to_yuv420 takes a non-empty (n, 3, H, W) float32 tensor, got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    n, _, H, W = x.shape
+    fb, m, fr = _yuv_args("frames_to_yuv420", H, W, matrix, full_range)
+    x = _dev(x.detach(), "x")
+    out = torch.empty((n, fb), device=x.device, dtype=torch.uint8)
+    L.check(L.lib().nq_frames_to_yuv420(_p(x), _p(out), n, H, W, m, fr, _stream()), "frames_to_yuv420")
+    return out
+
+
+def yuv420_to_rgb_u8(buf: torch.Tensor, H: int, W: int, matrix: str = "bt709", full_range: bool = False) -> torch.Tensor:
+    """uint8 I420 frames (n, H * W * 3 / 2) -> uint8 (n, 3, H, W) planar RGB; each chroma sample serves its 2 x 2 block."""
+    fb, m, fr = _yuv_args("yuv420_to_rgb_u8", H, W, matrix, full_range)
+    buf = _dev_as(_yuv_frames("yuv420_to_rgb_u8", buf, fb, H, W), torch.uint8, "frames")
+    n = buf.shape[0]
+    out = torch.empty((n, 3, int(H), int(W)), device=buf.device, dtype=torch.uint8)
+    L.check(L.lib().nq_yuv420_to_rgb_u8(_p(buf), _p(out), n, int(H), int(W), m, fr, _stream()), "yuv420_to_rgb_u8")
+    return out
+
+
+def yuv420_sse(a: torch.Tensor, b: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """exact sums of squared code differences of two sets of I420 frames -> int64 (n, 3): per frame, planes Y, U, V."""
+    fb, _, _ = _yuv_args("yuv420_sse", H, W, "bt709")
+    a, b = _yuv_frames("yuv420_sse", a, fb, H, W), _yuv_frames("yuv420_sse", b, fb, H, W)
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"yuv420_sse: the two sets of frames differ: {tuple(a.shape)} and {tuple(b.shape)}")
+    a, b = _dev_as(a, torch.uint8, "frames"), _dev_as(b, torch.uint8, "frames")
+    n = a.shape[0]
+    sse = torch.empty((n, 3), device=a.device, dtype=torch.int64)   # sums stay far below 2^63: the bytes of a uint64 (n, 3)
+    L.check(L.lib().nq_yuv420_sse(_p(a), _p(b), _p(sse), n, int(H), int(W), _stream()), "yuv420_sse")
+    return sse
+
+
+def yuv420_psnr(a: torch.Tensor, b: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """PSNR of the 8-bit Y, U and V planes -> float64 (n, 3): 10 log10(255^2 * plane_pixels / sse), inf where sse = 0."""
+    sse = yuv420_sse(a, b, H, W).double()
+    px = torch.tensor([H * W, H * W // 4, H * W // 4], device=sse.device, dtype=torch.float64)
+    return 10.0 * torch.log10(255.0 ** 2 * px / sse)
+
+
 # ------------------------------------------------------------------------------------------ entropy-coded levels (rANS)
 def rans_chunks(n: int, chunk: int) -> int:
     """chunks a tensor of n levels is cut into (0 for n <= 0, chunk <= 0 or chunk not a multiple of 64)."""
