@@ -599,6 +599,25 @@ NQ_API int nq_rans_decode(const uint16_t* words, const uint32_t* states, const u
                    int n_bits, int64_t chunk, const float* delta, const float* zp, int64_t row_len, uint8_t* levels, float* w,
                    nq_stream_t stream);
 
+/* ---- quantised, temporally coded frame embeddings (additive: nq_abi_version() stays 7) ----
+ * x is (N, C, HW) fp32: N frames, C embedding channels, HW positions, E = C * HW values per frame; delta / zp hold one value
+ * per channel.  level[t][e] = clamp(rint(x[t][e] / delta[c]) + zp[c], 0, 2^n_bits - 1) with c = e / HW, in fp32 and
+ * uncontracted: the level of nq_uaq_forward.  Symbols are frame-major (N, E): temporal = 0: sym[t] = level[t]; temporal = 1:
+ * sym[0] = level[0], sym[t] = (level[t] - level[t - 1]) mod 2^n_bits.
+ *   nq_embed_symbols  one launch, one thread per value (a thread recomputes its predecessor's level from x[t - 1]): writes
+ *                     the N * E levels and the N * E symbols, one byte each.  A NaN gives level 0.
+ *   nq_embed_restore  sym holds the N * E symbols as floats (exact integers: what nq_unpack_dequant / nq_rans_decode write
+ *                     with a step of one and a zero point of zero); a float outside [0, 255] is clamped, then masked to
+ *                     n_bits bits.  level[t] = temporal ? (level[t - 1] + sym[t]) & (2^n_bits - 1) : sym[t];
+ *                     out[t][e] = ((float)level[t][e] - zp[c]) * delta[c], the expression of nq_unpack_dequant.  One thread
+ *                     per column e, sequential over t.
+ * NQ_ERR_INVALID, before the device is touched, for null pointers, non-positive sizes, n_bits outside 2..8 and temporal
+ * outside {0, 1}; NQ_ERR_UNSUPPORTED for N * C * HW past int64 or more than 2^31 - 1 workgroups. */
+NQ_API int nq_embed_symbols(const float* x, const float* delta, const float* zp, int64_t N, int64_t C, int64_t HW, int n_bits,
+                     int temporal, uint8_t* levels, uint8_t* symbols, nq_stream_t stream);
+NQ_API int nq_embed_restore(const float* sym, const float* delta, const float* zp, int64_t N, int64_t C, int64_t HW, int n_bits,
+                     int temporal, float* out, nq_stream_t stream);
+
 /* ---- bit allocation under a size budget (additive: nq_abi_version() stays 7) ----
  * The Omega score of an allocation is a quadratic form: with K bit choices for each of L layers, the (L K) x (L K) Gram matrix
  * G[(l,c),(m,d)] = <v_l(c), (H v_m(d))_l> of the per-layer perturbations gives Omega(b) = sum_l sum_m G[(l,b_l),(m,b_m)].

@@ -189,6 +189,8 @@ def _load():
     sig("nq_yuv420_sse", I, P, P, P, L, I, I, P)
     sig("nq_rans_chunks", L, L, L)
     sig("nq_rans_decode", I, P, P, P, P, L, I, L, P, P, L, P, P, P)
+    sig("nq_embed_symbols", I, P, P, P, L, L, L, I, I, P, P, P)
+    sig("nq_embed_restore", I, P, P, P, L, L, L, I, I, P, P)
     sig("nq_rows_dot_ws_bytes", L, I, L)
     sig("nq_rows_dot", I, P, P, P, I, L, P, P)
     sig("nq_bit_search_ws_bytes", L, I, I)
@@ -211,6 +213,7 @@ EXPORTS = (
     "nq_packed_words", "nq_pack_levels", "nq_unpack_dequant", "nq_frames_to_u8",
     "nq_yuv420_frame_bytes", "nq_frames_to_yuv420", "nq_yuv420_to_rgb_u8", "nq_yuv420_sse",
     "nq_rans_chunks", "nq_rans_decode",
+    "nq_embed_symbols", "nq_embed_restore",
     "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",
     "nq_conv3_levels_supported", "nq_conv_forward3_levels",
     "nq_weight_layout3_f16", "nq_conv_forward3_levels_f16",

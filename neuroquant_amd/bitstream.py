@@ -11,7 +11,12 @@ model's evaluation bit for bit.
 By default (`coding="packed"`) the file realises the NOMINAL size (bits x parameters).  `coding="rans"` / `"auto"` store the
 levels entropy coded instead (§12): a 64-lane interleaved rANS code with one frequency table per tensor, encoded here on the
 host (`rans_encode`) and decoded at open by a HIP kernel, one wavefront per chunk.  The weights a player rebuilds are the same
-floats either way.  Scales, soft biases and embeddings are not coded.
+floats either way.  Scales and soft biases are not coded.
+
+HNeRV's frame embeddings are fp32 by default.  `embedding_bits=` stores them as levels of 2..8 bits with one
+scale per embedding channel: packed, rANS coded, or rANS coded as frame-to-frame differences, whichever is smallest.  The
+player rebuilds them once at open (`ops.embed_restore`) and decodes as before.  `quantise_embeddings` gives the tensor such a
+file restores, so that a model can be calibrated and evaluated on what its file will hold.
 """
 import json
 import math
@@ -189,6 +194,175 @@ def coded_tensors(header, sec, what="stream"):
     return out
 
 
+# ------------------------------------------------------------------------------------------ embeddings (host only)
+EMBED_MODES = ("packed", "rans", "temporal")   # the order in which ties between equal sizes are resolved
+# mode -> (temporal, coding) of the header's `embedding` entry
+_EMBED_LAYOUT = {"packed": (False, "packed"), "rans": (False, "rans"), "temporal": (True, "rans")}
+_EMBED_RANS = ("rans_freq", "rans_states", "rans_offsets", "rans_words")
+
+
+def smallest_embedding_mode(bytes_by_mode):
+    """{mode: section bytes} -> the mode `write_stream` keeps: the fewest bytes, ties in the order packed, rans, temporal."""
+    return min((m for m in EMBED_MODES if m in bytes_by_mode), key=lambda m: bytes_by_mode[m])
+
+
+def embedding_sections(header, sec, what="stream"):
+    """The quantised embeddings of a parsed file (`read_container`'s header and sections), checked on the host before anything
+    of them reaches the GPU: the counterpart of `coded_tensors`.  -> None for a file that stores fp32 embeddings (no
+    `embedding` entry), else dict(bits, temporal, coding, chunk, shape, delta, zero_point, levels, rans) with `rans` the four
+    coded arrays (None for coding 'packed').  ValueError names the rule that failed."""
+    entry = header.get("embedding")
+    if entry is None:
+        return None
+    shape = header.get("embedding_shape")
+    if header.get("arch") != "hnerv" or not isinstance(entry, dict):
+        raise ValueError(f"{what}: only an HNeRV stream stores embeddings, described by a table")
+    if (not isinstance(shape, list) or len(shape) != 4 or not all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in shape)
+            or shape[0] != header.get("frames")):
+        raise ValueError(f"{what}: embedding_shape must be (frames, C, h, w) with positive sizes, got {shape!r} for "
+                         f"{header.get('frames')!r} frames")
+    N, C, E = shape[0], shape[1], shape[1] * shape[2] * shape[3]
+    bits, temporal, coding = entry.get("bits"), entry.get("temporal"), entry.get("coding")
+    if not isinstance(bits, int) or isinstance(bits, bool) or not 2 <= bits <= 8:
+        raise ValueError(f"{what}: embedding bits must be an integer in 2..8, got {bits!r}")
+    if not isinstance(temporal, bool):
+        raise ValueError(f"{what}: embedding temporal must be true or false, got {temporal!r}")
+    if coding not in ("packed", "rans"):
+        raise ValueError(f"{what}: embeddings are stored in an unknown coding {coding!r}")
+    if entry.get("scale_rows") != C:
+        raise ValueError(f"{what}: embedding scale_rows is {entry.get('scale_rows')!r}, the embeddings have {C} channels")
+    if coding == "rans" and N < 2:
+        raise ValueError(f"{what}: coding 'rans' codes the frames after the first, the stream holds {N}")
+    if "embeddings" in sec:
+        raise ValueError(f"{what}: quantised embeddings and an fp32 'embeddings' section in one file")
+    try:
+        delta, zp, levels = (sec[f"embeddings.{k}"] for k in ("delta", "zero_point", "levels"))
+        rans = [sec[f"embeddings.{k}"] for k in _EMBED_RANS] if coding == "rans" else None
+    except KeyError as e:
+        raise ValueError(f"{what}: embeddings are stored as levels but section {e} is missing") from None
+    for name, a in (("delta", delta), ("zero_point", zp)):
+        if a.dtype.kind != "f" or len(a) != C:
+            raise ValueError(f"{what}: embeddings.{name} must hold {C} floats (one per channel), got {len(a)} of {a.dtype}")
+    n_packed = N * E if coding == "packed" else E
+    want = (n_packed * bits + 31) // 32
+    if levels.dtype.kind != "u" or levels.dtype.itemsize != 4 or len(levels) != want:
+        raise ValueError(f"{what}: embeddings.levels must hold {want} u32 words ({n_packed} symbols of {bits} bits), got "
+                         f"{len(levels)} of {levels.dtype}")
+    chunk = None
+    if rans is not None:
+        if [a.dtype.itemsize for a in rans] != [2, 4, 4, 2]:
+            raise ValueError(f"{what}: embeddings: frequencies and words are u16 sections, states and offsets u32")
+        chunk = entry.get("rans_chunk")
+        rans_validate(*rans, (N - 1) * E, bits, chunk, what=f"{what}: embeddings")
+    return dict(bits=bits, temporal=temporal, coding=coding, chunk=chunk, shape=tuple(shape), delta=delta, zero_point=zp,
+                levels=levels, rans=rans)
+
+
+# ------------------------------------------------------------------------------------------ embeddings (GPU)
+class QuantisedEmbeddings:
+    """HNeRV's frame embeddings quantised to `bits` bits: `source` (N, C, h, w) fp32 as given, `delta` /
+    `zero_point` one per channel ('max' rule, not rounded to fp16), `levels` uint8 (N, C*h*w) and `restored`, the fp32 tensor
+    a player rebuilds from a file that stores these levels: what a model whose file is to store them must be evaluated on."""
+
+    def __init__(self, source, bits, delta, zero_point, levels, restored):
+        self.source, self.bits, self.delta, self.zero_point = source, bits, delta, zero_point
+        self.levels, self.restored, self.shape = levels, restored, tuple(source.shape)
+
+
+def _embedding_tensor(x):
+    x = (torch.cat(list(x), 0) if isinstance(x, (list, tuple)) else x).detach().float()
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"embeddings must be a non-empty (N, C, h, w) tensor, got shape {tuple(x.shape)}")
+    return x.contiguous()
+
+
+@torch.no_grad()
+def quantise_embeddings(x, bits):
+    """(N, C, h, w) fp32 embeddings (tensor or the list `evaluate()` returned) on the GPU -> QuantisedEmbeddings.  One
+    (delta, zero_point) per channel from `ops.scale_init_max` on the channel-major view (C, N, h, w): 0 lies in the range, the
+    step is at least 1e-8, an all-zero channel restores to exact zeros.  ValueError for bits outside 2..8 and for embeddings
+    that are not finite."""
+    x = _embedding_tensor(x)
+    if not isinstance(bits, int) or isinstance(bits, bool) or not 2 <= bits <= 8:
+        raise ValueError(f"embedding bits must be an integer in 2..8, got {bits!r}")
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("embeddings are not finite: they cannot be quantised")
+    delta, zp = ops.scale_init_max(x.transpose(0, 1).contiguous(), 2 ** bits, True)
+    delta, zp = delta.reshape(-1).contiguous(), zp.reshape(-1).contiguous()
+    levels, _ = ops.embed_symbols(x, delta, zp, bits, False)
+    restored = ops.embed_restore(levels.float(), delta, zp, x.shape, bits, False)
+    return QuantisedEmbeddings(x, bits, delta, zp, levels, restored)
+
+
+@torch.no_grad()
+def encode_embeddings(x, bits, mode, chunk=DEFAULT_CHUNK):
+    """The embeddings x (fp32 tensor / list, or a QuantisedEmbeddings of the same `bits`) as one of EMBED_MODES would store
+    them -> (the header's `embedding` entry, sections [(name, tag, array)]).  'packed': all N * E levels at their bit-width;
+    'rans': frame 0's levels packed, the other frames' levels rANS coded; 'temporal': frame 0's levels packed, the
+    frame-to-frame differences modulo 2^bits rANS coded.  A single frame is always stored packed."""
+    if mode not in EMBED_MODES:
+        raise ValueError(f"mode must be one of {EMBED_MODES}, got {mode!r}")
+    q = x if isinstance(x, QuantisedEmbeddings) else quantise_embeddings(x, bits)
+    if q.bits != bits:
+        raise ValueError(f"embeddings were quantised to {q.bits} bits, asked to store {bits}")
+    if not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES:
+        raise ValueError(f"chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
+    N, C = q.shape[:2]
+    temporal, coding = _EMBED_LAYOUT["packed" if N == 1 else mode]
+    _, symbols = ops.embed_symbols(q.source, q.delta, q.zero_point, bits, temporal)
+    entry = dict(bits=bits, scale_rows=C, temporal=temporal, coding=coding)
+    sections = []
+    for key, t in (("delta", q.delta), ("zero_point", q.zero_point)):
+        tag, arr = _scale_section(t)
+        sections.append((f"embeddings.{key}", tag, arr))
+    packed = symbols if coding == "packed" else symbols[0]
+    sections.append(("embeddings.levels", "u32", ops.pack_levels(packed, bits).cpu().numpy().view(np.uint32)))
+    if coding == "rans":
+        entry["rans_chunk"] = chunk
+        coded = rans_encode(symbols[1:].cpu().numpy(), bits, chunk)
+        sections += [(f"embeddings.{k}", t, a) for k, t, a in zip(_EMBED_RANS, ("u16", "u32", "u32", "u16"), coded)]
+    return entry, sections
+
+
+def _section_bytes(sections):
+    return sum(_align4(np.asarray(a).size * np.dtype(_DTYPES[t]).itemsize) for _, t, a in sections)
+
+
+@torch.no_grad()
+def restore_embeddings(emb, device):
+    """`embedding_sections`' result -> the fp32 embeddings (N, C, h, w) on `device`: the symbols through the kernels that
+    decode every other level section (a step of one and a zero point of zero leave the integers), then one
+    `ops.embed_restore`."""
+    def up(a):
+        a = np.array(a)   # a writable copy
+        view = {2: np.int16, 4: np.int32}[a.dtype.itemsize] if a.dtype.kind == "u" else a.dtype
+        return torch.from_numpy(a.view(view)).to(device)
+
+    N, C, h, w = emb["shape"]
+    E, bits = C * h * w, emb["bits"]
+    one, zero = torch.ones(1, device=device), torch.zeros(1, device=device)
+    first = N * E if emb["coding"] == "packed" else E
+    sym = ops.unpack_dequant(up(emb["levels"]), one, zero, (first,), bits)
+    if emb["coding"] == "rans":
+        freq, states, offsets, words = (up(a) for a in emb["rans"])
+        rest = ops.rans_decode_dequant(words, states, offsets, freq, one, zero, ((N - 1) * E,), bits, emb["chunk"], trusted=True)
+        sym = torch.cat([sym, rest])
+    return ops.embed_restore(sym, up(emb["delta"]).float(), up(emb["zero_point"]).float(), (N, C, h, w), bits, emb["temporal"])
+
+
+def _embedding_stream_sections(q, chunk, frames, device):
+    """write_stream's part for quantised embeddings: all three modes, the smallest kept, and what is kept decoded again on the
+    GPU from the very arrays the file will hold and compared with q.restored bit for bit.  -> (entry, sections, {mode: bytes})"""
+    built = {m: encode_embeddings(q, q.bits, m, chunk) for m in EMBED_MODES}
+    sizes = {m: _section_bytes(s) for m, (_, s) in built.items()}
+    entry, sections = built[smallest_embedding_mode(sizes)]
+    header = dict(arch="hnerv", frames=frames, embedding_shape=list(q.shape), embedding=entry)
+    sec = {name: np.asarray(a).reshape(-1).astype(_DTYPES[tag]) for name, tag, a in sections}
+    if not torch.equal(restore_embeddings(embedding_sections(header, sec, "write_stream"), device), q.restored):
+        raise RuntimeError("write_stream: the stored embedding levels do not reproduce the embeddings the model was evaluated on")
+    return entry, sections, sizes
+
+
 # ------------------------------------------------------------------------------------------ writer
 def _scale_section(t):
     """fp16 when every entry survives the round trip (true after AdaRound's init, quantizer.py:264-265), else fp32."""
@@ -234,14 +408,20 @@ def _check_decoder_shape(arch, cfg):
 
 
 @torch.no_grad()
-def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft", coding="packed", chunk=DEFAULT_CHUNK):
+def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft", coding="packed", chunk=DEFAULT_CHUNK,
+                 embedding_bits=None):
     """Write the calibrated `qnn` to `path`.  embeddings: HNeRV's per-frame input embeddings (tensor (N, c, h, w) or the list
     `evaluate()` returned); NeRV stores none and needs `frames`.  bias: 'soft' stores the fp32 bias the evaluated model uses,
     'hard' its integer decision (export.py's module docstring).  coding: 'packed' stores every level tensor at its bit-width,
     'rans' entropy codes every one in chunks of `chunk` symbols, 'auto' codes a tensor only where its four
     coded sections are smaller than its packed words.  -> summary: file size, bytes per kind of section, bpp when the frame
     size is known, the gap to the nominal size `export_quantized` reports, and the bytes of all level sections
-    (`coded_level_bytes`) against the histogram entropy of those same tensors (`entropy_level_bytes`)."""
+    (`coded_level_bytes`) against the histogram entropy of those same tensors (`entropy_level_bytes`).
+    embedding_bits (HNeRV only; default None: fp32 embeddings, the file of before): store the embeddings as levels of 2..8
+    bits in whichever of EMBED_MODES takes the fewest bytes.  The frames such a file decodes to are those of the
+    model on the RESTORED embeddings (summary['embedding_restored']).  A caller that evaluated the model on them passes the
+    `QuantisedEmbeddings` it took them from as `embeddings` (quantising a restored tensor a second time derives other scales);
+    what is written is decoded again on the GPU and compared with exactly that tensor."""
     from .quantization.quant_layer import QuantModule
     from .quantization.quantizer import AdaRoundQuantizer
     if bias not in ("soft", "hard"):
@@ -251,11 +431,20 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
     if coding != "packed" and (not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES):
         raise ValueError(f"chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
     _check_decoder_shape(arch, cfg)
-    emb = None
+    emb = qemb = None
+    if embedding_bits is not None and arch != "hnerv":
+        raise ValueError("embedding_bits applies to HNeRV streams: a NeRV stream stores no embeddings")
     if arch == "hnerv":
         if embeddings is None:
             raise ValueError("an HNeRV stream stores the frame embeddings: pass embeddings=")
-        emb = (torch.cat(list(embeddings), 0) if isinstance(embeddings, (list, tuple)) else embeddings).detach().float()
+        if isinstance(embeddings, QuantisedEmbeddings):
+            if embedding_bits not in (None, embeddings.bits):
+                raise ValueError(f"embeddings were quantised to {embeddings.bits} bits, embedding_bits asks for {embedding_bits}")
+            qemb = embeddings
+        elif embedding_bits is not None:
+            qemb = quantise_embeddings(embeddings, embedding_bits)
+        emb = qemb.restored if qemb is not None else (
+            torch.cat(list(embeddings), 0) if isinstance(embeddings, (list, tuple)) else embeddings).detach().float()
         frames = emb.shape[0] if frames is None else frames
         if frames != emb.shape[0]:
             raise ValueError(f"{frames} frames but {emb.shape[0]} embeddings")
@@ -297,22 +486,37 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
         nominal_bits += wq.n_bits * m.weight.numel() + bq.n_bits * m.bias.numel()   # as export_quantized counts them
     header = dict(arch=arch, cfg=cfg, frames=int(frames), hadamard=bool(qnn.hadamard), bias=bias, layers=layers,
                   embedding_shape=None)
+    emb_sizes = None
     if emb is not None:
         header["embedding_shape"] = list(emb.shape)
-        sections.append(("embeddings", "f32", emb.cpu().numpy()))
+        if qemb is None:
+            sections.append(("embeddings", "f32", emb.cpu().numpy()))
+        else:
+            header["embedding"], secs, emb_sizes = _embedding_stream_sections(qemb, chunk, int(frames), emb.device)
+            sections += secs
     header, size = _write_container(path, header, sections)
     kinds = {}
     for s in header["sections"]:
-        kind = "embeddings" if s["name"] == "embeddings" else ("weight_" if s["name"][0] == "w" else "bias_") + s["name"].split(".")[1]
+        if s["name"].startswith("embeddings."):
+            part = s["name"].split(".")[1]
+            kind = "embedding_" + ("levels" if part == "levels" else "rans" if part.startswith("rans_") else "scales")
+        else:
+            kind = "embeddings" if s["name"] == "embeddings" else ("weight_" if s["name"][0] == "w" else "bias_") + s["name"].split(".")[1]
         kinds[kind] = kinds.get(kind, 0) + _align4(s["bytes"])
     nominal = math.ceil(nominal_bits / 8)
-    coded = sum(v for k, v in kinds.items() if k.endswith("_levels") or "_rans_" in k)
+    coded = sum(v for k, v in kinds.items() if k[0] in "wb" and (k.endswith("_levels") or "_rans_" in k))
     entropy = math.ceil(entropy_bits / 8)
     summary = dict(path=path, file_bytes=size, header_bytes=size - sum(kinds.values()), section_bytes=kinds,
                    total_bytes_nominal=nominal, gap_to_nominal_bytes=size - nominal, frames=int(frames), bias=bias,
                    coding=coding, coded_tensors=sum(("levels_coding" in l) + ("bias_levels_coding" in l) for l in layers),
                    coded_level_bytes=coded, entropy_level_bytes=entropy, gap_to_entropy_bytes=coded - entropy,
                    scale_dtypes=[[l["delta_dtype"], l["zero_point_dtype"]] for l in layers])
+    if qemb is not None:
+        e = header["embedding"]
+        summary.update(embedding=dict(bits=e["bits"], coding=e["coding"], temporal=e["temporal"],
+                                      mode=smallest_embedding_mode(emb_sizes), mode_bytes=emb_sizes,
+                                      bytes=sum(v for k, v in kinds.items() if k.startswith("embedding_"))),
+                       embedding_restored=emb)
     h, w = cfg.get("crop_h"), cfg.get("crop_w")
     if frames and h and w:
         summary["bpp"] = size * 8 / (frames * h * w)
@@ -373,6 +577,7 @@ class StreamDecoder:
             return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(self.device)
 
         coded = coded_tensors(header, sec, what=path)   # host validation of every coded tensor, before any upload
+        stored_emb = embedding_sections(header, sec, what=path)   # ... and of quantised embeddings
 
         def levels(tag, i, lay, prefix, shape, n_bits, integers=False):
             """the tensor stored as `{tag}{i}` in whichever coding the layer names, dequantised on the GPU.  integers: ->
@@ -434,7 +639,12 @@ class StreamDecoder:
                     b = levels("b", i, lay, "bias_", (co,), lay["bias_n_bits"])
                 self.weights.append(w.contiguous())
                 self.biases.append(b.contiguous())
-            if self.arch == "hnerv":
+            self.embedding_info = None   # quantised embeddings: {bits, coding, temporal, bytes (their sections, unpadded)}
+            if stored_emb is not None:
+                self.embeddings = restore_embeddings(stored_emb, self.device)
+                self.embedding_info = dict(bits=stored_emb["bits"], coding=stored_emb["coding"], temporal=stored_emb["temporal"],
+                                           bytes=sum(a.nbytes for n_, a in sec.items() if n_.startswith("embeddings.")))
+            elif self.arch == "hnerv":
                 self.embeddings = up("embeddings").float().view(header["embedding_shape"])
             else:   # NeRV.encode(idx / n) for every frame: elementwise, so a row does not depend on its batch
                 from .models._layers import PositionEncoding

@@ -14,7 +14,8 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     YUV 4:2:0 clip instead of a directory of PNGs (--yuv_size, --yuv_matrix, --yuv_range, --yuv_frames; DESIGN.md §16);
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
-    packed at their bit-width and entropy-coded levels)
+    packed at their bit-width and entropy-coded levels; --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
+    and evaluates on the embeddings a player restores, and stores them as levels: DESIGN.md §17)
 """
 import argparse
 import logging
@@ -68,6 +69,9 @@ def parse_args(argv):
                    help='write the calibrated model as a packed bit stream (.nqv, neuroquant_amd/bitstream.py) to this path')
     p.add_argument('--stream_coding', type=str, default='packed', choices=['packed', 'rans', 'auto'],
                    help='levels of --export_stream: packed at their bit-width, rANS coded, or whichever is smaller per tensor')
+    p.add_argument('--embed_bits', type=int, default=None, choices=range(2, 9), metavar='2..8',
+                   help='HNeRV: quantise the frame embeddings to this many bits (one scale per embedding channel); the calibration, '
+                        'every evaluation after the FP one and --export_stream use the embeddings a player restores from the levels')
     args = p.parse_args(argv)
     if args.precision_file is not None:
         args.precision = read_precision_file(args.precision_file)
@@ -179,11 +183,11 @@ METRIC_NAMES = ['pred_seen_psnr', 'pred_seen_ssim', 'pred_unseen_psnr', 'pred_un
 
 
 @torch.no_grad()
-def evaluate(model, cache: FrameCache, args, cfg):
+def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
     """Per-frame decode + PSNR + MS-SSIM (reference calibrate_network.py:82-145); returns ([seen_psnr, unseen_psnr],
     embeddings) and leaves all four means on args.eval_metrics, keyed by METRIC_NAMES (as the reference leaves args.fps).
     Frames too small for five scales (min(H, W) <= 160) are evaluated for PSNR only: MS-SSIM is logged as n/a and stored
-    as NaN."""
+    as NaN.  embeddings (N, c, h, w): frame i is decoded from row i instead of model.encode's output."""
     model.eval()
     n = len(cache)
     dev = cache.frames.device
@@ -192,7 +196,10 @@ def evaluate(model, cache: FrameCache, args, cfg):
     for i in range(n):
         idx = torch.tensor([i], device=dev)
         img = cache.batch(idx)
-        emb = model.encode(img) if args.arch == 'hnerv' else model.encode(idx.float() / n)
+        if embeddings is not None:
+            emb = embeddings[i:i + 1]
+        else:
+            emb = model.encode(img) if args.arch == 'hnerv' else model.encode(idx.float() / n)
         out, embed_list, dec_time = model.decode(emb)
         embeds.append(embed_list[0])
         dec_times.append(dec_time)
@@ -260,13 +267,23 @@ def calibrate(args, cfg):
     res, embedding_list = evaluate(model, cache, args, cfg)
     report('FP', res)
 
+    embed_bits, qemb, stored = getattr(args, 'embed_bits', None), None, None
+    if embed_bits is not None:
+        if args.arch != 'hnerv':
+            raise ValueError('--embed_bits applies to HNeRV: NeRV stores no embeddings')
+        from ..bitstream import quantise_embeddings
+        qemb = quantise_embeddings(embedding_list, embed_bits)
+        stored = qemb.restored      # what a player rebuilds from the levels: everything below runs on it
+        evaluate(model, cache, args, cfg, embeddings=stored)
+        report('FP, embeddings quantised to {} bits'.format(embed_bits), None)
+
     wq_params = {'n_bits': 8, 'channel_wise': args.channel_wise, 'scale_method': args.init}
     qnn = QuantModel(model=model, hadamard=args.hadamard, weight_quant_params=wq_params).to(device)
     if getattr(args, 'precision_file', None):
         read_precision_file(args.precision_file, len(qnn.quant_modules()))
     args.qbits = qnn.set_bitwidth(args.precision)
     qnn.eval()
-    cali_data = torch.cat(embedding_list, dim=0)
+    cali_data = torch.cat(embedding_list, dim=0) if stored is None else stored
     logging.info('input embedding shape: {}'.format(cali_data.shape))
 
     qnn.set_quant_state(True)
@@ -277,9 +294,9 @@ def calibrate(args, cfg):
     logging.info('Init time: {}'.format(time.time() - t0))
 
     qnn.set_quant_state(False)
-    report('Close quantization', evaluate(qnn, cache, args, cfg)[0])
+    report('Close quantization', evaluate(qnn, cache, args, cfg, embeddings=stored)[0])
     qnn.set_quant_state(True)
-    report('Weight quantization w/o opt', evaluate(qnn, cache, args, cfg)[0])
+    report('Weight quantization w/o opt', evaluate(qnn, cache, args, cfg, embeddings=stored)[0])
 
     logging.info('average bit-width: {}'.format(args.qbits))
     start = datetime.now()
@@ -291,7 +308,7 @@ def calibrate(args, cfg):
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
 
     qnn.set_quant_state(weight_quant=True)
-    res = evaluate(qnn, cache, args, cfg)[0]
+    res = evaluate(qnn, cache, args, cfg, embeddings=stored)[0]
     report('Weight quantization w/ opt', res)
     tag = 'CW' if args.channel_wise else 'LW'
     if rank == 0:
@@ -299,12 +316,16 @@ def calibrate(args, cfg):
         if getattr(args, 'export_stream', None):
             from ..bitstream import write_stream
             s = write_stream(qnn, args.export_stream, args.arch, cfg, frames=n,
-                             embeddings=cali_data if args.arch == 'hnerv' else None,
+                             embeddings=(qemb if qemb is not None else cali_data) if args.arch == 'hnerv' else None,
                              coding=getattr(args, 'stream_coding', 'packed'))
             logging.info('bit stream: {} ({} bytes, {} bpp; nominal {} bytes; coding {}: levels {} bytes, '
                          'gap to entropy {} bytes)'.format(
                              args.export_stream, s['file_bytes'], round(s.get('bpp', float('nan')), 5), s['total_bytes_nominal'],
                              s['coding'], s['coded_level_bytes'], s['gap_to_entropy_bytes']))
+            if 'embedding' in s:
+                e = s['embedding']
+                logging.info('bit stream embeddings: {} bits, stored {} ({} bytes; packed / rans / temporal: {})'.format(
+                    e['bits'], e['mode'], e['bytes'], ' / '.join(str(e['mode_bytes'][m]) for m in ('packed', 'rans', 'temporal'))))
     args.qnn = qnn
     return res
 

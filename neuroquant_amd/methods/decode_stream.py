@@ -17,7 +17,8 @@ for 'Weight quantization w/ opt'.  --arithmetic levels runs the big 3 x 3 / 5 x 
 MFMAs per product (not bit-identical to the live model, within its float64 bounds) and names the layers that
 took that path.  --arithmetic half runs the same layers on half-precision activations with one MFMA per product (DESIGN.md
 §15: an approximation, about ten times outside those bounds), names them likewise, and exits non-zero if an activation left the
-range of IEEE half.
+range of IEEE half.  A file whose embeddings are stored as levels plays like any other; their bits, coding and
+bytes are printed and returned as `embedding_info`.
 """
 import argparse
 import contextlib
@@ -119,6 +120,7 @@ def run(args):
                                                        torch.from_numpy(own).to(img.device), h, w))
     res = dict(frames=n, batch_size=B, open_seconds=open_s, fps=n / dec_time, file_bytes=os.path.getsize(args.stream),
                level_bytes=dec.level_bytes, level_tensors=dec.level_tensors, arithmetic=dec.arithmetic,
+               embedding_info=dec.embedding_info,
                saturated=dec.saturated(),     # once, after the last frame
                levels_used={b: list(v) for b, v in dec.levels_used.items()})
     yuv = acc.pop('psnr_yuv')
@@ -139,6 +141,10 @@ def main(argv):
         args.stream, res['file_bytes'], res['frames'], res['open_seconds'], round(res['fps'], 1), res['batch_size']))
     print('levels: rans {} bytes in {} tensors, packed {} bytes in {} tensors'.format(
         res['level_bytes']['rans'], res['level_tensors']['rans'], res['level_bytes']['packed'], res['level_tensors']['packed']))
+    if res['embedding_info']:
+        e = res['embedding_info']
+        print('embeddings: {} bits, {}{}, {} bytes'.format(e['bits'], e['coding'], ', frame-to-frame differences' if e['temporal'] else '',
+                                                           e['bytes']))
     if res['arithmetic'] in ('levels', 'half'):
         print('arithmetic {}: '.format(res['arithmetic']) + '; '.join('batch {}: layers {}'.format(b, v if v else 'none')
                                                            for b, v in sorted(res['levels_used'].items())))

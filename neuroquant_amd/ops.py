@@ -1981,6 +1981,46 @@ def rans_decode_dequant(words, states, offsets, freq, delta: torch.Tensor, zp: t
     return w
 
 
+# ------------------------------------------------------------------------------------------ quantised embeddings
+def _embed_args(what, shape, delta, zp, n_bits, temporal):
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 4 or min(shape) <= 0:
+        raise ValueError(f"{what} takes non-empty (N, C, h, w) embeddings, got shape {shape}")
+    if not 2 <= int(n_bits) <= 8:
+        raise ValueError(f"{what}: n_bits must be 2..8, got {n_bits}")
+    delta, zp = _dev(delta, "delta").reshape(-1), _dev(zp, "zero_point").reshape(-1)
+    if delta.numel() != shape[1] or zp.numel() != shape[1]:
+        raise ValueError(f"{what}: delta / zero_point must hold one value per embedding channel ({shape[1]}), got "
+                         f"{delta.numel()} / {zp.numel()}")
+    return shape, delta, zp, int(n_bits), int(bool(temporal))
+
+
+def embed_symbols(x: torch.Tensor, delta: torch.Tensor, zp: torch.Tensor, n_bits: int, temporal: bool):
+    """(N, C, h, w) fp32 embeddings -> (levels, symbols), uint8 (N, C*h*w) each: level = clamp(rint(x / delta[c]) + zp[c], 0,
+    2^n_bits - 1) with one delta / zp per channel (the UAQ element); symbols are the levels, or (temporal) frame 0's levels and
+    the differences to the previous frame's modulo 2^n_bits.  One launch."""
+    x = _dev(x.detach(), "x")
+    (N, C, h, w), delta, zp, n_bits, temporal = _embed_args("embed_symbols", x.shape, delta, zp, n_bits, temporal)
+    levels = torch.empty((N, C * h * w), device=x.device, dtype=torch.uint8)
+    symbols = torch.empty_like(levels)
+    L.check(L.lib().nq_embed_symbols(_p(x), _p(delta), _p(zp), N, C, h * w, n_bits, temporal, _p(levels), _p(symbols), _stream()),
+            "embed_symbols")
+    return levels, symbols
+
+
+def embed_restore(symbols_f32: torch.Tensor, delta: torch.Tensor, zp: torch.Tensor, shape, n_bits: int, temporal: bool) -> torch.Tensor:
+    """symbols as floats (exact integers, N * C*h*w of them: what `unpack_dequant` / `rans_decode_dequant` give with a step of
+    one and a zero point of zero) -> fp32 embeddings of `shape` (N, C, h, w): the levels rebuilt frame after frame, then
+    (level - zp[c]) * delta[c], the expression of `unpack_dequant`."""
+    sym = _dev(symbols_f32, "symbols").reshape(-1)
+    (N, C, h, w), delta, zp, n_bits, temporal = _embed_args("embed_restore", shape, delta, zp, n_bits, temporal)
+    if sym.numel() != N * C * h * w:
+        raise ValueError(f"embed_restore: {sym.numel()} symbols for embeddings of shape {(N, C, h, w)}")
+    out = torch.empty((N, C, h, w), device=sym.device, dtype=torch.float32)
+    L.check(L.lib().nq_embed_restore(_p(sym), _p(delta), _p(zp), N, C, h * w, n_bits, temporal, _p(out), _stream()), "embed_restore")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ bit allocation (DESIGN.md §13)
 def rows_dot(V: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """out[r] = <V[r], g> for the K <= 8 rows of V, in float64 (exact products, fixed summation order: bit-identical from call
