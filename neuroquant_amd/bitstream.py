@@ -18,6 +18,7 @@ scale per embedding channel: packed, rANS coded, or rANS coded as frame-to-frame
 player rebuilds them once at open (`ops.embed_restore`) and decodes as before.  `quantise_embeddings` gives the tensor such a
 file restores, so that a model can be calibrated and evaluated on what its file will hold.
 """
+import collections
 import json
 import math
 import os
@@ -38,10 +39,23 @@ RANS_M = 1 << RANS_PROB_BITS
 RANS_L = 1 << 16
 RANS_LANES = 64
 DEFAULT_CHUNK = 32768
+# the sections of a level tensor per coding, in file order: (name after the tensor's stem, dtype tag)
+_RANS_PARTS = (("rans_freq", "u16"), ("rans_states", "u32"), ("rans_offsets", "u32"), ("rans_words", "u16"))
+_LEVEL_PARTS = {"packed": (("levels", "u32"),), "rans": _RANS_PARTS}
 
 
 def _align4(n):
     return (n + 3) & ~3
+
+
+def _check_chunk(chunk, what):
+    if not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES:
+        raise ValueError(f"{what}: chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
+
+
+def _check_bits(bits, lo, hi, what):
+    if not isinstance(bits, int) or isinstance(bits, bool) or not lo <= bits <= hi:
+        raise ValueError(f"{what} must be an integer in {lo}..{hi}, got {bits!r}")
 
 
 # ------------------------------------------------------------------------------------------ container (host only)
@@ -119,9 +133,10 @@ def rans_encode(levels, n_bits, chunk=DEFAULT_CHUNK):
     reversed at the end)."""
     lv = np.ascontiguousarray(np.asarray(levels).reshape(-1)).astype(np.int64)
     n, n_bits, chunk = lv.size, int(n_bits), int(chunk)
-    if n == 0 or not 1 <= n_bits <= 8 or chunk <= 0 or chunk % RANS_LANES:
-        raise ValueError(f"rans_encode: need levels, n_bits in 1..8 and chunk a positive multiple of 64, got {n} levels, "
-                         f"n_bits={n_bits}, chunk={chunk}")
+    if n == 0:
+        raise ValueError("rans_encode: no levels to code")
+    _check_bits(n_bits, 1, 8, "rans_encode: n_bits")
+    _check_chunk(chunk, "rans_encode")
     if int(lv.max()) >= 1 << n_bits or int(lv.min()) < 0:
         raise ValueError(f"rans_encode: level {int(lv.max())} does not fit {n_bits} bits")
     freq = rans_normalise(np.bincount(lv, minlength=1 << n_bits))
@@ -153,8 +168,7 @@ def rans_validate(freq, states, offsets, words, n, n_bits, chunk, what="coded te
     """Host check of a coded tensor's four sections before they reach the GPU; ValueError names the rule that failed."""
     if not isinstance(n_bits, int) or not 1 <= n_bits <= 8 or len(freq) != 1 << n_bits or int(np.sum(freq, dtype=np.int64)) != RANS_M:
         raise ValueError(f"{what}: the frequency table must hold 2^n_bits entries that sum to {RANS_M}")
-    if not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES:
-        raise ValueError(f"{what}: chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
+    _check_chunk(chunk, what)
     chunks = -(-int(n) // chunk)
     if len(offsets) != chunks + 1:
         raise ValueError(f"{what}: {len(offsets)} offsets stored, {n} levels in chunks of {chunk} need {chunks + 1}")
@@ -165,40 +179,61 @@ def rans_validate(freq, states, offsets, words, n, n_bits, chunk, what="coded te
         raise ValueError(f"{what}: need {RANS_LANES} states per chunk, each at least {RANS_L}")
 
 
-def coded_tensors(header, sec, what="stream"):
-    """{tensor name ('w0', 'b3', ...): (freq, states, offsets, words, chunk)} for every rANS-coded tensor of a parsed file
-    (`read_container`'s header and sections), each validated with `rans_validate`.  Host only: this is the check the player
-    runs before anything of a coded tensor reaches the GPU.  ValueError for an unknown coding, a missing section or a failed
-    rule."""
+# ------------------------------------------------------------------------------------------ stored level tensors (host only)
+class StoredLevels(collections.namedtuple("StoredLevels", "name n n_bits coding arrays chunk")):
+    """One run of `n` levels of `n_bits` bits as a file holds it under the section stem `name`: coding 'packed' with
+    arrays = (u32 words,) and no chunk, or coding 'rans' with arrays = (freq, states, offsets, words).  Only `_stored_levels`
+    makes one, so holding one means the host checks have passed."""
+    words = property(lambda self: self.arrays[-1])
+    nbytes = property(lambda self: sum(a.nbytes for a in self.arrays))   # of its sections, unpadded
+
+
+def _stored_levels(sec, name, n, n_bits, coding, chunk, what):
+    """The level tensor `name` of `read_container`'s sections -> StoredLevels, checked on the host before anything of it
+    reaches the GPU; the only place that looks level sections up.  ValueError names the missing section or the failed rule."""
+    if coding not in tuple(_LEVEL_PARTS):
+        raise ValueError(f"{what}: {name} is stored in an unknown coding {coding!r}")
+    _check_bits(n_bits, 1, 8, f"{what}: {name}: n_bits")
+    arrays = [sec.get(f"{name}.{k}") for k, _ in _LEVEL_PARTS[coding]]
+    for (k, tag), a in zip(_LEVEL_PARTS[coding], arrays):
+        if a is None:
+            raise ValueError(f"{what}: {name} is stored {coding} but section {name}.{k} is missing")
+        if a.dtype != np.dtype(_DTYPES[tag]):
+            raise ValueError(f"{what}: {name}.{k} must be a {tag} section, got {a.dtype}")
+    if coding == "rans":
+        rans_validate(*arrays, n, n_bits, chunk, what=f"{what}: {name}")
+    elif len(arrays[0]) != (n * n_bits + 31) // 32:
+        raise ValueError(f"{what}: {name}.levels must hold {(n * n_bits + 31) // 32} u32 words ({n} symbols of {n_bits} bits), "
+                         f"got {len(arrays[0])}")
+    return StoredLevels(name, n, n_bits, coding, tuple(arrays), chunk if coding == "rans" else None)
+
+
+def stored_tensors(header, sec, what="stream"):
+    """{tensor name ('w0', 'b3', ...): StoredLevels} for every weight and hard-bias tensor of a parsed file (`read_container`'s
+    header and sections), packed ones included.  Host only: this is the check the player runs before anything of a level
+    tensor reaches the GPU.  ValueError for an unknown coding, a missing or mistyped section or a failed rule."""
     out = {}
     for i, lay in enumerate(header["layers"]):
         co, _, k, k2 = lay["shape"]
-        for tag, prefix, n, bits_key in (("w", "", co * lay["c_in_stored"] * k * k2, "n_bits"), ("b", "bias_", co, "bias_n_bits")):
+        for name, prefix, n in ((f"w{i}", "", co * lay["c_in_stored"] * k * k2), (f"b{i}", "bias_", co)):
             coding = lay.get(prefix + "levels_coding", "packed")
-            if coding == "packed":
+            if prefix and header.get("bias") != "hard":
+                if coding != "packed":
+                    raise ValueError(f"{what}: {name} is marked as coded but the stream stores soft biases")
                 continue
-            name = f"{tag}{i}"
-            if coding != "rans":
-                raise ValueError(f"{what}: {name} is stored in an unknown coding {coding!r}")
-            if tag == "b" and header.get("bias") != "hard":
-                raise ValueError(f"{what}: {name} is marked as coded but the stream stores soft biases")
-            try:
-                parts = [sec[f"{name}.rans_{k}"] for k in ("freq", "states", "offsets", "words")]
-            except KeyError as e:
-                raise ValueError(f"{what}: {name} is rANS coded but section {e} is missing") from None
-            if [a.dtype.itemsize for a in parts] != [2, 4, 4, 2]:
-                raise ValueError(f"{what}: {name}: frequencies and words are u16 sections, states and offsets u32")
-            chunk = lay.get(prefix + "rans_chunk")
-            rans_validate(*parts, n, lay.get(bits_key), chunk, what=f"{what}: {name}")
-            out[name] = (*parts, chunk)
+            out[name] = _stored_levels(sec, name, n, lay.get(prefix + "n_bits"), coding, lay.get(prefix + "rans_chunk"), what)
     return out
+
+
+def coded_tensors(header, sec, what="stream"):
+    """{tensor name: (freq, states, offsets, words, chunk)} for the rANS-coded tensors among `stored_tensors`."""
+    return {name: (*st.arrays, st.chunk) for name, st in stored_tensors(header, sec, what).items() if st.coding == "rans"}
 
 
 # ------------------------------------------------------------------------------------------ embeddings (host only)
 EMBED_MODES = ("packed", "rans", "temporal")   # the order in which ties between equal sizes are resolved
 # mode -> (temporal, coding) of the header's `embedding` entry
 _EMBED_LAYOUT = {"packed": (False, "packed"), "rans": (False, "rans"), "temporal": (True, "rans")}
-_EMBED_RANS = ("rans_freq", "rans_states", "rans_offsets", "rans_words")
 
 
 def smallest_embedding_mode(bytes_by_mode):
@@ -208,9 +243,10 @@ def smallest_embedding_mode(bytes_by_mode):
 
 def embedding_sections(header, sec, what="stream"):
     """The quantised embeddings of a parsed file (`read_container`'s header and sections), checked on the host before anything
-    of them reaches the GPU: the counterpart of `coded_tensors`.  -> None for a file that stores fp32 embeddings (no
+    of them reaches the GPU: the counterpart of `stored_tensors`.  -> None for a file that stores fp32 embeddings (no
     `embedding` entry), else dict(bits, temporal, coding, chunk, shape, delta, zero_point, levels, rans) with `rans` the four
-    coded arrays (None for coding 'packed').  ValueError names the rule that failed."""
+    coded arrays (None for coding 'packed'), and `stored`, the same two runs of levels as (StoredLevels, StoredLevels or None)
+    for `restore_embeddings`.  ValueError names the rule that failed."""
     entry = header.get("embedding")
     if entry is None:
         return None
@@ -223,8 +259,7 @@ def embedding_sections(header, sec, what="stream"):
                          f"{header.get('frames')!r} frames")
     N, C, E = shape[0], shape[1], shape[1] * shape[2] * shape[3]
     bits, temporal, coding = entry.get("bits"), entry.get("temporal"), entry.get("coding")
-    if not isinstance(bits, int) or isinstance(bits, bool) or not 2 <= bits <= 8:
-        raise ValueError(f"{what}: embedding bits must be an integer in 2..8, got {bits!r}")
+    _check_bits(bits, 2, 8, f"{what}: embedding bits")
     if not isinstance(temporal, bool):
         raise ValueError(f"{what}: embedding temporal must be true or false, got {temporal!r}")
     if coding not in ("packed", "rans"):
@@ -235,27 +270,74 @@ def embedding_sections(header, sec, what="stream"):
         raise ValueError(f"{what}: coding 'rans' codes the frames after the first, the stream holds {N}")
     if "embeddings" in sec:
         raise ValueError(f"{what}: quantised embeddings and an fp32 'embeddings' section in one file")
-    try:
-        delta, zp, levels = (sec[f"embeddings.{k}"] for k in ("delta", "zero_point", "levels"))
-        rans = [sec[f"embeddings.{k}"] for k in _EMBED_RANS] if coding == "rans" else None
-    except KeyError as e:
-        raise ValueError(f"{what}: embeddings are stored as levels but section {e} is missing") from None
+    delta, zp = sec.get("embeddings.delta"), sec.get("embeddings.zero_point")
     for name, a in (("delta", delta), ("zero_point", zp)):
+        if a is None:
+            raise ValueError(f"{what}: embeddings are stored as levels but section embeddings.{name} is missing")
         if a.dtype.kind != "f" or len(a) != C:
             raise ValueError(f"{what}: embeddings.{name} must hold {C} floats (one per channel), got {len(a)} of {a.dtype}")
-    n_packed = N * E if coding == "packed" else E
-    want = (n_packed * bits + 31) // 32
-    if levels.dtype.kind != "u" or levels.dtype.itemsize != 4 or len(levels) != want:
-        raise ValueError(f"{what}: embeddings.levels must hold {want} u32 words ({n_packed} symbols of {bits} bits), got "
-                         f"{len(levels)} of {levels.dtype}")
-    chunk = None
-    if rans is not None:
-        if [a.dtype.itemsize for a in rans] != [2, 4, 4, 2]:
-            raise ValueError(f"{what}: embeddings: frequencies and words are u16 sections, states and offsets u32")
-        chunk = entry.get("rans_chunk")
-        rans_validate(*rans, (N - 1) * E, bits, chunk, what=f"{what}: embeddings")
-    return dict(bits=bits, temporal=temporal, coding=coding, chunk=chunk, shape=tuple(shape), delta=delta, zero_point=zp,
-                levels=levels, rans=rans)
+    # frame 0 (coding 'packed': every frame) at its bit-width, the frames after it rANS coded
+    packed = _stored_levels(sec, "embeddings", N * E if coding == "packed" else E, bits, "packed", None, what)
+    coded = _stored_levels(sec, "embeddings", (N - 1) * E, bits, "rans", entry.get("rans_chunk"), what) if coding == "rans" else None
+    return dict(bits=bits, temporal=temporal, coding=coding, chunk=coded and coded.chunk, shape=tuple(shape), delta=delta,
+                zero_point=zp, levels=packed.words, rans=coded and list(coded.arrays), stored=(packed, coded))
+
+
+# ------------------------------------------------------------------------------------------ stored level tensors (GPU)
+def _upload(a, device):
+    """host array -> tensor on `device`, from a writable copy; unsigned travels as the signed dtype of the same width"""
+    a = np.array(a)
+    return torch.from_numpy(a.view(f"i{a.dtype.itemsize}") if a.dtype.kind == "u" else a).to(device)
+
+
+class _DeviceLevels:
+    """A StoredLevels uploaded once; `dequant(delta, zp, shape)` -> fp32 (level - zp) * delta, as often as wanted.  Legal
+    only on what `_stored_levels` returned: the coded arrays go to the kernel as trusted."""
+
+    def __init__(self, st, device):
+        self.st = st
+        if st.coding == "packed":
+            self.dev = (_upload(st.words, device),)
+        else:   # one host buffer, one upload: the four arrays side by side at 4-byte boundaries, viewed by type on the device
+            starts = np.cumsum([0] + [_align4(a.nbytes) for a in st.arrays])
+            host = np.zeros(int(starts[-1]), dtype=np.uint8)
+            for a, o in zip(st.arrays, starts):
+                host[o:o + a.nbytes] = a.view(np.uint8)
+            dev = torch.from_numpy(host).to(device)
+            self.dev = tuple(dev[o:o + a.nbytes].view(torch.int16 if a.dtype.itemsize == 2 else torch.int32)
+                             for a, o in zip(st.arrays, starts))
+
+    def dequant(self, delta, zp, shape):
+        st = self.st
+        if st.coding == "packed":
+            return ops.unpack_dequant(self.dev[0], delta, zp, shape, st.n_bits)
+        freq, states, offsets, words = self.dev
+        return ops.rans_decode_dequant(words, states, offsets, freq, delta, zp, shape, st.n_bits, st.chunk, trusted=True)
+
+
+# uint8 levels on the GPU -> the sections [(section name, tag, array)] that store them, one function per coding
+def _packed_section(name, levels_u8, n_bits):
+    return [(f"{name}.levels", "u32", ops.pack_levels(levels_u8, n_bits).cpu().numpy().view(np.uint32))]
+
+
+def _rans_sections(name, levels_u8, n_bits, chunk):
+    return [(f"{name}.{k}", tag, a) for (k, tag), a in zip(_RANS_PARTS, rans_encode(levels_u8.cpu().numpy(), n_bits, chunk))]
+
+
+def _section_bytes(sections):
+    return sum(_align4(np.asarray(a).size * np.dtype(_DTYPES[t]).itemsize) for _, t, a in sections)
+
+
+def _as_stored(sections):
+    """sections -> what `read_container` gives for the file they make: a writer puts this through the reader's own functions"""
+    return {name: np.asarray(a).reshape(-1).astype(_DTYPES[tag]) for name, tag, a in sections}
+
+
+def _scale_section(t):
+    """fp16 when every entry survives the round trip (true after AdaRound's init, quantizer.py:264-265), else fp32."""
+    t = t.detach().float().reshape(-1).cpu()
+    tag = "f16" if torch.equal(t.half().float(), t) else "f32"
+    return tag, t.numpy().astype(_DTYPES[tag])
 
 
 # ------------------------------------------------------------------------------------------ embeddings (GPU)
@@ -283,8 +365,7 @@ def quantise_embeddings(x, bits):
     step is at least 1e-8, an all-zero channel restores to exact zeros.  ValueError for bits outside 2..8 and for embeddings
     that are not finite."""
     x = _embedding_tensor(x)
-    if not isinstance(bits, int) or isinstance(bits, bool) or not 2 <= bits <= 8:
-        raise ValueError(f"embedding bits must be an integer in 2..8, got {bits!r}")
+    _check_bits(bits, 2, 8, "embedding bits")
     if not bool(torch.isfinite(x).all()):
         raise ValueError("embeddings are not finite: they cannot be quantised")
     delta, zp = ops.scale_init_max(x.transpose(0, 1).contiguous(), 2 ** bits, True)
@@ -292,6 +373,10 @@ def quantise_embeddings(x, bits):
     levels, _ = ops.embed_symbols(x, delta, zp, bits, False)
     restored = ops.embed_restore(levels.float(), delta, zp, x.shape, bits, False)
     return QuantisedEmbeddings(x, bits, delta, zp, levels, restored)
+
+
+# the kinds `write_stream`'s size summary files encode_embeddings' sections under, in the order it returns them
+_EMBED_KINDS = ("embedding_scales",) * 2 + ("embedding_levels",) + ("embedding_rans",) * len(_RANS_PARTS)
 
 
 @torch.no_grad()
@@ -305,76 +390,48 @@ def encode_embeddings(x, bits, mode, chunk=DEFAULT_CHUNK):
     q = x if isinstance(x, QuantisedEmbeddings) else quantise_embeddings(x, bits)
     if q.bits != bits:
         raise ValueError(f"embeddings were quantised to {q.bits} bits, asked to store {bits}")
-    if not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES:
-        raise ValueError(f"chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
+    _check_chunk(chunk, "encode_embeddings")
     N, C = q.shape[:2]
     temporal, coding = _EMBED_LAYOUT["packed" if N == 1 else mode]
     _, symbols = ops.embed_symbols(q.source, q.delta, q.zero_point, bits, temporal)
     entry = dict(bits=bits, scale_rows=C, temporal=temporal, coding=coding)
-    sections = []
-    for key, t in (("delta", q.delta), ("zero_point", q.zero_point)):
-        tag, arr = _scale_section(t)
-        sections.append((f"embeddings.{key}", tag, arr))
-    packed = symbols if coding == "packed" else symbols[0]
-    sections.append(("embeddings.levels", "u32", ops.pack_levels(packed, bits).cpu().numpy().view(np.uint32)))
+    sections = [(f"embeddings.{key}", *_scale_section(t)) for key, t in (("delta", q.delta), ("zero_point", q.zero_point))]
+    sections += _packed_section("embeddings", symbols if coding == "packed" else symbols[0], bits)
     if coding == "rans":
         entry["rans_chunk"] = chunk
-        coded = rans_encode(symbols[1:].cpu().numpy(), bits, chunk)
-        sections += [(f"embeddings.{k}", t, a) for k, t, a in zip(_EMBED_RANS, ("u16", "u32", "u32", "u16"), coded)]
+        sections += _rans_sections("embeddings", symbols[1:], bits, chunk)
     return entry, sections
-
-
-def _section_bytes(sections):
-    return sum(_align4(np.asarray(a).size * np.dtype(_DTYPES[t]).itemsize) for _, t, a in sections)
 
 
 @torch.no_grad()
 def restore_embeddings(emb, device):
-    """`embedding_sections`' result -> the fp32 embeddings (N, C, h, w) on `device`: the symbols through the kernels that
-    decode every other level section (a step of one and a zero point of zero leave the integers), then one
-    `ops.embed_restore`."""
-    def up(a):
-        a = np.array(a)   # a writable copy
-        view = {2: np.int16, 4: np.int32}[a.dtype.itemsize] if a.dtype.kind == "u" else a.dtype
-        return torch.from_numpy(a.view(view)).to(device)
-
-    N, C, h, w = emb["shape"]
-    E, bits = C * h * w, emb["bits"]
+    """`embedding_sections`' result -> the fp32 embeddings (N, C, h, w) on `device`: the symbols through the decode of every
+    other level tensor (a step of one and a zero point of zero leave the integers), then one `ops.embed_restore`."""
     one, zero = torch.ones(1, device=device), torch.zeros(1, device=device)
-    first = N * E if emb["coding"] == "packed" else E
-    sym = ops.unpack_dequant(up(emb["levels"]), one, zero, (first,), bits)
-    if emb["coding"] == "rans":
-        freq, states, offsets, words = (up(a) for a in emb["rans"])
-        rest = ops.rans_decode_dequant(words, states, offsets, freq, one, zero, ((N - 1) * E,), bits, emb["chunk"], trusted=True)
-        sym = torch.cat([sym, rest])
-    return ops.embed_restore(sym, up(emb["delta"]).float(), up(emb["zero_point"]).float(), (N, C, h, w), bits, emb["temporal"])
+    runs = [_DeviceLevels(st, device).dequant(one, zero, (st.n,)) for st in emb["stored"] if st is not None]
+    sym = runs[0] if len(runs) == 1 else torch.cat(runs)
+    delta, zp = _upload(emb["delta"], device).float(), _upload(emb["zero_point"], device).float()
+    return ops.embed_restore(sym, delta, zp, emb["shape"], emb["bits"], emb["temporal"])
 
 
 def _embedding_stream_sections(q, chunk, frames, device):
-    """write_stream's part for quantised embeddings: all three modes, the smallest kept, and what is kept decoded again on the
-    GPU from the very arrays the file will hold and compared with q.restored bit for bit.  -> (entry, sections, {mode: bytes})"""
+    """write_stream's part for quantised embeddings -> (entry, sections, {mode: bytes}): all three modes, the smallest kept and
+    read back from the very arrays the file will hold by the player's own functions: q.restored must come out bit for bit."""
     built = {m: encode_embeddings(q, q.bits, m, chunk) for m in EMBED_MODES}
     sizes = {m: _section_bytes(s) for m, (_, s) in built.items()}
     entry, sections = built[smallest_embedding_mode(sizes)]
     header = dict(arch="hnerv", frames=frames, embedding_shape=list(q.shape), embedding=entry)
-    sec = {name: np.asarray(a).reshape(-1).astype(_DTYPES[tag]) for name, tag, a in sections}
-    if not torch.equal(restore_embeddings(embedding_sections(header, sec, "write_stream"), device), q.restored):
+    if not torch.equal(restore_embeddings(embedding_sections(header, _as_stored(sections), "write_stream"), device), q.restored):
         raise RuntimeError("write_stream: the stored embedding levels do not reproduce the embeddings the model was evaluated on")
     return entry, sections, sizes
 
 
 # ------------------------------------------------------------------------------------------ writer
-def _scale_section(t):
-    """fp16 when every entry survives the round trip (true after AdaRound's init, quantizer.py:264-265), else fp32."""
-    t = t.detach().float().reshape(-1).cpu()
-    tag = "f16" if torch.equal(t.half().float(), t) else "f32"
-    return tag, t.numpy().astype(_DTYPES[tag])
-
-
-def _level_sections(q, x, name, coding, chunk):
-    """sections [(name, tag, array)] that store tensor x under quantiser q, the coding chosen ('packed' / 'rans') and the
-    entropy of its levels in bits.  Whatever is chosen is decoded again on the GPU and compared with q's hard-rounded forward
-    bit for bit, so a file that cannot reproduce the model is never written."""
+def _layer_side(q, x, name, prefix, kind, coding, chunk):
+    """One side of a layer, its weight (prefix '', kind 'weight') or its hard bias ('bias_', 'bias'): tensor x under quantiser q
+    as level sections in the coding chosen, then two scale sections -> ([(kind in the size summary, section)], the layer
+    entry's keys, entropy of the levels in bits).  The player's own host check and device decode read the level sections back
+    and q's hard-rounded forward must come out bit for bit, so a file that cannot reproduce the model is never written."""
     from .export import _entropy_bits, _levels
     from .quantization.quantizer import AdaRoundQuantizer
     if isinstance(q, AdaRoundQuantizer):
@@ -382,22 +439,23 @@ def _level_sections(q, x, name, coding, chunk):
     else:
         hard = ops.uaq_forward(x, q.delta.data, q.zero_point, q.n_levels)
     levels = _levels(q, x)
-    delta, zp = q.delta.detach().float().reshape(-1), q.zero_point.detach().float().reshape(-1)
-    words = ops.pack_levels(levels, q.n_bits)
-    entropy = _entropy_bits(levels, q.n_levels)   # as export_quantized computes it
+    chosen, secs = "packed", _packed_section(name, levels, q.n_bits)
     if coding != "packed":
-        coded = rans_encode(levels.cpu().numpy(), q.n_bits, chunk)
-        if coding == "rans" or sum(_align4(a.nbytes) for a in coded) < 4 * words.numel():
-            dev = [torch.from_numpy(a.view(np.int16 if a.dtype == np.uint16 else np.int32)).to(x.device) for a in coded]
-            freq, states, offsets, cw = dev
-            if not torch.equal(ops.rans_decode_dequant(cw, states, offsets, freq, delta, zp, x.shape, q.n_bits, chunk), hard):
-                raise RuntimeError("write_stream: coded levels do not reproduce the quantiser's output")
-            tags = ("u16", "u32", "u32", "u16")
-            kinds = ("rans_freq", "rans_states", "rans_offsets", "rans_words")
-            return [(f"{name}.{k}", t, a) for k, t, a in zip(kinds, tags, coded)], "rans", entropy
-    if not torch.equal(ops.unpack_dequant(words, delta, zp, x.shape, q.n_bits), hard):
-        raise RuntimeError("write_stream: packed levels do not reproduce the quantiser's output")
-    return [(f"{name}.levels", "u32", words.cpu().numpy().view(np.uint32))], "packed", entropy
+        coded = _rans_sections(name, levels, q.n_bits, chunk)
+        if coding == "rans" or _section_bytes(coded) < _section_bytes(secs):
+            chosen, secs = "rans", coded
+    stored = _stored_levels(_as_stored(secs), name, x.numel(), int(q.n_bits), chosen, chunk, "write_stream")
+    delta, zp = q.delta.detach().float().reshape(-1), q.zero_point.detach().float().reshape(-1)
+    if not torch.equal(_DeviceLevels(stored, x.device).dequant(delta, zp, x.shape), hard):
+        raise RuntimeError(f"write_stream: {'coded' if chosen == 'rans' else 'packed'} levels do not reproduce the quantiser's output")
+    kinds = [k for k, _ in _LEVEL_PARTS[chosen]] + ["delta", "zero_point"]
+    entry = {prefix + "n_bits": int(q.n_bits), prefix + "scale_rows": int(q.delta.numel())}
+    if chosen == "rans":
+        entry.update({prefix + "levels_coding": "rans", prefix + "rans_chunk": chunk})
+    for key, t in (("delta", q.delta), ("zero_point", q.zero_point)):
+        entry[f"{prefix}{key}_dtype"], arr = _scale_section(t)
+        secs.append((f"{name}.{key}", entry[f"{prefix}{key}_dtype"], arr))
+    return [(f"{kind}_{k}", s) for k, s in zip(kinds, secs)], entry, _entropy_bits(levels, q.n_levels)   # as export_quantized's
 
 
 def _check_decoder_shape(arch, cfg):
@@ -428,8 +486,8 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
         raise ValueError(f"bias must be 'soft' or 'hard', got {bias!r}")
     if coding not in CODINGS:
         raise ValueError(f"coding must be one of {CODINGS}, got {coding!r}")
-    if coding != "packed" and (not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES):
-        raise ValueError(f"chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
+    if coding != "packed":
+        _check_chunk(chunk, "write_stream")
     _check_decoder_shape(arch, cfg)
     emb = qemb = None
     if embedding_bits is not None and arch != "hnerv":
@@ -451,7 +509,7 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
     elif frames is None:
         raise ValueError("a NeRV stream needs the frame count: pass frames=")
     mods = [m for m in qnn.model.modules() if isinstance(m, QuantModule)]
-    layers, sections, nominal_bits, entropy_bits = [], [], 0, 0.0
+    layers, sections, nominal_bits, entropy_bits = [], [], 0, 0.0   # sections: [(kind in the size summary, (name, tag, array))]
     for i, m in enumerate(mods):
         wq, bq = m.weight_quantizer, m.bias_quantizer
         if not getattr(wq, "inited", True) or wq.delta is None or bq.delta is None or not m._hip_ok:
@@ -460,48 +518,29 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
         src = m.hadamard_weight if m.hadamard else m.weight.data
         if isinstance(wq, AdaRoundQuantizer) and wq.soft_targets:
             raise ValueError(f"layer {i}: weight quantiser still rounds softly; a stream stores hard decisions")
-        lay = dict(shape=list(m.weight.shape), c_in_stored=int(src.shape[1]), n_bits=int(wq.n_bits),
-                   scale_rows=int(wq.delta.numel()))
-        secs, chosen, e = _level_sections(wq, src, f"w{i}", coding, chunk)
-        sections += secs
-        entropy_bits += e
-        if chosen == "rans":
-            lay.update(levels_coding="rans", rans_chunk=chunk)
-        for key, t in (("delta", wq.delta), ("zero_point", wq.zero_point)):
-            lay[f"{key}_dtype"], arr = _scale_section(t)
-            sections.append((f"w{i}.{key}", lay[f"{key}_dtype"], arr))
-        if bias == "soft":
-            sections.append((f"b{i}.soft", "f32", bq(m.bias).detach().float().cpu().numpy()))
-        else:
-            lay.update(bias_n_bits=int(bq.n_bits), bias_scale_rows=int(bq.delta.numel()))
-            secs, chosen, e = _level_sections(bq, m.bias.data, f"b{i}", coding, chunk)
+        lay = dict(shape=list(m.weight.shape), c_in_stored=int(src.shape[1]))
+        sides = [(wq, src, f"w{i}", "", "weight")] + ([(bq, m.bias.data, f"b{i}", "bias_", "bias")] if bias == "hard" else [])
+        for side in sides:
+            secs, entry, e = _layer_side(*side, coding, chunk)
             sections += secs
+            lay.update(entry)
             entropy_bits += e
-            if chosen == "rans":
-                lay.update(bias_levels_coding="rans", bias_rans_chunk=chunk)
-            for key, t in (("delta", bq.delta), ("zero_point", bq.zero_point)):
-                lay[f"bias_{key}_dtype"], arr = _scale_section(t)
-                sections.append((f"b{i}.{key}", lay[f"bias_{key}_dtype"], arr))
+        if bias == "soft":
+            sections.append(("bias_soft", (f"b{i}.soft", "f32", bq(m.bias).detach().float().cpu().numpy())))
         layers.append(lay)
         nominal_bits += wq.n_bits * m.weight.numel() + bq.n_bits * m.bias.numel()   # as export_quantized counts them
     header = dict(arch=arch, cfg=cfg, frames=int(frames), hadamard=bool(qnn.hadamard), bias=bias, layers=layers,
                   embedding_shape=None)
-    emb_sizes = None
     if emb is not None:
         header["embedding_shape"] = list(emb.shape)
         if qemb is None:
-            sections.append(("embeddings", "f32", emb.cpu().numpy()))
+            sections.append(("embeddings", ("embeddings", "f32", emb.cpu().numpy())))
         else:
             header["embedding"], secs, emb_sizes = _embedding_stream_sections(qemb, chunk, int(frames), emb.device)
-            sections += secs
-    header, size = _write_container(path, header, sections)
+            sections += zip(_EMBED_KINDS, secs)
+    header, size = _write_container(path, header, [s for _, s in sections])
     kinds = {}
-    for s in header["sections"]:
-        if s["name"].startswith("embeddings."):
-            part = s["name"].split(".")[1]
-            kind = "embedding_" + ("levels" if part == "levels" else "rans" if part.startswith("rans_") else "scales")
-        else:
-            kind = "embeddings" if s["name"] == "embeddings" else ("weight_" if s["name"][0] == "w" else "bias_") + s["name"].split(".")[1]
+    for (kind, _), s in zip(sections, header["sections"]):
         kinds[kind] = kinds.get(kind, 0) + _align4(s["bytes"])
     nominal = math.ceil(nominal_bits / 8)
     coded = sum(v for k, v in kinds.items() if k[0] in "wb" and (k.endswith("_levels") or "_rans_" in k))
@@ -549,10 +588,23 @@ class StreamDecoder:
         if not torch.cuda.is_available():
             raise RuntimeError("neuroquant_amd needs an AMD GPU (no CPU path)")
         header, sec = read_container(path)
+        self._open_header(path, header, device, arithmetic)
+        stored = stored_tensors(header, sec, what=path)   # host validation of every level tensor, before any upload
+        stored_emb = embedding_sections(header, sec, what=path)   # ... and of quantised embeddings
+        with torch.no_grad():
+            self._load_layers(path, sec, stored)
+            self._load_embeddings(path, sec, stored_emb)
+        self._emb = list(self.embeddings.split(1))   # per-frame views: a decode gathers without a host -> device copy
+        self._operands = [dict() for _ in self.weights]   # per layer: 'bf16x3' / 'fp32' operand, built once
+        # 'half': the one sticky word every f16 launch of this decoder may raise and none clears
+        self._sat = torch.zeros(1, dtype=torch.int32, device=self.device) if self._lv_dtype == "f16" else None
+        torch.cuda.synchronize(self.device)
+
+    def _open_header(self, path, header, device, arithmetic):
+        """what the header alone decides: the arithmetic's operand dtype, the decoder's geometry and each layer's epilogue"""
         # the operand dtype of the levels path (ops.levels_operand / conv3_forward_levels_raw); None: no such path ('exact')
         self._lv_dtype = {"exact": None, "levels": "bf16", "half": "f16"}[arithmetic]
-        on_levels = self._lv_dtype is not None
-        if on_levels and header.get("hadamard"):
+        if self._lv_dtype is not None and header.get("hadamard"):
             raise ValueError(f"{path}: a Hadamard-domain file stores the levels of the TRANSFORMED weights, not the convolution's: "
                              f"arithmetic={arithmetic!r} does not apply")
         self.arithmetic, self.levels_used = arithmetic, {}
@@ -572,91 +624,64 @@ class StreamDecoder:
         self._r = [1] + [int(s) for s in strides] + [1]
         self._epi = [ops.EPI_PLAIN] + [ops.EPI_PS_GELU] * len(strides) + [ops.EPI_TANH]
 
-        def up(name):
-            a = np.array(sec[name])   # a writable copy; the packed words travel as int32, the dtype ops takes
-            return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(self.device)
+    def _dequant(self, sec, st, shape, integers=False):
+        """the level tensor `st` dequantised on the GPU by its scale sections -> (tensor, n, delta).  integers: n = level -
+        zero_point, the same uploaded arrays decoded once more with a step of one ((float(level) - zp) * 1 is exact); else None"""
+        delta, zp = (_upload(sec[f"{st.name}.{k}"], self.device).float() for k in ("delta", "zero_point"))
+        dev = _DeviceLevels(st, self.device)
+        w = dev.dequant(delta, zp, shape)
+        return w, (dev.dequant(torch.ones_like(delta), zp, shape) if integers else None), delta
 
-        coded = coded_tensors(header, sec, what=path)   # host validation of every coded tensor, before any upload
-        stored_emb = embedding_sections(header, sec, what=path)   # ... and of quantised embeddings
-
-        def levels(tag, i, lay, prefix, shape, n_bits, integers=False):
-            """the tensor stored as `{tag}{i}` in whichever coding the layer names, dequantised on the GPU.  integers: ->
-            (that tensor, n = level - zero_point, delta): the same kernel once more with a step of one, (float(level) - zp) * 1,
-            which is exact"""
-            name, coding = f"{tag}{i}", lay.get(prefix + "levels_coding", "packed")
-            delta, zp = up(f"{name}.delta").float(), up(f"{name}.zero_point").float()
-            if coding == "packed":
-                self.level_bytes["packed"] += sec[f"{name}.levels"].nbytes
-                self.level_tensors["packed"] += 1
-                packed = up(f"{name}.levels")
-                dequant = lambda step: ops.unpack_dequant(packed, step, zp, shape, n_bits)  # noqa: E731
-            else:
-                *parts, chunk = coded[name]
-                self.level_bytes["rans"] += sum(a.nbytes for a in parts)
-                self.level_tensors["rans"] += 1
-                # one host buffer, one upload: the four arrays side by side at 4-byte boundaries, viewed by type on the device
-                starts = np.cumsum([0] + [_align4(a.nbytes) for a in parts])
-                host = np.zeros(int(starts[-1]), dtype=np.uint8)
-                for a, o in zip(parts, starts):
-                    host[o:o + a.nbytes] = a.view(np.uint8)
-                dev = torch.from_numpy(host).to(self.device)
-                freq, states, offsets, words = (dev[o:o + a.nbytes].view(torch.int16 if a.dtype.itemsize == 2 else torch.int32)
-                                                for a, o in zip(parts, starts))
-                dequant = lambda step: ops.rans_decode_dequant(words, states, offsets, freq, step, zp, shape, n_bits,  # noqa: E731
-                                                               chunk, trusted=True)
-            w = dequant(delta)
-            return (w, dequant(torch.ones_like(delta)), delta) if integers else w
-
+    def _load_layers(self, path, sec, stored):
+        """weights, biases and (arithmetic 'levels' / 'half') the level operands of the layers that are eligible, in layer order"""
+        header, on_levels = self.header, self._lv_dtype is not None
         self.weights, self.biases = [], []
         self._levels = [None] * len(header["layers"])   # per layer: (levels operand, delta per output channel) where eligible
-        self.level_bytes = {"packed": 0, "rans": 0}   # bytes of the level sections this file stores, per coding (unpadded)
-        self.level_tensors = {"packed": 0, "rans": 0}
-        with torch.no_grad():
-            for i, lay in enumerate(header["layers"]):
-                co, ci, k, k2 = lay["shape"]
-                w = levels("w", i, lay, "", (co, lay["c_in_stored"], k, k2), lay["n_bits"], integers=on_levels)
-                if on_levels:
-                    w, n, delta = w
-                    # eligible: a 3 x 3 / 5 x 5 layer with integer n that bf16 holds exactly and finite steps; the reason a
-                    # layer is not stays on the decoder.  (The operand is then built without a second look at n: whatever
-                    # levels_operand still raises is a fault of this code, not a property of the file.)
-                    why = (f"kernel size {k} x {k2}" if k != k2 or k not in (3, 5) else
-                           "a step that is not finite" if not bool(torch.isfinite(delta).all()) else
-                           "level - zero_point is not an integer of magnitude <= 256" if not ops.levels_representable(n) else None)
-                    if why is None:
-                        self._levels[i] = (ops.levels_operand(n, checked=True, dtype=self._lv_dtype),
-                                           delta.reshape(-1).expand(co).contiguous())
-                    else:
-                        self.levels_ineligible[i] = why
-                    del n
-                if header["hadamard"]:
-                    w = ops.hadamard_along_channel_weight(w, n_out=ci)
-                elif lay["c_in_stored"] != ci:
-                    raise ValueError(f"{path}: layer {i} stores {lay['c_in_stored']} input channels outside the Hadamard domain")
-                if header["bias"] == "soft":
-                    b = up(f"b{i}.soft").float()
+        # the level tensors this file stores and the bytes of their sections (unpadded), per coding
+        self.level_tensors = {c: sum(st.coding == c for st in stored.values()) for c in ("packed", "rans")}
+        self.level_bytes = {c: sum(st.nbytes for st in stored.values() if st.coding == c) for c in ("packed", "rans")}
+        for i, lay in enumerate(header["layers"]):
+            co, ci, k, k2 = lay["shape"]
+            w, n, delta = self._dequant(sec, stored[f"w{i}"], (co, lay["c_in_stored"], k, k2), integers=on_levels)
+            if on_levels:
+                # eligible: a 3 x 3 / 5 x 5 layer with integer n that bf16 holds exactly and finite steps; the reason a
+                # layer is not stays on the decoder.  (The operand is then built without a second look at n: whatever
+                # levels_operand still raises is a fault of this code, not a property of the file.)
+                why = (f"kernel size {k} x {k2}" if k != k2 or k not in (3, 5) else
+                       "a step that is not finite" if not bool(torch.isfinite(delta).all()) else
+                       "level - zero_point is not an integer of magnitude <= 256" if not ops.levels_representable(n) else None)
+                if why is None:
+                    self._levels[i] = (ops.levels_operand(n, checked=True, dtype=self._lv_dtype),
+                                       delta.reshape(-1).expand(co).contiguous())
                 else:
-                    b = levels("b", i, lay, "bias_", (co,), lay["bias_n_bits"])
-                self.weights.append(w.contiguous())
-                self.biases.append(b.contiguous())
-            self.embedding_info = None   # quantised embeddings: {bits, coding, temporal, bytes (their sections, unpadded)}
-            if stored_emb is not None:
-                self.embeddings = restore_embeddings(stored_emb, self.device)
-                self.embedding_info = dict(bits=stored_emb["bits"], coding=stored_emb["coding"], temporal=stored_emb["temporal"],
-                                           bytes=sum(a.nbytes for n_, a in sec.items() if n_.startswith("embeddings.")))
-            elif self.arch == "hnerv":
-                self.embeddings = up("embeddings").float().view(header["embedding_shape"])
-            else:   # NeRV.encode(idx / n) for every frame: elementwise, so a row does not depend on its batch
-                from .models._layers import PositionEncoding
-                t = torch.arange(self.frames, device=self.device).float() / self.frames
-                self.embeddings = PositionEncoding(cfg["base"], cfg["level"])(t[:, None]).float()
+                    self.levels_ineligible[i] = why
+                del n
+            if header["hadamard"]:
+                w = ops.hadamard_along_channel_weight(w, n_out=ci)
+            elif lay["c_in_stored"] != ci:
+                raise ValueError(f"{path}: layer {i} stores {lay['c_in_stored']} input channels outside the Hadamard domain")
+            if header["bias"] == "soft":
+                b = _upload(sec[f"b{i}.soft"], self.device).float()
+            else:
+                b = self._dequant(sec, stored[f"b{i}"], (co,))[0]
+            self.weights.append(w.contiguous())
+            self.biases.append(b.contiguous())
+
+    def _load_embeddings(self, path, sec, stored_emb):
+        """one embedding per frame: restored from levels, the file's fp32 section, or (NeRV) the position code"""
+        self.embedding_info = None   # quantised embeddings: {bits, coding, temporal, bytes (their sections, unpadded)}
+        if stored_emb is not None:
+            self.embeddings = restore_embeddings(stored_emb, self.device)
+            self.embedding_info = dict(bits=stored_emb["bits"], coding=stored_emb["coding"], temporal=stored_emb["temporal"],
+                                       bytes=sum(a.nbytes for n_, a in sec.items() if n_.startswith("embeddings.")))
+        elif self.arch == "hnerv":
+            self.embeddings = _upload(sec["embeddings"], self.device).float().view(self.header["embedding_shape"])
+        else:   # NeRV.encode(idx / n) for every frame: elementwise, so a row does not depend on its batch
+            from .models._layers import PositionEncoding
+            t = torch.arange(self.frames, device=self.device).float() / self.frames
+            self.embeddings = PositionEncoding(self.cfg["base"], self.cfg["level"])(t[:, None]).float()
         if self.embeddings.shape[0] != self.frames:
             raise ValueError(f"{path}: {self.embeddings.shape[0]} embeddings for {self.frames} frames")
-        self._emb = list(self.embeddings.split(1))   # per-frame views: a decode gathers without a host -> device copy
-        self._operands = [dict() for _ in self.weights]   # per layer: 'bf16x3' / 'fp32' operand, built once
-        # 'half': the one sticky word every f16 launch of this decoder may raise and none clears
-        self._sat = torch.zeros(1, dtype=torch.int32, device=self.device) if self._lv_dtype == "f16" else None
-        torch.cuda.synchronize(self.device)
 
     def _takes_levels(self, i, x):
         """layer i runs on its integer levels for input x: eligible, bf16x3 precision, and the library offers the shape"""

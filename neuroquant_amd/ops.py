@@ -1818,19 +1818,26 @@ def pack_levels(levels_u8: torch.Tensor, n_bits: int) -> torch.Tensor:
     return words
 
 
+def _dequant_scales(what, delta, zp, shape):
+    """delta / zero_point of a dequantising decode on the GPU, checked against `shape`: one value per shape[0] (channel-wise) or
+    a single value -> (delta, zp, shape as a tuple of ints)"""
+    delta, zp = _dev(delta, "delta"), _dev(zp, "zero_point")
+    shape = tuple(int(s) for s in shape)
+    if delta.numel() != zp.numel() or delta.numel() not in (1, shape[0]):
+        raise ValueError(f"{what}: delta / zero_point must hold one value per output channel or a single value")
+    return delta, zp, shape
+
+
 def unpack_dequant(words: torch.Tensor, delta: torch.Tensor, zp: torch.Tensor, shape, n_bits: int) -> torch.Tensor:
     """packed words -> fp32 tensor of `shape`: (level - zp) * delta, the quantisers' own expression.  delta / zp hold one value
     per shape[0] (channel-wise) or a single value."""
     words = _dev_as(words, torch.int32, "words")
-    delta, zp = _dev(delta, "delta"), _dev(zp, "zero_point")
-    shape = tuple(int(s) for s in shape)
+    delta, zp, shape = _dequant_scales("unpack_dequant", delta, zp, shape)
     n = math.prod(shape)
     if not 1 <= int(n_bits) <= 8 or n <= 0:
         raise ValueError(f"unpack_dequant: n_bits must be 1..8 and the shape non-empty, got n_bits={n_bits}, shape {shape}")
     if words.numel() < packed_words(n, n_bits):
         raise ValueError(f"unpack_dequant: {words.numel()} words cannot hold {n} levels of {n_bits} bits")
-    if delta.numel() != zp.numel() or delta.numel() not in (1, shape[0]):
-        raise ValueError("unpack_dequant: delta / zero_point must hold one value per output channel or a single value")
     rows = delta.numel()
     w = torch.empty(shape, device=words.device, dtype=torch.float32)
     L.check(L.lib().nq_unpack_dequant(_p(words), _p(delta), _p(zp), _p(w), rows, n // rows, int(n_bits), _stream()),
@@ -1969,12 +1976,9 @@ def rans_decode_dequant(words, states, offsets, freq, delta: torch.Tensor, zp: t
                         trusted: bool = False) -> torch.Tensor:
     """rANS-coded levels -> fp32 tensor of `shape`: (level - zp) * delta, bit-identical to `unpack_dequant` of the same levels.
     delta / zp hold one value per shape[0] or a single value."""
-    shape = tuple(int(s) for s in shape)
+    delta, zp, shape = _dequant_scales("rans_decode_dequant", delta, zp, shape)
     n = math.prod(shape)
     words, states, offsets, freq = _rans_args(words, states, offsets, freq, n, n_bits, chunk, trusted, "rans_decode_dequant")
-    delta, zp = _dev(delta, "delta"), _dev(zp, "zero_point")
-    if delta.numel() != zp.numel() or delta.numel() not in (1, shape[0]):
-        raise ValueError("rans_decode_dequant: delta / zero_point must hold one value per output channel or a single value")
     w = torch.empty(shape, device=states.device, dtype=torch.float32)
     L.check(L.lib().nq_rans_decode(_p(words), _p(states), _p(offsets), _p(freq), n, int(n_bits), int(chunk), _p(delta), _p(zp),
                                    n // delta.numel(), None, _p(w), _stream()), "rans_decode_dequant")

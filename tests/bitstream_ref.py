@@ -11,7 +11,7 @@ import struct
 import numpy as np
 
 MAGIC = b"NQV1"
-DTYPES = {"u32": "<u4", "f16": "<f2", "f32": "<f4"}
+DTYPES = {"u16": "<u2", "u32": "<u4", "f16": "<f2", "f32": "<f4"}
 
 
 def align4(n):

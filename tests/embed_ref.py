@@ -8,9 +8,6 @@ x is (N, C, h, w) fp32, E = C*h*w.  One (delta, zero_point) per channel c from t
 Symbols, frame-major (N, E):  sym[t] = level[t], or (temporal) sym[0] = level[0], sym[t] = (level[t] - level[t-1]) mod 2^b.
 Restore: level[t] = (level[t-1] + sym[t]) & (2^b - 1);  value = (fp32(level) - zp[c]) * delta[c].
 """
-import json
-import struct
-
 import numpy as np
 
 import bitstream_ref as R
@@ -20,7 +17,6 @@ MODES = ("packed", "rans", "temporal")        # ties between equal sizes go in t
 LAYOUT = {"packed": (False, "packed"), "rans": (False, "rans"), "temporal": (True, "rans")}   # mode -> (temporal, coding)
 RANS_KINDS = ("rans_freq", "rans_states", "rans_offsets", "rans_words")
 RANS_TAGS = ("u16", "u32", "u32", "u16")
-DTYPES = dict(R.DTYPES, u16="<u2")
 F32 = np.float32
 
 
@@ -104,7 +100,7 @@ def sections(lv, delta, zp, b, mode, chunk=32768, encode=_ref_encode):
 
 
 def section_bytes(secs):
-    return sum(R.align4(np.asarray(a).size * np.dtype(DTYPES[t]).itemsize) for _, t, a in secs)
+    return sum(R.align4(np.asarray(a).size * np.dtype(R.DTYPES[t]).itemsize) for _, t, a in secs)
 
 
 def smallest(bytes_by_mode):
@@ -126,29 +122,3 @@ def restore_file(header, sec):
     entry, shape = header["embedding"], tuple(header["embedding_shape"])
     return restore(symbols_of(entry, sec, shape), sec["embeddings.delta"].astype(F32), sec["embeddings.zero_point"].astype(F32),
                    shape, entry["bits"], entry["temporal"])
-
-
-def read(path):
-    """bitstream_ref.read with the u16 sections a coded tensor has"""
-    data = open(path, "rb").read()
-    assert data[:4] == R.MAGIC
-    (hlen,) = struct.unpack("<I", data[4:8])
-    header = json.loads(data[8:8 + hlen].decode("utf-8"))
-    start = R.align4(8 + hlen)
-    out = {s["name"]: np.frombuffer(data, DTYPES[s["dtype"]], s["count"], start + s["offset"]) for s in header["sections"]}
-    return header, out, start
-
-
-def write(path, header, secs, version=1):
-    """bitstream_ref.write with the u16 sections a coded tensor needs"""
-    table, blobs, pos = [], [], 0
-    for name, tag, arr in secs:
-        raw = np.asarray(arr).reshape(-1).astype(DTYPES[tag]).tobytes()
-        table.append({"name": name, "dtype": tag, "count": int(np.asarray(arr).size), "offset": pos, "bytes": len(raw)})
-        blobs.append(raw.ljust(R.align4(len(raw)), b"\0"))
-        pos += len(blobs[-1])
-    header = dict(header, version=version, sections=table)
-    hj = json.dumps(header).encode("utf-8")
-    with open(path, "wb") as f:
-        f.write(R.MAGIC + struct.pack("<I", len(hj)) + hj.ljust(R.align4(8 + len(hj)) - 8, b"\0") + b"".join(blobs))
-    return header

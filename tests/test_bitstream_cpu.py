@@ -149,3 +149,46 @@ def test_read_container_rejects_damaged_files(tmp_path):
     def overlap(h):
         h["sections"][1]["offset"] -= 4
     rewrite(overlap, "overlap.nqv")
+
+
+def test_stored_tensors_checks_packed_tensors_on_the_host(tmp_path):
+    """A packed tensor is validated before any upload: its section present, u32 and exactly packed_words(n, n_bits) long."""
+    from neuroquant_amd.bitstream import coded_tensors, read_container, stored_tensors
+    path = tmp_path / "a.nqv"
+    _, sections, _ = _sample(path)
+    header, sec = read_container(str(path))
+    stored = stored_tensors(header, sec)
+    assert list(stored) == ["w0"]
+    w0 = stored["w0"]
+    assert (w0.name, w0.coding, w0.n, w0.n_bits, w0.chunk) == ("w0", "packed", 35, 3, None)
+    assert np.array_equal(w0.words, sections[0][2]) and len(w0.words) == R.packed_words(35, 3) == 4 and w0.nbytes == 16
+    assert coded_tensors(header, sec) == {}
+    words = sec["w0.levels"]
+    damaged = {"missing": {k: v for k, v in sec.items() if k != "w0.levels"},
+               "one word short": dict(sec, **{"w0.levels": words[:-1]}),
+               "one word long": dict(sec, **{"w0.levels": np.concatenate([words, words[:1]])}),
+               "f32": dict(sec, **{"w0.levels": words.view("<f4")})}
+    for what, bad in damaged.items():
+        with pytest.raises(ValueError, match="w0"):
+            stored_tensors(header, bad, what)
+        with pytest.raises(ValueError, match="w0"):     # the filter over it refuses the same files
+            coded_tensors(header, bad, what)
+
+
+def test_stored_tensors_on_a_coded_file(tmp_path):
+    from neuroquant_amd.bitstream import coded_tensors, read_container, stored_tensors
+    from test_rans_cpu import CHUNK, N_B, N_W, _coded_file
+    path = tmp_path / "c.nqv"
+    _coded_file(path)
+    header, sec = read_container(str(path))
+    stored = stored_tensors(header, sec)
+    assert sorted(stored) == ["b0", "w0"]
+    assert [(s.coding, s.n, s.n_bits, s.chunk) for s in (stored["w0"], stored["b0"])] == [("rans", N_W, 3, CHUNK), ("rans", N_B, 4, 64)]
+    coded = coded_tensors(header, sec)
+    assert sorted(coded) == ["b0", "w0"]
+    for name, chunk in (("w0", CHUNK), ("b0", 64)):
+        *parts, got_chunk = coded[name]
+        assert got_chunk == chunk and len(parts) == 4
+        for a, k in zip(parts, ("freq", "states", "offsets", "words")):
+            assert a is sec[f"{name}.rans_{k}"]
+        assert stored[name].nbytes == sum(a.nbytes for a in parts) and stored[name].words is parts[3]

@@ -322,6 +322,86 @@ def test_uncalibrated_extreme_widths(ops, golden, tmp_path, bits, channel_wise):
     _assert_plays_back(ops, qnn, lambda idx: emb[idx], path)
 
 
+# ------------------------------------------------------------------------------------------ layout of the file, open
+@pytest.fixture(scope="module")
+def hnerv_uncalibrated(golden):
+    """tiny HNeRV, bits [6,5,4,5,5,6,6], quantisers straight after their 'max' initialisation; shared, read-only."""
+    _, qnn, emb = _quant_model(golden, "traj_hnerv.npz", "hnerv", False)
+    return qnn, emb
+
+
+RANS_PARTS = ("rans_freq", "rans_states", "rans_offsets", "rans_words")
+HEADER_KEYS = {"arch", "cfg", "frames", "hadamard", "bias", "layers", "embedding_shape", "version", "sections"}
+LAYER_KEYS = {"shape", "c_in_stored", "n_bits", "scale_rows", "delta_dtype", "zero_point_dtype"}
+HARD_KEYS = {"bias_n_bits", "bias_scale_rows", "bias_delta_dtype", "bias_zero_point_dtype"}
+
+
+def test_section_order_and_header_keys(hnerv_uncalibrated, tmp_path):
+    """The order of the sections is part of the format's bytes (the header is written with sorted keys, the sections are
+    not sorted): per layer the weight's level sections, its two scales, then the bias; the embeddings last."""
+    from neuroquant_amd.bitstream import write_stream
+    qnn, emb = hnerv_uncalibrated
+    L = len(BITS)
+
+    def names(path, **kw):
+        write_stream(qnn, str(path), "hnerv", dict(TINY_HNERV), embeddings=emb, **kw)
+        header, _, _ = R.read(str(path))
+        return header, [s["name"] for s in header["sections"]]
+
+    header, got = names(tmp_path / "soft.nqv", bias="soft", coding="packed")
+    assert got == [f"{t}{i}.{k}" for i in range(L) for t, k in (("w", "levels"), ("w", "delta"), ("w", "zero_point"), ("b", "soft"))
+                   ] + ["embeddings"]
+    assert set(header) == HEADER_KEYS and all(set(lay) == LAYER_KEYS for lay in header["layers"]) and len(header["layers"]) == L
+
+    header, got = names(tmp_path / "hard.nqv", bias="hard", coding="rans", chunk=64)
+    assert got == [f"{t}{i}.{k}" for i in range(L) for t in "wb" for k in RANS_PARTS + ("delta", "zero_point")] + ["embeddings"]
+    coded_keys = {"levels_coding", "rans_chunk", "bias_levels_coding", "bias_rans_chunk"}
+    assert set(header) == HEADER_KEYS and all(set(lay) == LAYER_KEYS | HARD_KEYS | coded_keys for lay in header["layers"])
+
+    header, got = names(tmp_path / "emb.nqv", bias="soft", coding="packed", embedding_bits=6)
+    coded = header["embedding"]["coding"] == "rans"
+    assert got == [f"{t}{i}.{k}" for i in range(L) for t, k in (("w", "levels"), ("w", "delta"), ("w", "zero_point"), ("b", "soft"))
+                   ] + ["embeddings.delta", "embeddings.zero_point", "embeddings.levels"] + (
+                       [f"embeddings.{k}" for k in RANS_PARTS] if coded else [])
+    assert set(header) == HEADER_KEYS | {"embedding"} and all(set(lay) == LAYER_KEYS for lay in header["layers"])
+
+
+def test_open_decodes_each_tensor_from_one_upload_and_refuses_on_the_host(hnerv_uncalibrated, tmp_path):
+    """'levels' takes each weight twice from the arrays it uploaded once (its own step, then a step of one): the weights are
+    those of 'exact'.  A coded section one word short is refused by the host check, before any kernel."""
+    from neuroquant_amd.bitstream import StreamDecoder, write_stream
+    qnn, emb = hnerv_uncalibrated
+    path = str(tmp_path / "hard.nqv")
+    write_stream(qnn, path, "hnerv", dict(TINY_HNERV), embeddings=emb, bias="hard", coding="rans", chunk=64)
+    exact, levels = StreamDecoder(path, arithmetic="exact"), StreamDecoder(path, arithmetic="levels")
+    assert len(exact.weights) == len(levels.weights) == len(BITS)
+    for a, b in zip(exact.weights + exact.biases, levels.weights + levels.biases):
+        assert torch.equal(a, b)
+    header, sec, _ = R.read(path)
+    want = sum(a.nbytes for name, a in sec.items() if name[0] in "wb" and ".rans_" in name)
+    for dec in (exact, levels):
+        assert dec.level_tensors == {"packed": 0, "rans": 14} and dec.level_bytes == {"packed": 0, "rans": want}
+
+    def refused_one_short(src, victim):
+        header, sec, _ = R.read(src)
+        assert len(sec[victim]) > 0
+        bad = str(tmp_path / "short.nqv")
+        head = {k: v for k, v in header.items() if k not in ("version", "sections")}
+        R.write(bad, head, [(s["name"], s["dtype"], sec[s["name"]][:-1] if s["name"] == victim else sec[s["name"]])
+                            for s in header["sections"]])
+        assert len(R.read(bad)[1][victim]) == len(sec[victim]) - 1
+        with pytest.raises(ValueError, match=victim.split(".")[0]):
+            StreamDecoder(bad)
+
+    # chunks of 64 symbols give a lane one symbol, which never emits a word: every `rans_words` of this file is empty.  The
+    # states of w0 lose an entry here; the words of a tensor that has some, in a file of larger chunks, below.
+    assert len(sec["w0.rans_words"]) == 0
+    refused_one_short(path, "w0.rans_states")
+    longer = str(tmp_path / "hard4096.nqv")
+    write_stream(qnn, longer, "hnerv", dict(TINY_HNERV), embeddings=emb, bias="hard", coding="rans", chunk=4096)
+    refused_one_short(longer, "w1.rans_words")
+
+
 # ------------------------------------------------------------------------------------------ drivers
 def test_drivers_export_and_play_back(tmp_path):
     """calibrate_network --export_stream writes a stream whose playback (a fresh child process running the decode_stream

@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import bitstream_ref as R
 import embed_ref as E
 import rans_ref
 
@@ -77,7 +78,7 @@ def _file(tmp_path, shape=(4, 3, 2, 2), b=5, mode="temporal", name="e.nqv"):
     header = dict(arch="hnerv", cfg={}, frames=shape[0], hadamard=False, bias="soft", layers=[], embedding_shape=list(shape),
                   embedding=entry)
     path = str(tmp_path / name)
-    E.write(path, header, secs)
+    R.write(path, header, secs)
     return path, x, d, z, lv
 
 

@@ -165,7 +165,7 @@ def test_each_layout_opens_to_the_restored_embeddings(ops, calibrated, tmp_path,
     qnn, emb, q = calibrated
     base = tmp_path / "base.nqv"
     write_stream(qnn, str(base), "hnerv", dict(TINY_HNERV), embeddings=q.restored)
-    header, sec, _ = E.read(str(base))
+    header, sec, _ = R.read(str(base))
     entry, secs = encode_embeddings(q, 6, mode, 64)
     temporal, coding = E.LAYOUT[mode]
     assert entry == dict(bits=6, scale_rows=emb.shape[1], temporal=temporal, coding=coding, **({"rans_chunk": 64} if coding == "rans" else {}))
@@ -175,12 +175,12 @@ def test_each_layout_opens_to_the_restored_embeddings(ops, calibrated, tmp_path,
     want_entry, want_secs = E.sections(lv, d, z, 6, mode, 64)
     assert want_entry == entry and [(n, t) for n, t, _ in secs] == [(n, t) for n, t, _ in want_secs]
     for (name, tag, a), (_, _, r) in zip(secs, want_secs):
-        assert np.asarray(a).astype(E.DTYPES[tag]).tobytes() == np.asarray(r).astype(E.DTYPES[tag]).tobytes(), name
+        assert np.asarray(a).astype(R.DTYPES[tag]).tobytes() == np.asarray(r).astype(R.DTYPES[tag]).tobytes(), name
     # the base file with its fp32 embeddings replaced
     kept = [(s["name"], s["dtype"], sec[s["name"]]) for s in header["sections"] if s["name"] != "embeddings"]
     head = {k: v for k, v in header.items() if k not in ("sections", "version")}
     path = tmp_path / (mode + ".nqv")
-    E.write(str(path), dict(head, embedding=entry), kept + secs)
+    R.write(str(path), dict(head, embedding=entry), kept + secs)
     dec = StreamDecoder(str(path))
     assert dec.embeddings.dtype == torch.float32 and torch.equal(dec.embeddings, q.restored)
     h2, s2 = read_container(str(path))
@@ -205,7 +205,7 @@ def test_write_stream_keeps_the_smallest_layout(ops, calibrated, tmp_path, b, co
     sizes = _ref_sizes(E.levels(emb.cpu().numpy(), d, z, b), d, z, b)
     mode = E.smallest(sizes)
     print("tiny HNeRV, %d-bit embeddings %s: %s -> %s" % (b, tuple(emb.shape), sizes, mode))
-    header, sec, _ = E.read(str(path))
+    header, sec, _ = R.read(str(path))
     temporal, ecoding = E.LAYOUT["packed" if emb.shape[0] == 1 else mode]
     e = header["embedding"]
     assert (e["bits"], e["temporal"], e["coding"], e["scale_rows"]) == (b, temporal, ecoding, emb.shape[1])
@@ -235,7 +235,7 @@ def test_default_file_is_unchanged(ops, calibrated, tmp_path):
     for coding in ("packed", "rans"):
         path = tmp_path / (coding + ".nqv")
         s = write_stream(qnn, str(path), "hnerv", dict(TINY_HNERV), embeddings=emb, coding=coding)
-        header, sec, _ = E.read(str(path))
+        header, sec, _ = R.read(str(path))
         assert "embedding" not in header and "embedding" not in s and "embedding_restored" not in s
         assert sec["embeddings"].dtype == np.dtype("<f4") and np.array_equal(sec["embeddings"].reshape(emb.shape), emb.cpu().numpy())
         assert not any(n.startswith("embeddings.") for n in sec) and not any(k.startswith("embedding_") for k in s["section_bytes"])
@@ -291,7 +291,7 @@ def test_write_stream_takes_both_sides_of_the_choice_on_the_trained_fixture(ops,
         sizes = _ref_sizes(E.levels(emb.cpu().numpy(), d, z, b), d, z, b)
         print("HNeRV-3M fixture, %d-bit embeddings: %s -> %s (fp32: %d bytes)" % (b, sizes, s["embedding"]["mode"], 4 * emb.numel()))
         assert s["embedding"]["mode"] == mode == E.smallest(sizes) and s["embedding"]["mode_bytes"] == sizes
-        header, sec, _ = E.read(path)
+        header, sec, _ = R.read(path)
         assert (header["embedding"]["temporal"], header["embedding"]["coding"]) == E.LAYOUT[mode]
         assert np.array_equal(E.restore_file(header, sec), q.restored.cpu().numpy())
         dec = StreamDecoder(path)
@@ -338,5 +338,5 @@ def test_drivers_calibrate_export_and_play_back_quantised_embeddings(tmp_path, c
     info = res["embedding_info"]
     assert info["bits"] == 6 and info["coding"] in ("packed", "rans") and isinstance(info["temporal"], bool) and info["bytes"] > 0
     assert re.search(r"embeddings: 6 bits, (packed|rans)", out)
-    header, sec, _ = E.read(str(stream))
+    header, sec, _ = R.read(str(stream))
     assert header["embedding"]["bits"] == 6 and "embeddings" not in sec

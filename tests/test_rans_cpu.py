@@ -3,12 +3,12 @@ the package's numpy encoder against it byte for byte, the size conditions `auto`
 nq_rans_decode's argument checks before any device call, `u16` sections in the container reader, and the player's host
 validation of damaged coded files, one file per rule."""
 import ctypes
-import json
 import struct
 
 import numpy as np
 import pytest
 
+import bitstream_ref
 import rans_ref as R
 
 L = 1 << 16
@@ -204,22 +204,6 @@ def test_ops_refuse_cpu_tensors():
 
 
 # ------------------------------------------------------------------------------------------ container
-def _write(path, header, sections):
-    """a version-1 container written here: sections [(name, dtype tag, array)] -> the header as written"""
-    fmt = {"u16": "<u2", "u32": "<u4", "f16": "<f2", "f32": "<f4"}
-    table, blobs, pos = [], [], 0
-    for name, tag, arr in sections:
-        raw = np.asarray(arr).reshape(-1).astype(fmt[tag]).tobytes()
-        table.append({"name": name, "dtype": tag, "count": int(np.asarray(arr).size), "offset": pos, "bytes": len(raw)})
-        blobs.append(raw.ljust((len(raw) + 3) // 4 * 4, b"\0"))
-        pos += len(blobs[-1])
-    header = dict(header, version=1, sections=table)
-    hj = json.dumps(header).encode("utf-8")
-    with open(path, "wb") as fh:
-        fh.write(b"NQV1" + struct.pack("<I", len(hj)) + hj.ljust((8 + len(hj) + 3) // 4 * 4 - 8, b"\0") + b"".join(blobs))
-    return header
-
-
 N_W, N_B, CHUNK = 16 * 16 * 3 * 3, 16, 1024          # three chunks, the last short; 16 symbols a lane: words exist
 
 
@@ -245,7 +229,7 @@ def _coded_file(path, mutate=None, mutate_header=None):
         mutate_header(lay)
     header = dict(arch="hnerv", cfg=dict(crop_h=2, crop_w=2), frames=1, hadamard=False, bias="hard", embedding_shape=None,
                   layers=[lay])
-    return _write(str(path), header, sections), sections, wl, bl
+    return bitstream_ref.write(str(path), header, sections), sections, wl, bl
 
 
 def test_read_container_parses_u16_sections(tmp_path):
@@ -263,7 +247,7 @@ def test_read_container_parses_u16_sections(tmp_path):
     assert R.read_coded_levels(str(path), "w0") == wl.tolist() and R.read_coded_levels(str(path), "b0") == bl.tolist()
     # a section of no entries (a constant tensor's words) is a legal section, also as the last one of a file
     empty = tmp_path / "e.nqv"
-    _write(str(empty), dict(layers=[]), [("a", "u16", np.arange(3)), ("w0.rans_words", "u16", np.zeros(0)), ("z", "u16", np.zeros(0))])
+    bitstream_ref.write(str(empty), dict(layers=[]), [("a", "u16", np.arange(3)), ("w0.rans_words", "u16", np.zeros(0)), ("z", "u16", np.zeros(0))])
     _, sec = read_container(str(empty))
     assert sec["a"].tolist() == [0, 1, 2] and sec["w0.rans_words"].size == 0 and sec["z"].size == 0
 

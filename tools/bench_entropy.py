@@ -13,8 +13,8 @@ Per chunk = 4096 ... 262144: file bytes for coding packed / rans / auto, coded l
 StreamDecoder open time of each file (host clock around read + validate + upload + decode + synchronise; median, min and max
 over --opens opens, the three files taking turns) and decode frames/s at B = 1 (host clock around 4 sweeps over all frames,
 median of 5 windows).  --parent FILE times the StreamDecoder of another copy of neuroquant_amd/bitstream.py (the parent
-commit's) on the packed file in the same run, taking turns with the current one.  Prints ONE JSON object and writes it to
---out.  Needs the GPU."""
+commit's) on the packed file and on the first coded one (coding rans, chunk 4096) in the same run, taking turns with the
+current one.  Prints ONE JSON object and writes it to --out.  Needs the GPU."""
 import argparse
 import importlib.util
 import json
@@ -100,9 +100,9 @@ def measure(qnn, emb, opens, parent, tmp, tag):
     res = dict(frames=n, levels=int(sum(w.numel() for w in ref.weights)), total_bytes_nominal=sp["total_bytes_nominal"],
                entropy_level_bytes=sp["entropy_level_bytes"], packed_file_bytes=sp["file_bytes"],
                packed_level_bytes=sp["coded_level_bytes"], chunks=[])
-    if parent:
-        res["packed_open_ms_parent_vs_current"] = time_opens({"parent": load_parent(parent), "current": StreamDecoder},
-                                                             {"parent": packed, "current": packed}, opens)
+    versus = {"parent": load_parent(parent), "current": StreamDecoder} if parent else None
+    if versus:
+        res["packed_open_ms_parent_vs_current"] = time_opens(versus, dict.fromkeys(versus, packed), opens)
     res["packed_decode_fps_B1"] = decode_fps(ref, n)
     for chunk in CHUNKS:
         paths, row = {"packed": packed}, {"chunk": chunk}
@@ -116,6 +116,8 @@ def measure(qnn, emb, opens, parent, tmp, tag):
                            "level_bytes_over_entropy": round(s["coded_level_bytes"] / s["entropy_level_bytes"], 5),
                            "file_bytes_over_packed": round(s["file_bytes"] / sp["file_bytes"], 5),
                            "write_seconds": round(time.perf_counter() - t0, 2)}
+        if versus and chunk == CHUNKS[0]:   # the first coded file: every tensor through the rANS upload and decode
+            res["rans_open_ms_parent_vs_current"] = time_opens(versus, dict.fromkeys(versus, paths["rans"]), opens)
         row["open_ms"] = time_opens({k: StreamDecoder for k in paths}, paths, opens)
         for coding in ("rans", "auto"):
             dec = StreamDecoder(paths[coding])
