@@ -579,6 +579,34 @@ NQ_API int nq_yuv420_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t n, int 
                         nq_stream_t stream);
 NQ_API int nq_yuv420_sse(const uint8_t* a, const uint8_t* b, uint64_t* sse, int64_t n, int H, int W, nq_stream_t stream);
 
+/* ---- reconstruction loss in the 8-bit YUV 4:2:0 domain (additive: nq_abi_version() stays 7) ----
+ * pred, tgt: (B, 3, H, W) fp32 planar RGB, H and W even; matrix / full_range as above; weights wy, wu, wv >= 0 with a positive
+ * sum.  The transform is linear, so it is applied to d = pred - tgt (offsets cancel, nothing is clamped), fp32, uncontracted:
+ *   dy = (Kr d_r + Kg d_g) + Kb d_b;  dcb = (d_b - dy) icb;  dcr = (d_r - dy) icr          per pixel
+ *   eY = sY dy per pixel;  eU = sC mean2x2(dcb), eV = sC mean2x2(dcr) per 2 x 2 block, the box of nq_frames_to_yuv420
+ *   sY = 219/255, sC = 224/255 in limited range, both 1 in full range: errors are 8-bit code units / 255
+ *   MSE_Y = sum eY^2 / (B H W);  MSE_U = sum eU^2 / (B H W / 4);  MSE_V likewise
+ *   L = 3 (wy MSE_Y + wu MSE_U + wv MSE_V) / (wy + wu + wv)      (3: the scale of nq_l2_loss, a sum over three channels)
+ * -10 log10(MSE_plane) is the plane PSNR of the unrounded codes nq_frames_to_yuv420 would round.
+ *   loss[4] = {L, MSE_Y, MSE_U, MSE_V}.  A zero weight removes its plane from L and from the gradient exactly.
+ *   Target: exactly one of `tgt` and `cache_u8` (N, 3, H, W) + idx[B] is non-NULL; tgt = cache[idx[b]] / 255, the arithmetic of
+ *   nq_gather_frames_u8.
+ *   db == NULL: grad (B, 3, H, W) = gscale dL/dpred, exact: a pixel receives its own luma term and a quarter of its block's two
+ *   chroma terms.  db != NULL (tanh head, the contract of nq_l2_loss_tanh_head): grad = that value * 0.5 * (1 - (2 pred - 1)^2),
+ *   the gradient at the head conv's output, bit-identical to nq_tanh_out_backward of the db == NULL result; db[3] = its sums over
+ *   frames and pixels.
+ *   ws: nq_yuv420_loss_ws_floats(B, H, W) floats (0 for arguments the entry refuses).  One streaming launch (2 rows x 4 columns
+ *   per thread with 16-byte accesses when W % 4 == 0, pred / tgt / grad are 16-byte and the cache 4-byte aligned; else one thread
+ *   per 2 x 2 block) + one launch that adds the workgroups' partial sums in a fixed order: no atomics, bit-identical from call
+ *   to call.
+ * NQ_ERR_INVALID, before the device is touched, for null pointers, both or neither target, non-positive or odd H or W, B <= 0,
+ * matrix or full_range outside {0, 1}, a negative or non-finite weight, a zero weight sum and B * 3 * H * W past int64;
+ * NQ_ERR_UNSUPPORTED for more than 2^31 - 1 workgroups. */
+NQ_API int64_t nq_yuv420_loss_ws_floats(int B, int H, int W);
+NQ_API int nq_yuv420_loss(const float* pred, const float* tgt, const uint8_t* cache_u8, const int64_t* idx, float* loss, float* grad,
+                   float* db, float* ws, int B, int H, int W, int matrix, int full_range, float wy, float wu, float wv,
+                   float gscale, nq_stream_t stream);
+
 /* Entropy-coded levels: 64-lane interleaved rANS, one frequency table per tensor (probabilities in units of
  * 1 / 4096), 32-bit states >= 2^16, 16-bit words.  The n levels (flat, C order) are cut into chunks of `chunk` symbols (a
  * multiple of 64, the last may be short); lane l of a chunk owns its symbols l, l + 64, ...  One wavefront decodes one chunk.

@@ -12,6 +12,9 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     (--precision_file bits.json takes the bit-widths from `bit_assign --budget_bytes N --out bits.json`;
     --synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --data_path clip.y4m / clip.yuv reads an 8-bit
     YUV 4:2:0 clip instead of a directory of PNGs (--yuv_size, --yuv_matrix, --yuv_range, --yuv_frames; DESIGN.md §16);
+    --loss_domain yuv420 calibrates on the weighted plane MSEs of the 8-bit YUV 4:2:0 codes instead of RGB squared error
+    (--yuv_weights WY WU WV, default 6 1 1; matrix and range from --yuv_matrix / --yuv_range) and every evaluation also logs
+    PSNR-Y / U / V and their 6:1:1 mean: DESIGN.md §19;
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
     packed at their bit-width and entropy-coded levels; --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
@@ -44,6 +47,10 @@ def parse_args(argv):
     p.add_argument('--data_path', type=str)
     p.add_argument('--synthetic', type=int, default=0, help='use N synthetic frames instead of --data_path')
     add_yuv_args(p)
+    p.add_argument('--loss_domain', type=str, default='rgb', choices=['rgb', 'yuv420'],
+                   help='reconstruction loss of the calibration: RGB mean squared error, or the weighted plane MSEs of the 8-bit '
+                        'YUV 4:2:0 codes (--yuv_matrix, --yuv_range, --yuv_weights; DESIGN.md §19)')
+    add_yuv_loss_args(p)
     p.add_argument('--vid', type=str, default='Bunny')
     p.add_argument('--data_split', type=str, default='1_1_1')
     p.add_argument('--batch_size', default=12, type=int)
@@ -129,6 +136,28 @@ def add_yuv_args(p):
     p.add_argument('--yuv_frames', type=int, default=None, help='use the first N frames of a YUV clip')
 
 
+def add_yuv_loss_args(p):
+    """The flag of the YUV 4:2:0 objective that calibration and training share (matrix and range: add_yuv_args)."""
+    p.add_argument('--yuv_weights', type=float, nargs=3, default=[6.0, 1.0, 1.0], metavar=('WY', 'WU', 'WV'),
+                   help='plane weights of the YUV 4:2:0 objective (--loss_domain yuv420 / loss: yuv420; DESIGN.md §19)')
+
+
+def yuv_loss_params(args):
+    """matrix / full_range / weights of the YUV 4:2:0 objective (ops.yuv420_loss) and of the PSNR-Y / U / V evaluation: the
+    --yuv_matrix and --yuv_range that describe a clip (bt709, limited when unset; a .y4m / .yuv --data_path without --yuv_range
+    gives its own range) and --yuv_weights."""
+    from ..videoio import is_video_file
+    rng = getattr(args, 'yuv_range', None)
+    if rng not in (None, 'limited', 'full'):
+        raise ValueError(f"yuv_range must be 'limited' or 'full', got {rng!r}")
+    full = rng == 'full'
+    path = getattr(args, 'data_path', None)
+    if rng is None and not getattr(args, 'synthetic', 0) and path and is_video_file(path):
+        full = open_yuv_clip(args, path)[3]
+    return dict(matrix=getattr(args, 'yuv_matrix', None) or 'bt709', full_range=bool(full),
+                weights=tuple(getattr(args, 'yuv_weights', None) or ops.YUV_LOSS_WEIGHTS))
+
+
 def open_yuv_clip(args, path):
     """The clip at `path` as the yuv_* attributes of args describe it -> (YuvFile, frames to use, matrix, full_range)."""
     from ..videoio import open_yuv, parse_size
@@ -180,6 +209,7 @@ def load_frames(args, cfg, device):
 
 
 METRIC_NAMES = ['pred_seen_psnr', 'pred_seen_ssim', 'pred_unseen_psnr', 'pred_unseen_ssim']   # reference args.metric_names
+YUV_METRIC_NAMES = ['psnr_y', 'psnr_u', 'psnr_v', 'psnr_yuv_611']    # added by --loss_domain yuv420 (the player's keys)
 
 
 @torch.no_grad()
@@ -192,6 +222,10 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
     n = len(cache)
     dev = cache.frames.device
     with_ssim = min(cache.frames.shape[-2:]) > 160
+    # --loss_domain yuv420: also the figure that objective is after, PSNR of the 8-bit Y / U / V planes of the output against
+    # those of the cached ground truth (both through ops.frames_to_yuv420), in the player's format
+    yuv = yuv_loss_params(args) if getattr(args, 'loss_domain', 'rgb') == 'yuv420' else None
+    psnr_yuv = []
     psnr, ssim, embeds, dec_times = [], [], [], []
     for i in range(n):
         idx = torch.tensor([i], device=dev)
@@ -206,6 +240,10 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
         psnr.append(ops.frame_psnr(out, img))
         if with_ssim:
             ssim.append(ops.ms_ssim(out, img))
+        if yuv is not None:
+            h, w = img.shape[-2:]
+            psnr_yuv.append(ops.yuv420_psnr(ops.frames_to_yuv420(out, yuv['matrix'], yuv['full_range']),
+                                            ops.frames_to_yuv420(img, yuv['matrix'], yuv['full_range']), h, w))
         if i % args.print_freq == 0 or i == n - 1:
             logging.info('[{}], Eval at Step [{}/{}], FPS {}, PSNR {}, MS-SSIM {}'.format(
                 datetime.now().strftime("%Y/%m/%d %H:%M:%S"), i + 1, n,
@@ -219,6 +257,12 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
     res = [psnr[seen].mean() if seen else torch.zeros(()), psnr[unseen].mean() if unseen else torch.zeros(())]
     args.eval_metrics = dict(zip(METRIC_NAMES, [res[0], ssim[seen].mean() if seen else torch.zeros(()),
                                                 res[1], ssim[unseen].mean() if unseen else torch.zeros(())]))
+    if yuv is not None:   # over all frames, as the player reports them: means of decibels, 6:1:1 per frame
+        p = torch.cat(psnr_yuv).cpu()                  # (frames, 3) float64
+        y, u, v = p.mean(0)
+        m611 = ((6.0 * p[:, 0] + p[:, 1] + p[:, 2]) / 8.0).mean()
+        args.eval_metrics.update(dict(zip(YUV_METRIC_NAMES, [y, u, v, m611])))
+        logging.info('yuv420: PSNR-Y {} U {} V {} | 6:1:1 {}'.format(*(RoundTensor(t, 2) for t in (y, u, v, m611))))
     model.train()
     return res, embeds
 
@@ -227,7 +271,7 @@ def report_line(tag, args):
     """'<tag>: best_pred_seen_psnr: .. | best_pred_seen_ssim: .. | best_pred_unseen_psnr: .. | best_pred_unseen_ssim: ..' from the
     metrics the last evaluate() left on args (the reference's print_str, calibrate_network.py:212-217)."""
     return (tag + ': ' if tag else '') + ' | '.join(
-        f'best_{k}: {RoundTensor(v, 4 if k.endswith("ssim") else 2)}' for k, v in args.eval_metrics.items())
+        f'best_{k}: {RoundTensor(v, 4 if k.endswith("ssim") else 2)}' for k, v in args.eval_metrics.items() if k in METRIC_NAMES)
 
 
 def calibrate(args, cfg):
@@ -299,11 +343,15 @@ def calibrate(args, cfg):
     report('Weight quantization w/o opt', evaluate(qnn, cache, args, cfg, embeddings=stored)[0])
 
     logging.info('average bit-width: {}'.format(args.qbits))
+    loss_domain = getattr(args, 'loss_domain', 'rgb')
+    if loss_domain == 'yuv420':
+        logging.info('reconstruction loss: YUV 4:2:0 plane MSEs, {}'.format(yuv_loss_params(args)))
     start = datetime.now()
     qnn.set_quant_state(weight_quant=True)
     model_reconstruction(qnn, cali_data=cali_data, gt=train_loader, arch=args.arch, batch_size=args.batch_size,
                          iters=args.iters_w, weight=args.weight, opt_mode='mse', hadamard=args.hadamard,
-                         b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr)
+                         b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr,
+                         loss_domain=loss_domain, yuv=yuv_loss_params(args) if loss_domain == 'yuv420' else None)
     torch.cuda.synchronize()
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
 

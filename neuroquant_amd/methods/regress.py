@@ -1,6 +1,6 @@
 """FP32 INR trainer (counterpart of the reference's methods/regress.py:151-322; SURVEY §8f-4, a "next" row).
 
-Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss, per-epoch
+Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss or `loss: yuv420`, per-epoch
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
 from the GPU-resident cache; the ConvNeXt encoder and Adam stay in PyTorch.  Evaluations report PSNR and MS-SSIM
@@ -21,7 +21,8 @@ import torch
 from ..models import HNeRV, NeRV
 from ..utils import CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger
 from .. import ops
-from .calibrate_network import add_yuv_args, evaluate, load_frames, report_line, seed_all
+from .calibrate_network import (add_yuv_args, add_yuv_loss_args, evaluate, load_frames, report_line, seed_all,
+                                yuv_loss_params)
 
 
 def parse_args(argv):
@@ -33,6 +34,7 @@ def parse_args(argv):
     p.add_argument('--data_path', type=str)
     p.add_argument('--synthetic', type=int, default=0)
     add_yuv_args(p)
+    add_yuv_loss_args(p)
     p.add_argument('--vid', type=str, default='Bunny')
     p.add_argument('--data_split', type=str, default='1_1_1')
     p.add_argument('-p', '--print-freq', default=50, type=int)
@@ -63,11 +65,29 @@ def adjust_lr(optimizer, cur_epoch, args, eta_min=0.05):
     return args.lr * lr_mult
 
 
+def loss_params(args, cfg):
+    """cfg['loss'] -> None for 'l2', the keywords of ops.yuv420_loss for 'yuv420' (the weighted plane MSEs of the 8-bit YUV
+    4:2:0 codes; --yuv_matrix, --yuv_range, --yuv_weights; evaluations then also report PSNR-Y / U / V); anything else raises."""
+    loss_name = cfg.get('loss', 'l2')
+    if loss_name == 'l2':
+        return None
+    if loss_name != 'yuv420':
+        raise NotImplementedError("only the l2 loss of the shipped configs and 'yuv420' (DESIGN.md §19) are built")
+    args.loss_domain = 'yuv420'
+    return yuv_loss_params(args)
+
+
+def step_loss(img_out, img, yuv=None):
+    """the scalar one training step differentiates: per-channel mean of the loss"""
+    if yuv is not None:
+        return ops.yuv420_loss(img_out, img, **yuv) / 3
+    return ops.l2_loss(img_out, img) / img.shape[1]     # F.mse_loss(...).flatten(1).mean(1).mean()
+
+
 def train(args, cfg):
     if not torch.cuda.is_available():
         raise RuntimeError('neuroquant_amd needs an AMD GPU')
-    if cfg.get('loss', 'l2') != 'l2':
-        raise NotImplementedError('only the l2 loss of the shipped configs is built')
+    yuv = loss_params(args, cfg)
     device = 'cuda'
     cache = FrameCache(load_frames(args, cfg, device))
     n = len(cache)
@@ -92,7 +112,7 @@ def train(args, cfg):
             lr = adjust_lr(optimizer, (epoch + float(i) / len(loader)) / cfg['epoch'], args)
             img = sample['img']
             img_out, _, _ = model(img if args.arch == 'hnerv' else sample['norm_idx'])
-            loss = ops.l2_loss(img_out, img) / img.shape[1]     # F.mse_loss(...).flatten(1).mean(1).mean()
+            loss = step_loss(img_out, img, yuv)
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             optimizer.step()

@@ -1746,6 +1746,99 @@ def l2_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, node=None):
     return loss, head.dconv
 
 
+# ---- the same tail in the 8-bit YUV 4:2:0 domain (include/nq_hip.h: nq_yuv420_loss) ----
+YUV_LOSS_WEIGHTS = (6.0, 1.0, 1.0)
+yuv420_loss_launches = 0    # nq_yuv420_loss launches issued (or captured) by this process: the default paths issue none
+
+
+def yuv420_loss_args(what, shape, matrix, full_range, weights):
+    """-> (matrix code, range code, (wy, wu, wv)); ValueError naming `what` before anything is launched"""
+    if len(shape) != 4 or shape[1] != 3 or shape[0] <= 0:
+        raise ValueError(f"{what} takes (B, 3, H, W) images, got {tuple(shape)}")
+    _, m, fr = _yuv_args(what, shape[2], shape[3], matrix, full_range)
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        w = ()
+    if len(w) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in w) or not sum(w) > 0.0:
+        raise ValueError(f"{what}: weights must be three finite numbers >= 0 with a positive sum, got {weights!r}")
+    return m, fr, w
+
+
+def yuv420_loss_raw(pred, tgt=None, cache_u8=None, idx=None, matrix="bt709", full_range=False, weights=YUV_LOSS_WEIGHTS,
+                    head=False):
+    """One nq_yuv420_loss launch pair on images `pred` (B, 3, H, W), H and W even -> (loss4, grad, db): loss4 = (L, MSE_Y, MSE_U,
+    MSE_V) with L = 3 (wY MSE_Y + wU MSE_U + wV MSE_V) / (wY + wU + wV) over the unrounded 8-bit 4:2:0 codes / 255; the target is
+    `tgt` or frames `cache_u8[idx] / 255` read straight from the uint8 cache.  head=False: grad = dL/dpred, db = None.
+    head=True (`pred` = tanh(conv) * 0.5 + 0.5): grad = the gradient at the conv OUTPUT and db its per-channel sums (the head's
+    bias gradient), as l2_loss_tanh_head_raw.  ValueError for a bad shape, matrix or weights before any launch."""
+    global yuv420_loss_launches
+    if not isinstance(pred, torch.Tensor):
+        raise ValueError(f"yuv420_loss takes (B, 3, H, W) images, got {type(pred)}")
+    m, fr, w = yuv420_loss_args("yuv420_loss", pred.shape, matrix, full_range, weights)
+    pred_d = _dev(pred.detach(), "pred")
+    B, C, H, W = pred_d.shape
+    if (tgt is None) == (cache_u8 is None):
+        raise ValueError("yuv420_loss takes exactly one of tgt and cache_u8 + idx")
+    if cache_u8 is not None:
+        if not cache_u8.is_cuda or cache_u8.dtype != torch.uint8 or not cache_u8.is_contiguous() \
+                or tuple(cache_u8.shape[1:]) != (C, H, W) or idx is None or idx.numel() != B:
+            raise RuntimeError("frame cache must be a contiguous uint8 GPU tensor of the image's shape")
+        idx = idx.to(device=pred_d.device, dtype=torch.int64).contiguous()
+    else:
+        tgt = _dev(tgt, "tgt")
+        if tgt.shape != pred_d.shape:
+            raise ValueError(f"yuv420_loss: pred {tuple(pred_d.shape)} and tgt {tuple(tgt.shape)} differ")
+    loss4 = torch.empty(4, device=pred_d.device, dtype=torch.float32)
+    grad = torch.empty_like(pred_d)
+    db = torch.empty(3, device=pred_d.device, dtype=torch.float32) if head else None
+    ws = torch.empty(_q("nq_yuv420_loss_ws_floats", B, H, W), device=pred_d.device, dtype=torch.float32)
+    yuv420_loss_launches += 1
+    L.check(_timed("yuv420_loss", lambda: L.lib().nq_yuv420_loss(
+        _p(pred_d), _p(tgt) if cache_u8 is None else None, _p(cache_u8) if cache_u8 is not None else None,
+        _p(idx) if cache_u8 is not None else None, _p(loss4), _p(grad), _p(db), _p(ws), B, H, W, m, fr, w[0], w[1], w[2], 1.0,
+        _stream())), "yuv420_loss")
+    return loss4, grad, db
+
+
+class _YuvLossFn(Function):
+    """L of yuv420_loss_raw as a scalar; backward is grad * g (as _L2LossFn)."""
+
+    @staticmethod
+    def forward(ctx, pred, tgt, matrix, full_range, weights):
+        loss4, grad, _ = yuv420_loss_raw(pred, tgt=tgt, matrix=matrix, full_range=full_range, weights=weights)
+        ctx.save_for_backward(grad)
+        return loss4[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None, None
+
+
+def yuv420_loss(pred, tgt, matrix="bt709", full_range=False, weights=YUV_LOSS_WEIGHTS):
+    """Differentiable L of yuv420_loss_raw (w.r.t. `pred`): the weighted plane MSEs of the 8-bit YUV 4:2:0 codes, on the scale
+    of l2_loss (the trainer divides both by 3)."""
+    return _YuvLossFn.apply(pred, tgt, matrix, bool(full_range), tuple(weights))
+
+
+def yuv420_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, matrix="bt709", full_range=False,
+                          weights=YUV_LOSS_WEIGHTS, node=None):
+    """l2_loss_head_grad for the YUV 4:2:0 objective: -> (loss4, g) where `pred.backward(g)` (or decoder_backward_steps(node,
+    g)) continues the backward pass.  When `pred` carries the hand-over slot of a tanh-headed decoder node, g is the
+    gradient at the head conv's OUTPUT and the head's bias gradient is handed over with it; otherwise g = dL/dpred and the
+    ordinary backward runs.  Never None: the kernel has no tiling restriction."""
+    head = getattr(node if node is not None else pred.grad_fn, "nq_head", None)
+    if not isinstance(head, _HeadHandoff) or os.environ.get("NQ_FUSED_LOSS", "1") == "0":
+        loss4, g, _ = yuv420_loss_raw(pred, tgt, cache_u8, idx, matrix, full_range, weights, head=False)
+        return loss4, g
+    # (a result of ops.fused_head_loss that nobody asked for is dropped: this objective replaces it)
+    head.loss = None
+    loss4, head.dconv, head.db = yuv420_loss_raw(pred, tgt, cache_u8, idx, matrix, full_range, weights, head=True)
+    head.version = head.dconv._version
+    return loss4, head.dconv
+
+
 def frame_psnr(out, gt):
     """per-frame PSNR (reference utils.py:148-151): -10*log10(mean((out-gt)^2) + 1e-9)."""
     out, gt = _dev(out.detach()), _dev(gt.detach())

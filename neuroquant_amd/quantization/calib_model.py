@@ -48,8 +48,9 @@ class LossFunction:
 
     def __init__(self, model: nn.Module, round_loss: str = 'relaxation', weight: float = 1., rec_loss: str = 'mse',
                  max_count: int = 2000, b_range: tuple = (10, 2), decay_start: float = 0.0, warmup: float = 0.0,
-                 p: float = 2.):
+                 p: float = 2., yuv: dict = None):
         self.model = model
+        self.yuv = dict(yuv or {})   # rec_loss 'yuv420': matrix, full_range, weights of ops.yuv420_loss
         self.round = round_loss
         self.weight = weight
         self.rec = rec_loss
@@ -66,9 +67,12 @@ class LossFunction:
 
     def __call__(self, pred, tgt, grad=None):
         self.count += 1
-        if self.rec != 'mse':
+        if self.rec == 'yuv420':
+            rec_loss = ops.yuv420_loss(pred, tgt, **self.yuv)
+        elif self.rec == 'mse':
+            rec_loss = lp_loss(pred, tgt, p=self.p)
+        else:
             raise NotImplementedError(f'rec_loss {self.rec!r}: the drivers hard-code opt_mode="mse"')
-        rec_loss = lp_loss(pred, tgt, p=self.p)
         b = self.temp_decay(self.count)
         if self.count < self.loss_start or self.round == 'none':
             b = self.round_loss = 0
@@ -171,7 +175,8 @@ def _mean_all_reduce(t):
 def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: str = 'hnerv', batch_size: int = 8,
                          iters: int = 20000, weight: float = 0.01, opt_mode: str = 'mse', hadamard: bool = True,
                          b_range: tuple = (20, 2), warmup: float = 0.0, p: float = 2.0, lr: float = 0.0015,
-                         recorder: list = None, max_steps: int = None, step_hook=None, probe=None):
+                         recorder: list = None, max_steps: int = None, step_hook=None, probe=None,
+                         loss_domain: str = 'rgb', yuv: dict = None):
     """Network-wise calibration, in place (reference calib_model.py:92-240).
 
     gt: any sized iterable of dict batches {'img' (B,3,H,W), 'idx' (B,), 'norm_idx'}; cali_data[idx] feeds the
@@ -180,11 +185,22 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
     before every iteration (bench.py uses both to time exactly K steps).  probe(phase, layers, grads) is called after
     the backward pass and before the optimiser step with phase 'uaq' | 'ada', the engine's per-layer records (L.W.grad /
     L.b.grad = dL/dW^, dL/db^) and the list of parameter gradients in optimiser order (gradient parity tests).
+    loss_domain 'yuv420' replaces lp_loss by the weighted plane MSEs of the 8-bit YUV 4:2:0 codes (ops.yuv420_loss_head_grad,
+    DESIGN.md §19) with yuv = dict(matrix, full_range, weights) (bt709, limited range, 6:1:1 where absent); the logged `rec` is
+    that loss.  Everything else of the iteration is the same.
     """
     if arch not in ('hnerv', 'nerv'):
         raise ValueError
     if opt_mode != 'mse' or p != 2.0:
         raise NotImplementedError('only opt_mode="mse", p=2 is on the calibration path')
+    if loss_domain not in ('rgb', 'yuv420'):
+        raise ValueError(f"loss_domain must be 'rgb' or 'yuv420', got {loss_domain!r}")
+    yuv = dict(yuv or {})
+    if set(yuv) - {'matrix', 'full_range', 'weights'}:
+        raise ValueError(f"yuv takes matrix, full_range and weights, got {sorted(yuv)}")
+    if loss_domain == 'yuv420':   # a bad matrix or bad weights stop here, before the first iteration
+        ops.yuv420_loss_args('model_reconstruction', (1, 3, 2, 2), yuv.get('matrix', 'bt709'), yuv.get('full_range', False),
+                             yuv.get('weights', ops.YUV_LOSS_WEIGHTS))
     model.set_quant_state(True)
     device = next(model.parameters()).device
     layers = [_Layer(m, hadamard) for m in _quant_modules(model)]
@@ -338,7 +354,11 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                         L._finish(fq[2 * i], fq[2 * i + 1])
             node = None
             # (the loss tail runs behind the head convolution when the decoder is the fused stack: ops.fused_head_loss)
-            loss_req = ops.fused_head_loss(cache_u8=img[0], idx=img[1]) if isinstance(img, tuple) else ops.fused_head_loss(tgt=img)
+            # (... for lp_loss only: the YUV objective has its own launch behind the head)
+            if loss_domain == 'yuv420':
+                loss_req = contextlib.nullcontext()
+            else:
+                loss_req = ops.fused_head_loss(cache_u8=img[0], idx=img[1]) if isinstance(img, tuple) else ops.fused_head_loss(tgt=img)
             with loss_req:
                 if staged is None:
                     img_out, _, _ = model(inputs)
@@ -349,8 +369,14 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
             # lp_loss p=2 (quantizer.py:66-71) and its gradient; behind a tanh-headed fused decoder the loss kernel also
             # applies the tanh backward and sums the head's bias gradient (ops.l2_loss_head_grad), reading the target
             # straight from the uint8 frame cache when the batch came as (frames_u8, indices)
-            fused = ops.l2_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node) if isinstance(img, tuple) \
-                else ops.l2_loss_head_grad(img_out, tgt=img, node=node)
+            if loss_domain == 'yuv420':
+                # the weighted plane MSEs of the 8-bit 4:2:0 codes instead: same hand-over, same targets
+                loss4, dimg = ops.yuv420_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **yuv) \
+                    if isinstance(img, tuple) else ops.yuv420_loss_head_grad(img_out, tgt=img, node=node, **yuv)
+                fused = (loss4[0], dimg)
+            else:
+                fused = ops.l2_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node) if isinstance(img, tuple) \
+                    else ops.l2_loss_head_grad(img_out, tgt=img, node=node)
             if fused is None:
                 if isinstance(img, tuple):
                     img = ops.gather_frames_u8(img[0], img[1])
