@@ -607,6 +607,32 @@ NQ_API int nq_yuv420_loss(const float* pred, const float* tgt, const uint8_t* ca
                    float* db, float* ws, int B, int H, int W, int matrix, int full_range, float wy, float wu, float wv,
                    float gscale, nq_stream_t stream);
 
+/* ---- MSE + single-scale SSIM training loss with its exact gradient (additive: nq_abi_version() stays 7) ----
+ * The reference's `ssim`, `Fusion1`, `Fusion3` and `Fusion5` losses (reference utils.py:119-130): w_mse * mse + w_ssim * (1 -
+ * pytorch_msssim.ssim(X, Y, data_range=1, size_average=False)) per frame, then the mean over frames.
+ * X = pred, Y = tgt: (B, C, H, W) fp32, H, W >= 11.  Window g: 11 taps, sigma 1.5, taps evaluated in float32; g* filters
+ * separably and valid, along H then W, each channel on its own.  C1 = 1e-4, C2 = 9e-4, no relu.  Per plane
+ *   mu_x = g*X, mu_y = g*Y, Sxx = g*(X^2), Syy = g*(Y^2), Sxy = g*(XY)
+ *   A1 = 2 mu_x mu_y + C1, A2 = 2 (Sxy - mu_x mu_y) + C2, B1 = mu_x^2 + mu_y^2 + C1, B2 = (Sxx - mu_x^2) + (Syy - mu_y^2) + C2
+ *   S = A1 A2 / (B1 B2) on the (H - 10) x (W - 10) valid region, N = (H - 10)(W - 10);  SSIM_b = mean over channels of mean S
+ *   L = mean_b [ w_mse mean_{c,h,w} (X - Y)^2 + w_ssim (1 - SSIM_b) ]
+ *   loss3[3] = {L, mean MSE, mean SSIM}; after the call ws[0 .. B) holds SSIM_b of every frame.
+ * Gradient, with the five moments as the independent quantities and gT* the adjoint of the valid filter (the same window
+ * over the map zero-extended by 10 on every side, an H x W result):
+ *   P = dS/d mu_x = 2 mu_y (A2 - A1) / (B1 B2) + 2 mu_x S (1 / B2 - 1 / B1),  Q = dS/d Sxx = -S / B2,  R = dS/d Sxy = 2 A1 / (B1 B2)
+ *   dL/dX = w_mse 2 (X - Y) / (B C H W) - w_ssim / (B C N) (gT*P + 2 X gT*Q + Y gT*R)
+ *   grad != NULL: grad (B, C, H, W) = grad_scale dL/dX.  grad == NULL: forward only, P, Q, R are not written.
+ * Three launches: forward (S, P, Q, R and one partial sum of S and of (X - Y)^2 per workgroup; moments about a per-workgroup
+ * pivot as nq_ms_ssim), backward (a gather, every gradient element has one writer), and one that adds the partial sums in a
+ * fixed order in double.  No atomics: bit-identical from call to call, a frame's SSIM depends on that frame's bytes only.
+ * pred == tgt gives SSIM = 1, MSE = 0 and a zero gradient exactly.
+ *   ws: nq_ssim_loss_ws_floats(B, C, H, W) floats (0 for arguments the entry refuses).
+ * NQ_ERR_INVALID, before the device is touched, for null pred / tgt / loss3 / ws, non-positive B or C, H or W below 11, a
+ * negative or non-finite weight, a non-finite grad_scale and an element count past int64; NQ_ERR_UNSUPPORTED for B * C > 65535. */
+NQ_API int64_t nq_ssim_loss_ws_floats(int B, int C, int H, int W);
+NQ_API int nq_ssim_loss(const float* pred, const float* tgt, float* loss3, float* grad, float* ws, int B, int C, int H, int W,
+                 float w_mse, float w_ssim, float grad_scale, nq_stream_t stream);
+
 /* Entropy-coded levels: 64-lane interleaved rANS, one frequency table per tensor (probabilities in units of
  * 1 / 4096), 32-bit states >= 2^16, 16-bit words.  The n levels (flat, C order) are cut into chunks of `chunk` symbols (a
  * multiple of 64, the last may be short); lane l of a chunk owns its symbols l, l + 64, ...  One wavefront decodes one chunk.

@@ -189,6 +189,8 @@ def _load():
     sig("nq_yuv420_sse", I, P, P, P, L, I, I, P)
     sig("nq_yuv420_loss_ws_floats", L, I, I, I)
     sig("nq_yuv420_loss", I, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, F, P)
+    sig("nq_ssim_loss_ws_floats", L, I, I, I, I)
+    sig("nq_ssim_loss", I, P, P, P, P, P, I, I, I, I, F, F, F, P)
     sig("nq_rans_chunks", L, L, L)
     sig("nq_rans_decode", I, P, P, P, P, L, I, L, P, P, L, P, P, P)
     sig("nq_embed_symbols", I, P, P, P, L, L, L, I, I, P, P, P)
@@ -214,7 +216,7 @@ EXPORTS = (
     "nq_adaround_fwht_multi", "nq_fwht_adaround_adam_multi", "nq_weight_layouts_all",
     "nq_packed_words", "nq_pack_levels", "nq_unpack_dequant", "nq_frames_to_u8",
     "nq_yuv420_frame_bytes", "nq_frames_to_yuv420", "nq_yuv420_to_rgb_u8", "nq_yuv420_sse",
-    "nq_yuv420_loss_ws_floats", "nq_yuv420_loss",
+    "nq_yuv420_loss_ws_floats", "nq_yuv420_loss", "nq_ssim_loss_ws_floats", "nq_ssim_loss",
     "nq_rans_chunks", "nq_rans_decode",
     "nq_embed_symbols", "nq_embed_restore",
     "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",

@@ -1,0 +1,352 @@
+// Training loss of MSE and single-scale SSIM with its exact gradient: the reference's `ssim` and `Fusion1/3/5` losses
+// (reference utils.py:119-130 -> pytorch_msssim.ssim(X, Y, data_range=1, size_average=False)); the definition and the
+// gradient are spelled out at nq_ssim_loss in include/nq_hip.h.
+//
+// Forward launch, tiled as msssim_scale_kernel (msssim.hip): a workgroup owns an 8 x 118 tile of the valid region of one
+// (frame, channel) plane, stages the 18 x 128 input tile of both images in LDS, filters the five moments along H into LDS
+// and along W in registers, evaluates S per valid pixel and reduces S and (X - Y)^2 to ONE partial sum each (every image
+// pixel belongs to exactly one tile: the last tile of a row / column of tiles owns its halo).  With a gradient wanted it
+// also writes the three maps P = dS/d mu_x, Q = dS/d Sxx, R = dS/d Sxy.  Moments are taken about a per-workgroup pivot
+// with the window-sum correction that msssim.hip derives, so variances cancel at the size of the local contrast.
+//
+// Backward launch, a gather: a workgroup owns an 8 x 118 tile of INPUT pixels, stages the 18 x 128 tiles of P, Q, R that
+// reach it (zero outside the valid region: the adjoint of the valid filter), filters them with the same two passes (the
+// window is symmetric) and writes dL/dX with the MSE term folded in.  No atomics: every gradient element has one writer.
+//
+// Finishing launch: one workgroup adds the partial sums frame by frame in a fixed order in double.
+//
+// X and Y go through the same instructions and P, Q, R are formed so that X == Y gives S = 1, P = 0 and R = -2 Q bit for
+// bit: the SSIM is then exactly 1 and the gradient exactly 0.  Window products are explicit fused multiply-adds,
+// everything else rounds operation by operation (-ffp-contract=off).
+#include <cmath>
+
+#include "nq_common.h"
+
+namespace {
+
+constexpr int SL_WIN = 11, SL_HALO = SL_WIN - 1;
+constexpr int SL_TH = 8, SL_TW = 118;                             // tile a workgroup owns
+constexpr int SL_IH = SL_TH + SL_HALO, SL_IW = SL_TW + SL_HALO;   // staged tile: 18 x 128
+constexpr int SL_VS = SL_IW + 4;                                  // row stride of the H-filtered maps (16-byte reads run 4 past)
+constexpr int SL_TPB = 256;
+constexpr int SL_RG = 4;                                          // rows / columns one thread filters at a time
+constexpr int SL_NCG = (SL_TW + SL_RG - 1) / SL_RG;               // column groups of a tile row: 30
+static_assert(SL_IW * (SL_TH / SL_RG) == SL_TPB, "one (column, row group) per thread in the H pass");
+static_assert(SL_IH % (SL_TPB / SL_IW) == 0, "the staging loop covers the tile's rows exactly");
+static_assert(SL_TH * SL_NCG <= SL_TPB, "one (row, column group) per thread in the W pass");
+static_assert((SL_NCG - 1) * SL_RG + SL_RG + SL_HALO + 2 <= SL_VS, "the W pass reads inside a row of the filtered maps");
+
+// the window and its sums as msssim.hip states them: exp(-(i-5)^2 / (2 * 1.5^2)) / sum, evaluated in float32; the taps add up
+// to G = 0.999999969266355, G^2 in two dimensions
+__constant__ float sl_g[SL_WIN] = {0x1.0d957p-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f,
+                                   0x1.b43c3ep-3f, 0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d957p-10f};
+constexpr float SL_D2 = 6.146728898e-08f;       // 1 - G^2
+constexpr float SL_G2D2 = 6.146728520e-08f;     // G^2 (1 - G^2)
+
+// what the shift by the pivots (p of x, q of y) took from g*(xy) - (g*x)(g*y); a = g*x', b = g*y'
+__device__ __forceinline__ float sl_shift_term(float p, float q, float a, float b) {
+  return SL_D2 * (q * a + p * b) + (p * q) * SL_G2D2;
+}
+
+// ---- along H: thread = (column, group of 4 rows); 14 staged rows feed 4 x NM sums, taps in rising order.
+//      `value(r, c, m)` hands over the NM quantities of staged element (r, c). ----
+template <int NM, typename V>
+__device__ __forceinline__ void sl_filter_h(float (*sv)[SL_TH][SL_VS], V value) {
+  const int c = threadIdx.x & (SL_IW - 1), r0 = (threadIdx.x / SL_IW) * SL_RG;
+  float acc[SL_RG][NM];
+#pragma unroll
+  for (int j = 0; j < SL_RG; ++j)
+#pragma unroll
+    for (int q = 0; q < NM; ++q) acc[j][q] = 0.f;
+#pragma unroll
+  for (int r = 0; r < SL_RG + SL_HALO; ++r) {
+    float m[NM];
+    value(r0 + r, c, m);
+#pragma unroll
+    for (int j = 0; j < SL_RG; ++j) {
+      const int t = r - j;
+      if (t >= 0 && t < SL_WIN) {
+#pragma unroll
+        for (int q = 0; q < NM; ++q) acc[j][q] = __builtin_fmaf(sl_g[t], m[q], acc[j][q]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < SL_RG; ++j)
+#pragma unroll
+    for (int q = 0; q < NM; ++q) sv[q][r0 + j][c] = acc[j][q];
+}
+
+// ---- along W: row r, columns c0 .. c0 + 3 of the tile from columns c0 .. c0 + 13 of the H-filtered maps ----
+template <int NM>
+__device__ __forceinline__ void sl_filter_w(const float (*sv)[SL_TH][SL_VS], int r, int c0, float (*acc)[NM]) {
+#pragma unroll
+  for (int q = 0; q < NM; ++q) {
+    float v[SL_RG + SL_HALO + 2];
+#pragma unroll
+    for (int k = 0; k < (SL_RG + SL_HALO + 2) / 4; ++k) {
+      const float4 t = *reinterpret_cast<const float4*>(&sv[q][r][c0 + 4 * k]);
+      v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
+    }
+#pragma unroll
+    for (int j = 0; j < SL_RG; ++j) {
+      float a = 0.f;
+#pragma unroll
+      for (int t = 0; t < SL_WIN; ++t) a = __builtin_fmaf(sl_g[t], v[j + t], a);
+      acc[j][q] = a;
+    }
+  }
+}
+
+__device__ __forceinline__ double sl_wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// Sums of a and of b over the workgroup (a multiple of 64 threads, at most 256) in a fixed order; valid in thread 0.
+__device__ __forceinline__ void sl_block_sum2(double& a, double& b, double (*red)[2]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  a = sl_wave_sum_d(a);
+  b = sl_wave_sum_d(b);
+  if (lane == 0) {
+    red[wave][0] = a;
+    red[wave][1] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int i = 1; i < nw; ++i) {
+      a += red[i][0];
+      b += red[i][1];
+    }
+}
+
+// grid (ntx * nty, planes).  maps: P, Q, R of every plane ((h - 10) x (w - 10) each), map_stride floats apart; MAPS false: unused.
+template <bool MAPS>
+__global__ __launch_bounds__(SL_TPB) void ssim_loss_forward_kernel(const float* __restrict__ xi, const float* __restrict__ yi,
+                                                                   float* __restrict__ part_s, float* __restrict__ part_m,
+                                                                   float* __restrict__ maps, int64_t map_stride, int h, int w,
+                                                                   int ntx, int nty) {
+  __shared__ float sx[SL_IH][SL_IW], sy[SL_IH][SL_IW];
+  __shared__ __attribute__((aligned(16))) float sv[5][SL_TH][SL_VS];
+  __shared__ double red[SL_TPB / 64][2];
+  const int tid = threadIdx.x;
+  const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
+  const int64_t plane = blockIdx.y;
+  const int R0 = ty * SL_TH, C0 = tx * SL_TW;
+  const int vh = h - SL_HALO, vw = w - SL_HALO;
+  const float* __restrict__ xp = xi + plane * ((int64_t)h * w);
+  const float* __restrict__ yp = yi + plane * ((int64_t)h * w);
+
+  // ---- stage the tile + halo of both images (zeros beyond the image); the squared differences of the pixels this tile owns ----
+  double sum_m = 0.0;
+  {
+    const int c = tid & (SL_IW - 1), gx = C0 + c;
+    const bool own_c = c < SL_TW || tx == ntx - 1;
+#pragma unroll
+    for (int k = 0; k < SL_IH / (SL_TPB / SL_IW); ++k) {
+      const int r = tid / SL_IW + k * (SL_TPB / SL_IW), gy = R0 + r;
+      const bool in = gy < h && gx < w;
+      const int64_t o = (int64_t)gy * w + gx;
+      const float x = in ? xp[o] : 0.f, y = in ? yp[o] : 0.f;
+      sx[r][c] = x;
+      sy[r][c] = y;
+      const double d = (double)(x - y);
+      sum_m += own_c && (r < SL_TH || ty == nty - 1) ? d * d : 0.0;
+    }
+  }
+  __syncthreads();
+
+  // the pivots: the staged tile's centre, moved into the image where the tile hangs over its edge
+  const int pr = min(SL_IH / 2, h - 1 - R0), pc = min(SL_IW / 2, w - 1 - C0);
+  const float pvx = sx[pr][pc], pvy = sy[pr][pc];
+
+  sl_filter_h<5>(sv, [&](int r, int c, float* m) {
+    const float x = sx[r][c] - pvx, y = sy[r][c] - pvy;
+    m[0] = x; m[1] = y; m[2] = x * x; m[3] = y * y; m[4] = x * y;
+  });
+  __syncthreads();
+
+  // ---- along W + the maps: thread = (row, group of 4 columns) ----
+  double sum_s = 0.0;
+  if (tid < SL_TH * SL_NCG) {
+    const int r = tid / SL_NCG, c0 = (tid - r * SL_NCG) * SL_RG;
+    float acc[SL_RG][5];
+    sl_filter_w<5>(sv, r, c0, acc);
+    const float C1c = 0.01f * 0.01f, C2c = 0.03f * 0.03f;
+    float* __restrict__ mp = MAPS ? maps + plane * ((int64_t)vh * vw) + (int64_t)(R0 + r) * vw + C0 : nullptr;
+#pragma unroll
+    for (int j = 0; j < SL_RG; ++j) {
+      const int cc = c0 + j;
+      // columns past the tile (or the valid region) were filtered from stale LDS: selected away, never added or stored
+      const bool ok = cc < SL_TW && C0 + cc < vw && R0 + r < vh;
+      const float m1 = acc[j][0], m2 = acc[j][1];
+      const float s1 = (acc[j][2] - m1 * m1) + sl_shift_term(pvx, pvx, m1, m1);
+      const float s2 = (acc[j][3] - m2 * m2) + sl_shift_term(pvy, pvy, m2, m2);
+      const float s12 = (acc[j][4] - m1 * m2) + sl_shift_term(pvx, pvy, m1, m2);
+      const float u1 = (m1 - pvx * SL_D2) + pvx, u2 = (m2 - pvy * SL_D2) + pvy;   // g*x = g*x' + p G^2
+      const float A1 = 2.f * u1 * u2 + C1c, B1 = u1 * u1 + u2 * u2 + C1c;
+      const float A2 = 2.f * s12 + C2c, B2 = s1 + s2 + C2c;
+      const float lum = A1 / B1;
+      const float S = lum * (A2 / B2);
+      sum_s += ok ? (double)S : 0.0;
+      if (MAPS && ok) {
+        // P = 2 mu_y (A2 - A1) / (B1 B2) + 2 mu_x S (1 / B2 - 1 / B1) over one denominator: both products cancel when X == Y
+        mp[cc] = 2.f * (u2 * (A2 - A1) + (u1 * S) * (B1 - B2)) / (B1 * B2);
+        mp[map_stride + cc] = -S / B2;
+        mp[2 * map_stride + cc] = 2.f * lum / B2;
+      }
+    }
+  }
+  sl_block_sum2(sum_s, sum_m, red);
+  if (tid == 0) {
+    const int64_t o = plane * ((int64_t)ntx * nty) + blockIdx.x;
+    part_s[o] = (float)sum_s;
+    part_m[o] = (float)sum_m;
+  }
+}
+
+// grid (ntx * nty, planes), tiles of the h x w image.  grad = k_mse (X - Y) + k_ssim (gT*P + 2 X gT*Q + Y gT*R).
+__global__ __launch_bounds__(SL_TPB) void ssim_loss_backward_kernel(const float* __restrict__ xi, const float* __restrict__ yi,
+                                                                    const float* __restrict__ maps, int64_t map_stride,
+                                                                    float* __restrict__ grad, int h, int w, int ntx, float k_mse,
+                                                                    float k_ssim) {
+  __shared__ float sm[3][SL_IH][SL_IW];
+  __shared__ __attribute__((aligned(16))) float sv[3][SL_TH][SL_VS];
+  const int tid = threadIdx.x;
+  const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
+  const int64_t plane = blockIdx.y;
+  const int R0 = ty * SL_TH, C0 = tx * SL_TW;
+  const int vh = h - SL_HALO, vw = w - SL_HALO;
+  const float* __restrict__ mp = maps + plane * ((int64_t)vh * vw);
+
+  // ---- stage the map pixels whose windows reach the tile: rows R0 - 10 .. R0 + 7, zero outside the valid region ----
+  {
+    const int c = tid & (SL_IW - 1), gx = C0 - SL_HALO + c;
+#pragma unroll
+    for (int k = 0; k < SL_IH / (SL_TPB / SL_IW); ++k) {
+      const int r = tid / SL_IW + k * (SL_TPB / SL_IW), gy = R0 - SL_HALO + r;
+      const bool in = gy >= 0 && gy < vh && gx >= 0 && gx < vw;
+      const int64_t o = (int64_t)gy * vw + gx;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) sm[q][r][c] = in ? mp[q * map_stride + o] : 0.f;
+    }
+  }
+  __syncthreads();
+  sl_filter_h<3>(sv, [&](int r, int c, float* m) {
+    m[0] = sm[0][r][c]; m[1] = sm[1][r][c]; m[2] = sm[2][r][c];
+  });
+  __syncthreads();
+
+  if (tid < SL_TH * SL_NCG) {
+    const int r = tid / SL_NCG, c0 = (tid - r * SL_NCG) * SL_RG;
+    float acc[SL_RG][3];
+    sl_filter_w<3>(sv, r, c0, acc);
+    const int gy = R0 + r;
+#pragma unroll
+    for (int j = 0; j < SL_RG; ++j) {
+      const int cc = c0 + j, gx = C0 + cc;
+      if (cc < SL_TW && gx < w && gy < h) {
+        const int64_t o = plane * ((int64_t)h * w) + (int64_t)gy * w + gx;
+        const float x = xi[o], y = yi[o];
+        // the three terms cancel to a small part of their size where the image is flat: their products and sum in double
+        const double ds = (double)acc[j][0] + ((double)(2.f * x) * (double)acc[j][1] + (double)y * (double)acc[j][2]);
+        grad[o] = k_mse * (x - y) + k_ssim * (float)ds;
+      }
+    }
+  }
+}
+
+// One workgroup.  per_frame = C * tiles partial sums of each kind per frame, added lane-strided, then the tree, in double.
+__global__ __launch_bounds__(SL_TPB) void ssim_loss_finish_kernel(const float* __restrict__ part_s, const float* __restrict__ part_m,
+                                                                  int B, int64_t per_frame, double n_ssim, double n_mse,
+                                                                  double w_mse, double w_ssim, float* __restrict__ frame_ssim,
+                                                                  float* __restrict__ loss3) {
+  __shared__ double red[SL_TPB / 64][2];
+  double tot_s = 0.0, tot_m = 0.0;
+  for (int b = 0; b < B; ++b) {
+    double s = 0.0, m = 0.0;
+    for (int64_t i = threadIdx.x; i < per_frame; i += SL_TPB) {
+      s += (double)part_s[b * per_frame + i];
+      m += (double)part_m[b * per_frame + i];
+    }
+    sl_block_sum2(s, m, red);
+    if (threadIdx.x == 0) {
+      const double v = s / n_ssim;                      // divided by the count: a map of ones has mean exactly 1
+      frame_ssim[b] = (float)v;
+      tot_s += v;
+      tot_m += m;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double mse = tot_m / n_mse, ssim = tot_s / (double)B;
+    loss3[0] = (float)(w_mse * mse + w_ssim * (1.0 - ssim));
+    loss3[1] = (float)mse;
+    loss3[2] = (float)ssim;
+  }
+}
+
+struct SlPlan {
+  int64_t planes, fwd_tiles, bwd_tiles, map_stride;
+  int ntx, nty, btx;
+  int64_t off_s, off_m, off_maps, total;   // the workspace: B frame values, the two kinds of partial sums, P | Q | R
+};
+
+inline bool sl_plan(int B, int C, int H, int W, SlPlan& p) {
+  if (B <= 0 || C <= 0 || H < SL_WIN || W < SL_WIN) return false;
+  p.planes = (int64_t)B * C;
+  const int64_t hw = (int64_t)H * W;
+  if (p.planes > (INT64_MAX / 8) / hw) return false;
+  p.ntx = (W - SL_HALO + SL_TW - 1) / SL_TW;
+  p.nty = (H - SL_HALO + SL_TH - 1) / SL_TH;
+  p.btx = (W + SL_TW - 1) / SL_TW;
+  p.fwd_tiles = (int64_t)p.ntx * p.nty;
+  p.bwd_tiles = (int64_t)p.btx * ((H + SL_TH - 1) / SL_TH);
+  p.map_stride = p.planes * (H - SL_HALO) * (int64_t)(W - SL_HALO);
+  p.off_s = B;
+  p.off_m = p.off_s + p.planes * p.fwd_tiles;
+  p.off_maps = p.off_m + p.planes * p.fwd_tiles;
+  p.total = p.off_maps + 3 * p.map_stride;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nq_ssim_loss_ws_floats(int B, int C, int H, int W) {
+  SlPlan p;
+  return sl_plan(B, C, H, W, p) ? p.total : 0;
+}
+
+int nq_ssim_loss(const float* pred, const float* tgt, float* loss3, float* grad, float* ws, int B, int C, int H, int W, float w_mse,
+                 float w_ssim, float grad_scale, nq_stream_t stream) {
+  SlPlan p;
+  if (!pred || !tgt || !loss3 || !ws || !sl_plan(B, C, H, W, p)) return NQ_ERR_INVALID;
+  if (!std::isfinite(w_mse) || !std::isfinite(w_ssim) || !std::isfinite(grad_scale) || w_mse < 0.f || w_ssim < 0.f)
+    return NQ_ERR_INVALID;
+  if (p.planes > 65535 || p.bwd_tiles > 0x7fffffffLL) return NQ_ERR_UNSUPPORTED;   // grid.y, grid.x
+  const hipStream_t st = nq_s(stream);
+  float *part_s = ws + p.off_s, *part_m = ws + p.off_m, *maps = ws + p.off_maps;
+  const dim3 fgrid((unsigned)p.fwd_tiles, (unsigned)p.planes);
+  if (grad)
+    hipLaunchKernelGGL(ssim_loss_forward_kernel<true>, fgrid, dim3(SL_TPB), 0, st, pred, tgt, part_s, part_m, maps, p.map_stride,
+                       H, W, p.ntx, p.nty);
+  else
+    hipLaunchKernelGGL(ssim_loss_forward_kernel<false>, fgrid, dim3(SL_TPB), 0, st, pred, tgt, part_s, part_m, (float*)nullptr,
+                       (int64_t)0, H, W, p.ntx, p.nty);
+  const double n_mse = (double)p.planes * (double)H * (double)W;
+  const double n_map = (double)(H - SL_HALO) * (double)(W - SL_HALO);
+  if (grad) {
+    const float k_mse = (float)((double)grad_scale * (double)w_mse * 2.0 / n_mse);
+    const float k_ssim = (float)(-(double)grad_scale * (double)w_ssim / ((double)p.planes * n_map));
+    hipLaunchKernelGGL(ssim_loss_backward_kernel, dim3((unsigned)p.bwd_tiles, (unsigned)p.planes), dim3(SL_TPB), 0, st, pred, tgt,
+                       maps, p.map_stride, grad, H, W, p.btx, k_mse, k_ssim);
+  }
+  hipLaunchKernelGGL(ssim_loss_finish_kernel, dim3(1), dim3(SL_TPB), 0, st, part_s, part_m, B, (int64_t)C * p.fwd_tiles,
+                     (double)C * n_map, n_mse, (double)w_mse, (double)w_ssim, ws, loss3);
+  return nq_launch_status();
+}
+
+}  // extern "C"

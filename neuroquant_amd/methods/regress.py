@@ -1,6 +1,7 @@
 """FP32 INR trainer (counterpart of the reference's methods/regress.py:151-322; SURVEY §8f-4, a "next" row).
 
-Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss or `loss: yuv420`, per-epoch
+Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss, `loss: yuv420` or the
+reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5`, per-epoch
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
 from the GPU-resident cache; the ConvNeXt encoder and Adam stay in PyTorch.  Evaluations report PSNR and MS-SSIM
@@ -65,20 +66,31 @@ def adjust_lr(optimizer, cur_epoch, args, eta_min=0.05):
     return args.lr * lr_mult
 
 
+# the members of the reference's loss table (utils.py:119-130) made of MSE and single-scale SSIM only: (w_mse, w_ssim)
+SSIM_LOSSES = {'ssim': (0.0, 1.0), 'Fusion1': (0.3, 0.7), 'Fusion3': (0.5, 0.5), 'Fusion5': (0.7, 0.3)}
+
+
 def loss_params(args, cfg):
     """cfg['loss'] -> None for 'l2', the keywords of ops.yuv420_loss for 'yuv420' (the weighted plane MSEs of the 8-bit YUV
-    4:2:0 codes; --yuv_matrix, --yuv_range, --yuv_weights; evaluations then also report PSNR-Y / U / V); anything else raises."""
+    4:2:0 codes; --yuv_matrix, --yuv_range, --yuv_weights; evaluations then also report PSNR-Y / U / V), the keywords of
+    ops.ssim_loss for 'ssim' / 'Fusion1' / 'Fusion3' / 'Fusion5' (DESIGN.md §20); anything else raises."""
     loss_name = cfg.get('loss', 'l2')
     if loss_name == 'l2':
         return None
+    if loss_name in SSIM_LOSSES:
+        w_mse, w_ssim = SSIM_LOSSES[loss_name]
+        return dict(w_mse=w_mse, w_ssim=w_ssim)
     if loss_name != 'yuv420':
-        raise NotImplementedError("only the l2 loss of the shipped configs and 'yuv420' (DESIGN.md §19) are built")
+        raise NotImplementedError("only the l2 loss of the shipped configs, 'yuv420' (DESIGN.md §19) and 'ssim' / 'Fusion1' / "
+                                  "'Fusion3' / 'Fusion5' (DESIGN.md §20) are built")
     args.loss_domain = 'yuv420'
     return yuv_loss_params(args)
 
 
 def step_loss(img_out, img, yuv=None):
-    """the scalar one training step differentiates: per-channel mean of the loss"""
+    """the scalar one training step differentiates: per-channel mean of the loss (`yuv`: what loss_params returned)"""
+    if yuv is not None and 'w_ssim' in yuv:
+        return ops.ssim_loss(img_out, img, **yuv)       # the reference's per-frame loss, then .mean(): nothing on top
     if yuv is not None:
         return ops.yuv420_loss(img_out, img, **yuv) / 3
     return ops.l2_loss(img_out, img) / img.shape[1]     # F.mse_loss(...).flatten(1).mean(1).mean()

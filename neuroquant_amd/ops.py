@@ -1839,6 +1839,77 @@ def yuv420_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, matrix="bt709
     return loss4, head.dconv
 
 
+# ---- MSE + single-scale SSIM, the reference's ssim / Fusion1 / 3 / 5 losses (include/nq_hip.h: nq_ssim_loss) ----
+SSIM_LOSS_TILE = (8, 118)   # rows x columns a workgroup of csrc/ssim_loss.hip owns (SL_TH, SL_TW): the tests' edge shapes
+
+
+def ssim_loss_args(what, pred_shape, tgt_shape, w_mse, w_ssim):
+    """-> (w_mse, w_ssim) as floats; ValueError naming `what` before anything is launched"""
+    if len(pred_shape) != 4 or min(pred_shape[:2]) <= 0 or min(pred_shape[2:]) < 11:
+        raise ValueError(f"{what} takes (B, C, H, W) images with H, W >= 11, got {tuple(pred_shape)}")
+    if tuple(tgt_shape) != tuple(pred_shape):
+        raise ValueError(f"{what}: pred {tuple(pred_shape)} and tgt {tuple(tgt_shape)} differ")
+    try:
+        w = (float(w_mse), float(w_ssim))
+    except (TypeError, ValueError):
+        w = (-1.0, -1.0)
+    if not all(math.isfinite(v) and v >= 0.0 for v in w) or not sum(w) > 0.0:
+        raise ValueError(f"{what}: weights must be two finite numbers >= 0 with a positive sum, got {(w_mse, w_ssim)!r}")
+    return w
+
+
+def _ssim_loss_launch(what, pred, tgt, w_mse, w_ssim, want_grad):
+    """-> (loss3, grad or None, ws): ws[:B] holds the per-frame SSIM"""
+    if not isinstance(pred, torch.Tensor) or not isinstance(tgt, torch.Tensor):
+        raise ValueError(f"{what} takes two (B, C, H, W) tensors, got {type(pred)} and {type(tgt)}")
+    w = ssim_loss_args(what, pred.shape, tgt.shape, w_mse, w_ssim)
+    pred_d, tgt = _dev(pred.detach(), "pred"), _dev(tgt.detach(), "tgt")
+    B, C, H, W = pred_d.shape
+    loss3 = torch.empty(3, device=pred_d.device, dtype=torch.float32)
+    grad = torch.empty_like(pred_d) if want_grad else None
+    ws = torch.empty(_q("nq_ssim_loss_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
+    L.check(_timed("ssim_loss", lambda: L.lib().nq_ssim_loss(_p(pred_d), _p(tgt), _p(loss3), _p(grad), _p(ws), B, C, H, W, w[0],
+                                                             w[1], 1.0, _stream())), "ssim_loss")
+    return loss3, grad, ws
+
+
+def ssim_loss_raw(pred, tgt, w_mse, w_ssim, want_grad=True):
+    """One nq_ssim_loss call on images `pred`, `tgt` (B, C, H, W), H, W >= 11 -> (loss3, grad): loss3 = (L, mean MSE, mean SSIM)
+    with L = mean_b [w_mse * MSE_b + w_ssim * (1 - SSIM_b)], SSIM the single-scale pytorch_msssim.ssim(pred, tgt, data_range=1,
+    size_average=False) (11-tap Gaussian window, valid filtering; reference utils.py:119-130); grad = dL/dpred, exact, or None
+    with want_grad=False (the forward launch alone: the same loss3 bits).  Bit-identical from call to call.  ValueError for a bad
+    shape or bad weights before any launch."""
+    loss3, grad, _ = _ssim_loss_launch("ssim_loss", pred, tgt, w_mse, w_ssim, want_grad)
+    return loss3, grad
+
+
+class _SsimLossFn(Function):
+    """L of ssim_loss_raw as a scalar; backward is grad * g (as _YuvLossFn)."""
+
+    @staticmethod
+    def forward(ctx, pred, tgt, w_mse, w_ssim):
+        loss3, grad = ssim_loss_raw(pred, tgt, w_mse, w_ssim)
+        ctx.save_for_backward(grad)
+        return loss3[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None
+
+
+def ssim_loss(pred, tgt, w_mse=0.0, w_ssim=1.0):
+    """Differentiable L of ssim_loss_raw (w.r.t. `pred`): the reference's per-frame loss followed by .mean()."""
+    return _SsimLossFn.apply(pred, tgt, float(w_mse), float(w_ssim))
+
+
+def ssim(out, gt):
+    """per-frame single-scale SSIM of (F, C, H, W) images -> (F,) fp32 (pytorch_msssim.ssim(out, gt, data_range=1,
+    size_average=False)); a frame's value depends on that frame's bytes only.  Forward only (inputs are detached)."""
+    _, _, ws = _ssim_loss_launch("ssim", out, gt, 0.0, 1.0, False)
+    return ws[:out.shape[0]].clone()
+
+
 def frame_psnr(out, gt):
     """per-frame PSNR (reference utils.py:148-151): -10*log10(mean((out-gt)^2) + 1e-9)."""
     out, gt = _dev(out.detach()), _dev(gt.detach())
