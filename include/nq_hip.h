@@ -633,6 +633,32 @@ NQ_API int64_t nq_ssim_loss_ws_floats(int B, int C, int H, int W);
 NQ_API int nq_ssim_loss(const float* pred, const float* tgt, float* loss3, float* grad, float* ws, int B, int C, int H, int W,
                  float w_mse, float w_ssim, float grad_scale, nq_stream_t stream);
 
+/* ---- the same loss as the tail of a calibration iteration (additive: nq_abi_version() stays 7) ----
+ * L, MSE, SSIM and dL/dX as nq_ssim_loss defines them, with what nq_l2_loss_tanh_head and nq_yuv420_loss hand over:
+ *   loss3[3] = {scale L (the float L of nq_ssim_loss times scale, one more rounding), mean MSE, mean SSIM}; ws[0 .. B) holds
+ *   SSIM_b.  The calibration engine passes scale = C: weights (1, 0) then give the value and gradient of lp_loss(p = 2).
+ *   Target: exactly one of `tgt` (B, C, H, W) and `cache_u8` (N, C, H, W) + idx[B] is non-NULL; tgt = cache[idx[b]] / 255, the
+ *   arithmetic of nq_gather_frames_u8, converted while the forward and the backward launch stage their tiles (no float copy of
+ *   the target is written).  The VALUES of idx are the caller's responsibility, as for nq_l2_loss_tanh_head and nq_yuv420_loss:
+ *   they live on the device and are not read by the host (that would stop a capture), an index outside [0, N) reads outside
+ *   the cache.
+ *   db == NULL: grad (B, C, H, W) = scale dL/dX (grad == NULL: forward only).  With a float target every output but loss3[0]
+ *   equals nq_ssim_loss(grad_scale = scale) bit for bit.
+ *   db != NULL (X = tanh(conv) * 0.5 + 0.5; grad must be given): grad = that value * 0.5 * (1 - (2 X - 1)^2), the gradient at
+ *   the head conv's output, bit-identical to nq_tanh_out_backward of the db == NULL result; db[C] = its sums over frames and
+ *   pixels: every backward workgroup (one tile of one (frame, channel) plane) adds its results in double and stores one float,
+ *   the finishing launch adds those per channel, frame by frame, in double.
+ * At most three launches (forward, backward, finish: 1 + C workgroups with db), no atomics, no host read, no launch argument
+ * that depends on device data: bit-identical from call to call and capturable in a hipGraph.
+ *   ws: nq_ssim_loss_head_ws_floats(B, C, H, W) floats = nq_ssim_loss_ws_floats + B C ceil(H / 8) ceil(W / 118) (0 for
+ *   arguments the entry refuses).
+ * NQ_ERR_INVALID, before the device is touched, for what nq_ssim_loss refuses, both or neither target, a cache without idx
+ * and db without grad; NQ_ERR_UNSUPPORTED for B * C > 65535. */
+NQ_API int64_t nq_ssim_loss_head_ws_floats(int B, int C, int H, int W);
+NQ_API int nq_ssim_loss_head(const float* pred, const float* tgt, const uint8_t* cache_u8, const int64_t* idx, float* loss3,
+                      float* grad, float* db, float* ws, int B, int C, int H, int W, float w_mse, float w_ssim, float scale,
+                      nq_stream_t stream);
+
 /* Entropy-coded levels: 64-lane interleaved rANS, one frequency table per tensor (probabilities in units of
  * 1 / 4096), 32-bit states >= 2^16, 16-bit words.  The n levels (flat, C order) are cut into chunks of `chunk` symbols (a
  * multiple of 64, the last may be short); lane l of a chunk owns its symbols l, l + 64, ...  One wavefront decodes one chunk.

@@ -15,6 +15,13 @@
 //
 // Finishing launch: one workgroup adds the partial sums frame by frame in a fixed order in double.
 //
+// nq_ssim_loss_head (the tail of a calibration iteration) launches the same three kernels with template
+// flags: U8 reads the target from the uint8 frame cache through device-side frame indices while the tiles are staged, HEAD
+// applies the tanh backward to every gradient element and leaves one partial sum of the results per backward workgroup, which
+// further workgroups of the finishing launch add per channel (the head's bias gradient).  The instantiations nq_ssim_loss
+// launches run the arithmetic they ran, operation by operation (its results are unchanged); they take the new kernel
+// arguments and read the target through SlTarget, so their machine code is not the earlier build's.
+//
 // X and Y go through the same instructions and P, Q, R are formed so that X == Y gives S = 1, P = 0 and R = -2 Q bit for
 // bit: the SSIM is then exactly 1 and the gradient exactly 0.  Window products are explicit fused multiply-adds,
 // everything else rounds operation by operation (-ffp-contract=off).
@@ -121,9 +128,33 @@ __device__ __forceinline__ void sl_block_sum2(double& a, double& b, double (*red
     }
 }
 
+// The target plane of a workgroup: float frames, or (U8) the plane of frame idx[plane / C] of the uint8 cache, converted as
+// gather_u8_kernel does while the tile is staged (elementwise.hip: (float)byte / 255.f).
+template <bool U8>
+struct SlTarget {
+  const float* __restrict__ f;
+  const uint8_t* __restrict__ u;
+  __device__ __forceinline__ SlTarget(const float* yi, const uint8_t* cache, const int64_t* idx, int64_t plane, int C, int64_t hw)
+      : f(nullptr), u(nullptr) {
+    if constexpr (U8) {
+      const int64_t b = plane / C;
+      u = cache + (idx[b] * C + (plane - b * C)) * hw;
+    } else {
+      f = yi + plane * hw;
+    }
+  }
+  __device__ __forceinline__ float operator[](int64_t o) const {
+    if constexpr (U8) return (float)u[o] / 255.f;
+    else return f[o];
+  }
+};
+
 // grid (ntx * nty, planes).  maps: P, Q, R of every plane ((h - 10) x (w - 10) each), map_stride floats apart; MAPS false: unused.
-template <bool MAPS>
+// U8: the target is read from the uint8 frame cache (cache, idx, C; yi unused), else from yi (cache, idx, C unused).
+template <bool MAPS, bool U8 = false>
 __global__ __launch_bounds__(SL_TPB) void ssim_loss_forward_kernel(const float* __restrict__ xi, const float* __restrict__ yi,
+                                                                   const uint8_t* __restrict__ cache,
+                                                                   const int64_t* __restrict__ idx, int C,
                                                                    float* __restrict__ part_s, float* __restrict__ part_m,
                                                                    float* __restrict__ maps, int64_t map_stride, int h, int w,
                                                                    int ntx, int nty) {
@@ -136,7 +167,7 @@ __global__ __launch_bounds__(SL_TPB) void ssim_loss_forward_kernel(const float* 
   const int R0 = ty * SL_TH, C0 = tx * SL_TW;
   const int vh = h - SL_HALO, vw = w - SL_HALO;
   const float* __restrict__ xp = xi + plane * ((int64_t)h * w);
-  const float* __restrict__ yp = yi + plane * ((int64_t)h * w);
+  const SlTarget<U8> yp(yi, cache, idx, plane, C, (int64_t)h * w);
 
   // ---- stage the tile + halo of both images (zeros beyond the image); the squared differences of the pixels this tile owns ----
   double sum_m = 0.0;
@@ -207,10 +238,16 @@ __global__ __launch_bounds__(SL_TPB) void ssim_loss_forward_kernel(const float* 
 }
 
 // grid (ntx * nty, planes), tiles of the h x w image.  grad = k_mse (X - Y) + k_ssim (gT*P + 2 X gT*Q + Y gT*R).
+// U8: the target as in the forward kernel.  HEAD (X = tanh(conv) * 0.5 + 0.5): that value times 0.5 (1 - (2 X - 1)^2), the
+// expression of tanh_out_bwd_kernel (elementwise.hip) on the very float the other mode stores, and the sum of the tile's
+// results -- one (frame, channel) plane, added in double -- rounded once into part_g[plane * tiles + tile].
+template <bool U8 = false, bool HEAD = false>
 __global__ __launch_bounds__(SL_TPB) void ssim_loss_backward_kernel(const float* __restrict__ xi, const float* __restrict__ yi,
+                                                                    const uint8_t* __restrict__ cache,
+                                                                    const int64_t* __restrict__ idx, int C,
                                                                     const float* __restrict__ maps, int64_t map_stride,
-                                                                    float* __restrict__ grad, int h, int w, int ntx, float k_mse,
-                                                                    float k_ssim) {
+                                                                    float* __restrict__ grad, float* __restrict__ part_g, int h,
+                                                                    int w, int ntx, float k_mse, float k_ssim) {
   __shared__ float sm[3][SL_IH][SL_IW];
   __shared__ __attribute__((aligned(16))) float sv[3][SL_TH][SL_VS];
   const int tid = threadIdx.x;
@@ -238,6 +275,8 @@ __global__ __launch_bounds__(SL_TPB) void ssim_loss_backward_kernel(const float*
   });
   __syncthreads();
 
+  const SlTarget<U8> yp(yi, cache, idx, plane, C, (int64_t)h * w);
+  double sum_g = 0.0;
   if (tid < SL_TH * SL_NCG) {
     const int r = tid / SL_NCG, c0 = (tid - r * SL_NCG) * SL_RG;
     float acc[SL_RG][3];
@@ -247,22 +286,54 @@ __global__ __launch_bounds__(SL_TPB) void ssim_loss_backward_kernel(const float*
     for (int j = 0; j < SL_RG; ++j) {
       const int cc = c0 + j, gx = C0 + cc;
       if (cc < SL_TW && gx < w && gy < h) {
-        const int64_t o = plane * ((int64_t)h * w) + (int64_t)gy * w + gx;
-        const float x = xi[o], y = yi[o];
+        const int64_t po = (int64_t)gy * w + gx, o = plane * ((int64_t)h * w) + po;
+        const float x = xi[o], y = yp[po];
         // the three terms cancel to a small part of their size where the image is flat: their products and sum in double
         const double ds = (double)acc[j][0] + ((double)(2.f * x) * (double)acc[j][1] + (double)y * (double)acc[j][2]);
-        grad[o] = k_mse * (x - y) + k_ssim * (float)ds;
+        const float g = k_mse * (x - y) + k_ssim * (float)ds;
+        if constexpr (HEAD) {
+          const float u = 2.f * x - 1.f;
+          const float d = g * 0.5f * (1.f - u * u);
+          grad[o] = d;
+          sum_g += (double)d;
+        } else {
+          grad[o] = g;
+        }
       }
     }
   }
+  if constexpr (HEAD) {
+    __shared__ double red[SL_TPB / 64][2];   // in the HEAD instantiations only
+    double unused = 0.0;
+    sl_block_sum2(sum_g, unused, red);
+    if (tid == 0) part_g[plane * (int64_t)gridDim.x + blockIdx.x] = (float)sum_g;
+  }
 }
 
-// One workgroup.  per_frame = C * tiles partial sums of each kind per frame, added lane-strided, then the tree, in double.
+// Workgroup 0.  per_frame = C * tiles partial sums of each kind per frame, added lane-strided, then the tree, in double.
+// HEAD (nq_ssim_loss_head): loss3[0] is the float L times `scale`; with db, workgroup 1 + c adds the backward launch's partial
+// sums of channel c (g_tiles per plane) frame by frame, lane-strided, then the tree, in double: db[c].
+template <bool HEAD = false>
 __global__ __launch_bounds__(SL_TPB) void ssim_loss_finish_kernel(const float* __restrict__ part_s, const float* __restrict__ part_m,
                                                                   int B, int64_t per_frame, double n_ssim, double n_mse,
                                                                   double w_mse, double w_ssim, float* __restrict__ frame_ssim,
-                                                                  float* __restrict__ loss3) {
+                                                                  float* __restrict__ loss3, float scale,
+                                                                  const float* __restrict__ part_g, int64_t g_tiles, int C,
+                                                                  float* __restrict__ db) {
   __shared__ double red[SL_TPB / 64][2];
+  if constexpr (HEAD) {
+    if (blockIdx.x > 0) {
+      const int c = blockIdx.x - 1;
+      double s = 0.0, unused = 0.0;
+      for (int b = 0; b < B; ++b) {
+        const float* __restrict__ p = part_g + ((int64_t)b * C + c) * g_tiles;
+        for (int64_t i = threadIdx.x; i < g_tiles; i += SL_TPB) s += (double)p[i];
+      }
+      sl_block_sum2(s, unused, red);
+      if (threadIdx.x == 0) db[c] = (float)s;
+      return;
+    }
+  }
   double tot_s = 0.0, tot_m = 0.0;
   for (int b = 0; b < B; ++b) {
     double s = 0.0, m = 0.0;
@@ -281,7 +352,9 @@ __global__ __launch_bounds__(SL_TPB) void ssim_loss_finish_kernel(const float* _
   }
   if (threadIdx.x == 0) {
     const double mse = tot_m / n_mse, ssim = tot_s / (double)B;
-    loss3[0] = (float)(w_mse * mse + w_ssim * (1.0 - ssim));
+    const float l = (float)(w_mse * mse + w_ssim * (1.0 - ssim));
+    if constexpr (HEAD) loss3[0] = scale * l;
+    else loss3[0] = l;
     loss3[1] = (float)mse;
     loss3[2] = (float)ssim;
   }
@@ -291,6 +364,7 @@ struct SlPlan {
   int64_t planes, fwd_tiles, bwd_tiles, map_stride;
   int ntx, nty, btx;
   int64_t off_s, off_m, off_maps, total;   // the workspace: B frame values, the two kinds of partial sums, P | Q | R
+  int64_t off_g, total_head;               // nq_ssim_loss_head: + one partial sum per backward workgroup
 };
 
 inline bool sl_plan(int B, int C, int H, int W, SlPlan& p) {
@@ -308,7 +382,39 @@ inline bool sl_plan(int B, int C, int H, int W, SlPlan& p) {
   p.off_m = p.off_s + p.planes * p.fwd_tiles;
   p.off_maps = p.off_m + p.planes * p.fwd_tiles;
   p.total = p.off_maps + 3 * p.map_stride;
+  p.off_g = p.total;
+  p.total_head = p.off_g + p.planes * p.bwd_tiles;
   return true;
+}
+
+// the launches of nq_ssim_loss_head for one kind of target
+template <bool U8>
+void sl_head_launches(const SlPlan& p, hipStream_t st, const float* pred, const float* tgt, const uint8_t* cache, const int64_t* idx,
+                      float* loss3, float* grad, float* db, float* ws, int B, int C, int H, int W, float w_mse, float w_ssim,
+                      float scale) {
+  float *part_s = ws + p.off_s, *part_m = ws + p.off_m, *maps = ws + p.off_maps, *part_g = ws + p.off_g;
+  const dim3 fgrid((unsigned)p.fwd_tiles, (unsigned)p.planes), bgrid((unsigned)p.bwd_tiles, (unsigned)p.planes);
+  if (grad)
+    hipLaunchKernelGGL((ssim_loss_forward_kernel<true, U8>), fgrid, dim3(SL_TPB), 0, st, pred, tgt, cache, idx, C, part_s, part_m,
+                       maps, p.map_stride, H, W, p.ntx, p.nty);
+  else
+    hipLaunchKernelGGL((ssim_loss_forward_kernel<false, U8>), fgrid, dim3(SL_TPB), 0, st, pred, tgt, cache, idx, C, part_s, part_m,
+                       (float*)nullptr, (int64_t)0, H, W, p.ntx, p.nty);
+  const double n_mse = (double)p.planes * (double)H * (double)W;
+  const double n_map = (double)(H - SL_HALO) * (double)(W - SL_HALO);
+  if (grad) {   // the constants of nq_ssim_loss with grad_scale = scale
+    const float k_mse = (float)((double)scale * (double)w_mse * 2.0 / n_mse);
+    const float k_ssim = (float)(-(double)scale * (double)w_ssim / ((double)p.planes * n_map));
+    if (db)
+      hipLaunchKernelGGL((ssim_loss_backward_kernel<U8, true>), bgrid, dim3(SL_TPB), 0, st, pred, tgt, cache, idx, C, maps,
+                         p.map_stride, grad, part_g, H, W, p.btx, k_mse, k_ssim);
+    else
+      hipLaunchKernelGGL((ssim_loss_backward_kernel<U8, false>), bgrid, dim3(SL_TPB), 0, st, pred, tgt, cache, idx, C, maps,
+                         p.map_stride, grad, (float*)nullptr, H, W, p.btx, k_mse, k_ssim);
+  }
+  hipLaunchKernelGGL(ssim_loss_finish_kernel<true>, dim3(db ? 1u + (unsigned)C : 1u), dim3(SL_TPB), 0, st, part_s, part_m, B,
+                     (int64_t)C * p.fwd_tiles, (double)C * n_map, n_mse, (double)w_mse, (double)w_ssim, ws, loss3, scale, part_g,
+                     p.bwd_tiles, C, db);
 }
 
 }  // namespace
@@ -330,22 +436,47 @@ int nq_ssim_loss(const float* pred, const float* tgt, float* loss3, float* grad,
   const hipStream_t st = nq_s(stream);
   float *part_s = ws + p.off_s, *part_m = ws + p.off_m, *maps = ws + p.off_maps;
   const dim3 fgrid((unsigned)p.fwd_tiles, (unsigned)p.planes);
+  const uint8_t* no_cache = nullptr;
+  const int64_t* no_idx = nullptr;
   if (grad)
-    hipLaunchKernelGGL(ssim_loss_forward_kernel<true>, fgrid, dim3(SL_TPB), 0, st, pred, tgt, part_s, part_m, maps, p.map_stride,
-                       H, W, p.ntx, p.nty);
+    hipLaunchKernelGGL(ssim_loss_forward_kernel<true>, fgrid, dim3(SL_TPB), 0, st, pred, tgt, no_cache, no_idx, C, part_s, part_m,
+                       maps, p.map_stride, H, W, p.ntx, p.nty);
   else
-    hipLaunchKernelGGL(ssim_loss_forward_kernel<false>, fgrid, dim3(SL_TPB), 0, st, pred, tgt, part_s, part_m, (float*)nullptr,
-                       (int64_t)0, H, W, p.ntx, p.nty);
+    hipLaunchKernelGGL(ssim_loss_forward_kernel<false>, fgrid, dim3(SL_TPB), 0, st, pred, tgt, no_cache, no_idx, C, part_s, part_m,
+                       (float*)nullptr, (int64_t)0, H, W, p.ntx, p.nty);
   const double n_mse = (double)p.planes * (double)H * (double)W;
   const double n_map = (double)(H - SL_HALO) * (double)(W - SL_HALO);
   if (grad) {
     const float k_mse = (float)((double)grad_scale * (double)w_mse * 2.0 / n_mse);
     const float k_ssim = (float)(-(double)grad_scale * (double)w_ssim / ((double)p.planes * n_map));
-    hipLaunchKernelGGL(ssim_loss_backward_kernel, dim3((unsigned)p.bwd_tiles, (unsigned)p.planes), dim3(SL_TPB), 0, st, pred, tgt,
-                       maps, p.map_stride, grad, H, W, p.btx, k_mse, k_ssim);
+    hipLaunchKernelGGL(ssim_loss_backward_kernel<>, dim3((unsigned)p.bwd_tiles, (unsigned)p.planes), dim3(SL_TPB), 0, st, pred, tgt,
+                       no_cache, no_idx, C, maps, p.map_stride, grad, (float*)nullptr, H, W, p.btx, k_mse, k_ssim);
   }
-  hipLaunchKernelGGL(ssim_loss_finish_kernel, dim3(1), dim3(SL_TPB), 0, st, part_s, part_m, B, (int64_t)C * p.fwd_tiles,
-                     (double)C * n_map, n_mse, (double)w_mse, (double)w_ssim, ws, loss3);
+  hipLaunchKernelGGL(ssim_loss_finish_kernel<>, dim3(1), dim3(SL_TPB), 0, st, part_s, part_m, B, (int64_t)C * p.fwd_tiles,
+                     (double)C * n_map, n_mse, (double)w_mse, (double)w_ssim, ws, loss3, 1.f, (const float*)nullptr, (int64_t)0, C,
+                     (float*)nullptr);
+  return nq_launch_status();
+}
+
+int64_t nq_ssim_loss_head_ws_floats(int B, int C, int H, int W) {
+  SlPlan p;
+  return sl_plan(B, C, H, W, p) ? p.total_head : 0;
+}
+
+int nq_ssim_loss_head(const float* pred, const float* tgt, const uint8_t* cache_u8, const int64_t* idx, float* loss3, float* grad,
+                      float* db, float* ws, int B, int C, int H, int W, float w_mse, float w_ssim, float scale,
+                      nq_stream_t stream) {
+  SlPlan p;
+  if (!pred || !loss3 || !ws || !sl_plan(B, C, H, W, p)) return NQ_ERR_INVALID;
+  if ((tgt == nullptr) == (cache_u8 == nullptr) || (cache_u8 && !idx)) return NQ_ERR_INVALID;
+  if (db && !grad) return NQ_ERR_INVALID;   // the bias gradient is the sum of what the backward launch writes
+  if (!std::isfinite(w_mse) || !std::isfinite(w_ssim) || !std::isfinite(scale) || w_mse < 0.f || w_ssim < 0.f) return NQ_ERR_INVALID;
+  if (p.planes > 65535 || p.bwd_tiles > 0x7fffffffLL) return NQ_ERR_UNSUPPORTED;   // grid.y, grid.x
+  const hipStream_t st = nq_s(stream);
+  if (cache_u8)
+    sl_head_launches<true>(p, st, pred, tgt, cache_u8, idx, loss3, grad, db, ws, B, C, H, W, w_mse, w_ssim, scale);
+  else
+    sl_head_launches<false>(p, st, pred, tgt, cache_u8, idx, loss3, grad, db, ws, B, C, H, W, w_mse, w_ssim, scale);
   return nq_launch_status();
 }
 

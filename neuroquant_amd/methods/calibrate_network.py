@@ -15,6 +15,8 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     --loss_domain yuv420 calibrates on the weighted plane MSEs of the 8-bit YUV 4:2:0 codes instead of RGB squared error
     (--yuv_weights WY WU WV, default 6 1 1; matrix and range from --yuv_matrix / --yuv_range) and every evaluation also logs
     PSNR-Y / U / V and their 6:1:1 mean: DESIGN.md §19;
+    --rec_loss ssim | Fusion1 | Fusion3 | Fusion5 calibrates on the reference's MSE + (1 - SSIM) losses instead of squared error
+    (--rec_weights W_MSE W_SSIM: free weights) and every evaluation also logs the mean single-scale SSIM: DESIGN.md §21;
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
     packed at their bit-width and entropy-coded levels; --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
@@ -51,6 +53,7 @@ def parse_args(argv):
                    help='reconstruction loss of the calibration: RGB mean squared error, or the weighted plane MSEs of the 8-bit '
                         'YUV 4:2:0 codes (--yuv_matrix, --yuv_range, --yuv_weights; DESIGN.md §19)')
     add_yuv_loss_args(p)
+    add_rec_loss_args(p)
     p.add_argument('--vid', type=str, default='Bunny')
     p.add_argument('--data_split', type=str, default='1_1_1')
     p.add_argument('--batch_size', default=12, type=int)
@@ -142,6 +145,42 @@ def add_yuv_loss_args(p):
                    help='plane weights of the YUV 4:2:0 objective (--loss_domain yuv420 / loss: yuv420; DESIGN.md §19)')
 
 
+# the reference's losses of MSE and single-scale SSIM (reference utils.py:119-130): name -> (w_mse, w_ssim); the one table of the
+# calibration driver (--rec_loss) and the trainer (regress.SSIM_LOSSES, `loss:` of a config)
+SSIM_LOSSES = {'ssim': (0.0, 1.0), 'Fusion1': (0.3, 0.7), 'Fusion3': (0.5, 0.5), 'Fusion5': (0.7, 0.3)}
+
+
+def add_rec_loss_args(p):
+    """The flags of the calibration's MSE + SSIM objective: a name of the reference's, or free weights."""
+    g = p.add_mutually_exclusive_group()
+    g.add_argument('--rec_loss', type=str, default='l2', choices=['l2'] + list(SSIM_LOSSES),
+                   help='reconstruction loss of the calibration: squared error, or w_mse * MSE + w_ssim * (1 - SSIM) with the '
+                        "reference's weights: " + ', '.join(f'{k} {v}' for k, v in SSIM_LOSSES.items()))
+    g.add_argument('--rec_weights', type=float, nargs=2, default=None, metavar=('W_MSE', 'W_SSIM'),
+                   help='free weights of the MSE + SSIM reconstruction loss')
+
+
+def rec_loss_params(args):
+    """-> None for the squared error (--rec_loss l2, no --rec_weights), else dict(w_mse, w_ssim) of ops.ssim_loss_head_grad /
+    model_reconstruction(ssim=...).  ValueError for an unknown name, both flags, bad weights and --loss_domain yuv420."""
+    name, w = getattr(args, 'rec_loss', None) or 'l2', getattr(args, 'rec_weights', None)
+    if w is not None:
+        if name != 'l2':
+            raise ValueError('--rec_loss and --rec_weights exclude each other')
+        if len(w) != 2:
+            raise ValueError(f'--rec_weights takes W_MSE W_SSIM, got {w!r}')
+        w = ops.ssim_loss_args('--rec_weights', (1, 1, 11, 11), (1, 1, 11, 11), *w)   # finite, >= 0, a positive sum
+    elif name == 'l2':
+        return None
+    elif name in SSIM_LOSSES:
+        w = SSIM_LOSSES[name]
+    else:
+        raise ValueError(f"rec_loss must be one of {['l2'] + list(SSIM_LOSSES)}, got {name!r}")
+    if getattr(args, 'loss_domain', 'rgb') == 'yuv420':
+        raise ValueError('the MSE + SSIM objective is defined on RGB frames: it does not combine with --loss_domain yuv420')
+    return dict(w_mse=float(w[0]), w_ssim=float(w[1]))
+
+
 def yuv_loss_params(args):
     """matrix / full_range / weights of the YUV 4:2:0 objective (ops.yuv420_loss) and of the PSNR-Y / U / V evaluation: the
     --yuv_matrix and --yuv_range that describe a clip (bt709, limited when unset; a .y4m / .yuv --data_path without --yuv_range
@@ -209,6 +248,7 @@ def load_frames(args, cfg, device):
 
 
 METRIC_NAMES = ['pred_seen_psnr', 'pred_seen_ssim', 'pred_unseen_psnr', 'pred_unseen_ssim']   # reference args.metric_names
+SSIM_METRIC_NAME = 'ssim_single_scale'    # added by an MSE + SSIM objective (--rec_loss / --rec_weights)
 YUV_METRIC_NAMES = ['psnr_y', 'psnr_u', 'psnr_v', 'psnr_yuv_611']    # added by --loss_domain yuv420 (the player's keys)
 
 
@@ -226,6 +266,9 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
     # those of the cached ground truth (both through ops.frames_to_yuv420), in the player's format
     yuv = yuv_loss_params(args) if getattr(args, 'loss_domain', 'rgb') == 'yuv420' else None
     psnr_yuv = []
+    # --rec_loss ssim / Fusion* / --rec_weights: also the figure that objective is after, the single-scale SSIM (ops.ssim)
+    ssim_obj = rec_loss_params(args)
+    ssim1 = []
     psnr, ssim, embeds, dec_times = [], [], [], []
     for i in range(n):
         idx = torch.tensor([i], device=dev)
@@ -244,6 +287,8 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
             h, w = img.shape[-2:]
             psnr_yuv.append(ops.yuv420_psnr(ops.frames_to_yuv420(out, yuv['matrix'], yuv['full_range']),
                                             ops.frames_to_yuv420(img, yuv['matrix'], yuv['full_range']), h, w))
+        if ssim_obj is not None:
+            ssim1.append(ops.ssim(out, img))
         if i % args.print_freq == 0 or i == n - 1:
             logging.info('[{}], Eval at Step [{}/{}], FPS {}, PSNR {}, MS-SSIM {}'.format(
                 datetime.now().strftime("%Y/%m/%d %H:%M:%S"), i + 1, n,
@@ -263,6 +308,10 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
         m611 = ((6.0 * p[:, 0] + p[:, 1] + p[:, 2]) / 8.0).mean()
         args.eval_metrics.update(dict(zip(YUV_METRIC_NAMES, [y, u, v, m611])))
         logging.info('yuv420: PSNR-Y {} U {} V {} | 6:1:1 {}'.format(*(RoundTensor(t, 2) for t in (y, u, v, m611))))
+    if ssim_obj is not None:   # over all frames
+        s1 = torch.cat(ssim1).cpu().mean()
+        args.eval_metrics[SSIM_METRIC_NAME] = s1
+        logging.info('ssim objective {}: SSIM {}'.format(ssim_obj, RoundTensor(s1, 4)))
     model.train()
     return res, embeds
 
@@ -346,12 +395,16 @@ def calibrate(args, cfg):
     loss_domain = getattr(args, 'loss_domain', 'rgb')
     if loss_domain == 'yuv420':
         logging.info('reconstruction loss: YUV 4:2:0 plane MSEs, {}'.format(yuv_loss_params(args)))
+    ssim_obj = rec_loss_params(args)
+    if ssim_obj is not None:
+        logging.info('reconstruction loss: C * (w_mse * MSE + w_ssim * (1 - SSIM)), {}'.format(ssim_obj))
     start = datetime.now()
     qnn.set_quant_state(weight_quant=True)
     model_reconstruction(qnn, cali_data=cali_data, gt=train_loader, arch=args.arch, batch_size=args.batch_size,
                          iters=args.iters_w, weight=args.weight, opt_mode='mse', hadamard=args.hadamard,
                          b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr,
-                         loss_domain=loss_domain, yuv=yuv_loss_params(args) if loss_domain == 'yuv420' else None)
+                         loss_domain=loss_domain, yuv=yuv_loss_params(args) if loss_domain == 'yuv420' else None,
+                         ssim=ssim_obj)
     torch.cuda.synchronize()
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
 

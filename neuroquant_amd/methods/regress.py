@@ -22,7 +22,7 @@ import torch
 from ..models import HNeRV, NeRV
 from ..utils import CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger
 from .. import ops
-from .calibrate_network import (add_yuv_args, add_yuv_loss_args, evaluate, load_frames, report_line, seed_all,
+from .calibrate_network import (SSIM_LOSSES, add_yuv_args, add_yuv_loss_args, evaluate, load_frames, report_line, seed_all,
                                 yuv_loss_params)
 
 
@@ -66,8 +66,8 @@ def adjust_lr(optimizer, cur_epoch, args, eta_min=0.05):
     return args.lr * lr_mult
 
 
-# the members of the reference's loss table (utils.py:119-130) made of MSE and single-scale SSIM only: (w_mse, w_ssim)
-SSIM_LOSSES = {'ssim': (0.0, 1.0), 'Fusion1': (0.3, 0.7), 'Fusion3': (0.5, 0.5), 'Fusion5': (0.7, 0.3)}
+# SSIM_LOSSES (imported above): the members of the reference's loss table (utils.py:119-130) made of MSE and single-scale SSIM
+# only, name -> (w_mse, w_ssim); one table with the calibration driver's --rec_loss (calibrate_network.py)
 
 
 def loss_params(args, cfg):

@@ -1903,6 +1903,68 @@ def ssim_loss(pred, tgt, w_mse=0.0, w_ssim=1.0):
     return _SsimLossFn.apply(pred, tgt, float(w_mse), float(w_ssim))
 
 
+ssim_loss_head_launches = 0    # nq_ssim_loss_head calls issued (or captured) by this process: the default paths issue none
+
+
+def ssim_loss_head_raw(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ssim=1.0, head=False):
+    """One nq_ssim_loss_head call on images `pred` (B, C, H, W), H, W >= 11 -> (loss3, grad, db): loss3 = (C * L, mean MSE, mean
+    SSIM) with L of ssim_loss_raw (the factor C puts weights (1, 0) on the scale of lp_loss(p=2), as the 3 of yuv420_loss_raw);
+    the target is `tgt` or frames `cache_u8[idx] / 255` read straight from the uint8 cache.  head=False: grad = C * dL/dpred,
+    db = None.  head=True (`pred` = tanh(conv) * 0.5 + 0.5): grad = the gradient at the conv OUTPUT and db its per-channel sums
+    (the head's bias gradient), as l2_loss_tanh_head_raw.  ValueError for a bad shape, target or weights before any launch.
+    The VALUES of idx are not among what is checked: they stay on the device (a host read would stop a capture), and keeping
+    them inside [0, N) is the caller's responsibility, as for l2_loss_tanh_head_raw and yuv420_loss_raw."""
+    global ssim_loss_head_launches
+    if not isinstance(pred, torch.Tensor):
+        raise ValueError(f"ssim_loss_head takes (B, C, H, W) images, got {type(pred)}")
+    if (tgt is None) == (cache_u8 is None):
+        raise ValueError("ssim_loss_head takes exactly one of tgt and cache_u8 + idx")
+    if cache_u8 is not None:
+        if not isinstance(cache_u8, torch.Tensor) or cache_u8.dtype != torch.uint8 or cache_u8.dim() != 4 \
+                or not isinstance(idx, torch.Tensor) or idx.dim() != 1:
+            raise ValueError("ssim_loss_head: the frame cache must be a uint8 (N, C, H, W) tensor with a 1-d idx")
+        tgt_shape = (idx.numel(),) + tuple(cache_u8.shape[1:])
+    else:
+        if not isinstance(tgt, torch.Tensor):
+            raise ValueError(f"ssim_loss_head takes a (B, C, H, W) target, got {type(tgt)}")
+        tgt_shape = tgt.shape
+    w = ssim_loss_args("ssim_loss_head", pred.shape, tgt_shape, w_mse, w_ssim)
+    pred_d = _dev(pred.detach(), "pred")
+    B, C, H, W = pred_d.shape
+    if cache_u8 is not None:
+        if not cache_u8.is_cuda or not cache_u8.is_contiguous():
+            raise RuntimeError("frame cache must be a contiguous uint8 GPU tensor of the image's shape")
+        idx = idx.to(device=pred_d.device, dtype=torch.int64).contiguous()
+    else:
+        tgt = _dev(tgt.detach(), "tgt")
+    loss3 = torch.empty(3, device=pred_d.device, dtype=torch.float32)
+    grad = torch.empty_like(pred_d)
+    db = torch.empty(C, device=pred_d.device, dtype=torch.float32) if head else None
+    ws = torch.empty(_q("nq_ssim_loss_head_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
+    ssim_loss_head_launches += 1
+    L.check(_timed("ssim_loss_head", lambda: L.lib().nq_ssim_loss_head(
+        _p(pred_d), _p(tgt) if cache_u8 is None else None, _p(cache_u8) if cache_u8 is not None else None,
+        _p(idx) if cache_u8 is not None else None, _p(loss3), _p(grad), _p(db), _p(ws), B, C, H, W, w[0], w[1], float(C),
+        _stream())), "ssim_loss_head")
+    return loss3, grad, db
+
+
+def ssim_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ssim=1.0, node=None):
+    """l2_loss_head_grad for the MSE + SSIM objective: -> (loss3, g) where `pred.backward(g)` (or decoder_backward_steps(node,
+    g)) continues the backward pass.  When `pred` carries the hand-over slot of a tanh-headed decoder node, g is the
+    gradient at the head conv's OUTPUT and the head's bias gradient is handed over with it; otherwise g = C * dL/dpred and the
+    ordinary backward runs.  Never None: the kernel has no tiling restriction."""
+    head = getattr(node if node is not None else getattr(pred, "grad_fn", None), "nq_head", None)
+    if not isinstance(head, _HeadHandoff) or os.environ.get("NQ_FUSED_LOSS", "1") == "0":
+        loss3, g, _ = ssim_loss_head_raw(pred, tgt, cache_u8, idx, w_mse, w_ssim, head=False)
+        return loss3, g
+    # (a result of ops.fused_head_loss that nobody asked for is dropped: this objective replaces it)
+    head.loss = None
+    loss3, head.dconv, head.db = ssim_loss_head_raw(pred, tgt, cache_u8, idx, w_mse, w_ssim, head=True)
+    head.version = head.dconv._version
+    return loss3, head.dconv
+
+
 def ssim(out, gt):
     """per-frame single-scale SSIM of (F, C, H, W) images -> (F,) fp32 (pytorch_msssim.ssim(out, gt, data_range=1,
     size_average=False)); a frame's value depends on that frame's bytes only.  Forward only (inputs are detached)."""

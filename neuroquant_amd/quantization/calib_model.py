@@ -48,9 +48,10 @@ class LossFunction:
 
     def __init__(self, model: nn.Module, round_loss: str = 'relaxation', weight: float = 1., rec_loss: str = 'mse',
                  max_count: int = 2000, b_range: tuple = (10, 2), decay_start: float = 0.0, warmup: float = 0.0,
-                 p: float = 2., yuv: dict = None):
+                 p: float = 2., yuv: dict = None, ssim: dict = None):
         self.model = model
         self.yuv = dict(yuv or {})   # rec_loss 'yuv420': matrix, full_range, weights of ops.yuv420_loss
+        self.ssim = dict(ssim or {})   # rec_loss 'ssim': w_mse, w_ssim of ops.ssim_loss
         self.round = round_loss
         self.weight = weight
         self.rec = rec_loss
@@ -69,6 +70,8 @@ class LossFunction:
         self.count += 1
         if self.rec == 'yuv420':
             rec_loss = ops.yuv420_loss(pred, tgt, **self.yuv)
+        elif self.rec == 'ssim':   # on the scale of lp_loss, as model_reconstruction(ssim=...) logs it
+            rec_loss = ops.ssim_loss(pred, tgt, **self.ssim) * pred.shape[1]
         elif self.rec == 'mse':
             rec_loss = lp_loss(pred, tgt, p=self.p)
         else:
@@ -176,7 +179,7 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                          iters: int = 20000, weight: float = 0.01, opt_mode: str = 'mse', hadamard: bool = True,
                          b_range: tuple = (20, 2), warmup: float = 0.0, p: float = 2.0, lr: float = 0.0015,
                          recorder: list = None, max_steps: int = None, step_hook=None, probe=None,
-                         loss_domain: str = 'rgb', yuv: dict = None):
+                         loss_domain: str = 'rgb', yuv: dict = None, ssim: dict = None):
     """Network-wise calibration, in place (reference calib_model.py:92-240).
 
     gt: any sized iterable of dict batches {'img' (B,3,H,W), 'idx' (B,), 'norm_idx'}; cali_data[idx] feeds the
@@ -187,7 +190,9 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
     L.b.grad = dL/dW^, dL/db^) and the list of parameter gradients in optimiser order (gradient parity tests).
     loss_domain 'yuv420' replaces lp_loss by the weighted plane MSEs of the 8-bit YUV 4:2:0 codes (ops.yuv420_loss_head_grad,
     DESIGN.md §19) with yuv = dict(matrix, full_range, weights) (bt709, limited range, 6:1:1 where absent); the logged `rec` is
-    that loss.  Everything else of the iteration is the same.
+    that loss.  ssim = dict(w_mse, w_ssim) replaces lp_loss by C * mean_b[w_mse MSE_b + w_ssim (1 - SSIM_b)], the reference's
+    ssim / Fusion losses on the scale of lp_loss (ops.ssim_loss_head_grad; weights (1, 0) are lp_loss); the
+    logged `rec` is that loss; it does not combine with loss_domain 'yuv420'.  Everything else of the iteration is the same.
     """
     if arch not in ('hnerv', 'nerv'):
         raise ValueError
@@ -201,6 +206,13 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
     if loss_domain == 'yuv420':   # a bad matrix or bad weights stop here, before the first iteration
         ops.yuv420_loss_args('model_reconstruction', (1, 3, 2, 2), yuv.get('matrix', 'bt709'), yuv.get('full_range', False),
                              yuv.get('weights', ops.YUV_LOSS_WEIGHTS))
+    if ssim is not None:   # bad keys, bad weights and the YUV combination stop here, before the first iteration
+        if not isinstance(ssim, dict) or set(ssim) != {'w_mse', 'w_ssim'}:
+            raise ValueError(f"ssim takes dict(w_mse, w_ssim), got {sorted(ssim) if isinstance(ssim, dict) else ssim!r}")
+        if loss_domain == 'yuv420':
+            raise ValueError("the SSIM objective is defined on RGB frames: it does not combine with loss_domain 'yuv420'")
+        ssim = dict(zip(('w_mse', 'w_ssim'), ops.ssim_loss_args('model_reconstruction', (1, 1, 11, 11), (1, 1, 11, 11),
+                                                                ssim['w_mse'], ssim['w_ssim'])))
     model.set_quant_state(True)
     device = next(model.parameters()).device
     layers = [_Layer(m, hadamard) for m in _quant_modules(model)]
@@ -354,8 +366,8 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                         L._finish(fq[2 * i], fq[2 * i + 1])
             node = None
             # (the loss tail runs behind the head convolution when the decoder is the fused stack: ops.fused_head_loss)
-            # (... for lp_loss only: the YUV objective has its own launch behind the head)
-            if loss_domain == 'yuv420':
+            # (... for lp_loss only: the YUV and the SSIM objective have their own launch behind the head)
+            if loss_domain == 'yuv420' or ssim is not None:
                 loss_req = contextlib.nullcontext()
             else:
                 loss_req = ops.fused_head_loss(cache_u8=img[0], idx=img[1]) if isinstance(img, tuple) else ops.fused_head_loss(tgt=img)
@@ -374,6 +386,11 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                 loss4, dimg = ops.yuv420_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **yuv) \
                     if isinstance(img, tuple) else ops.yuv420_loss_head_grad(img_out, tgt=img, node=node, **yuv)
                 fused = (loss4[0], dimg)
+            elif ssim is not None:
+                # MSE + SSIM instead: same hand-over, same targets
+                loss3, dimg = ops.ssim_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **ssim) \
+                    if isinstance(img, tuple) else ops.ssim_loss_head_grad(img_out, tgt=img, node=node, **ssim)
+                fused = (loss3[0], dimg)
             else:
                 fused = ops.l2_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node) if isinstance(img, tuple) \
                     else ops.l2_loss_head_grad(img_out, tgt=img, node=node)
