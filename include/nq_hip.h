@@ -659,6 +659,40 @@ NQ_API int nq_ssim_loss_head(const float* pred, const float* tgt, const uint8_t*
                       float* grad, float* db, float* ws, int B, int C, int H, int W, float w_mse, float w_ssim, float scale,
                       nq_stream_t stream);
 
+/* ---- MSE + five-scale MS-SSIM training loss with its exact gradient (additive: nq_abi_version() stays 7) ----
+ * X_1 = pred, Y_1 = tgt: (B, C, H, W) fp32, min(H, W) > 160.  Scales s = 1 .. 5 of h_s x w_s pixels:
+ *   X_{s+1} = avg_pool2d(X_s, 2, 2, padding (h_s % 2, w_s % 2)), divisor 4 (the padding counts), as nq_ms_ssim; the same for Y.
+ *   Window, valid separable filter g*, C1, C2, A1, A2, B1, B2 as nq_ssim_loss states them; per scale the maps
+ *   cs = A2 / B2 and ssim = A1 A2 / (B1 B2) on the (h_s - 10) x (w_s - 10) valid region, N_s its pixel count.
+ *   v_s(b, c) = mean cs (s = 1 .. 4), mean ssim (s = 5);  w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+ *   M(b, c) = prod_s relu(v_s)^(w_s),  MS_b = mean_c M(b, c),  MSE_b = mean_{c,h,w} (X - Y)^2
+ *   L = mean_b [ w_mse MSE_b + w_ms (1 - MS_b) ]
+ *   loss3[3] = {L, mean MSE, mean MS-SSIM}; after the call ws[0 .. B) holds MS_b of every frame.
+ * Gradient.  On a plane where every v_s > 0: dL/dv_s = -(w_ms / (B C)) w_s M / v_s.  With the five moments as the independent
+ * quantities and gT* the adjoint of the valid filter (nq_ssim_loss), the derivative maps of scale s are
+ *   s = 5: P, Q, R of nq_ssim_loss;   s < 5 (the luminance factor dropped): P = d cs / d mu_x = 2 (mu_x cs - mu_y) / B2,
+ *   Q = d cs / d Sxx = -cs / B2,  R = d cs / d Sxy = 2 / B2
+ *   own_s = dL/dv_s / N_s (gT*P + 2 X_s gT*Q + Y_s gT*R)
+ *   G_s = own_s + up(G_{s+1}),  up(G)[i, j] = G[(i + h_s % 2) / 2, (j + w_s % 2) / 2] / 4  (the exact adjoint of the pooling)
+ *   dL/dX = G_1 + w_mse 2 (X - Y) / (B C H W)
+ * On a plane where some v_s <= 0 the relu is active and M = 0 exactly; the MS-SSIM part of that plane's gradient is DEFINED as
+ * exactly zero at every scale (autograd through 0^w gives NaN there).
+ *   grad != NULL: grad (B, C, H, W) = grad_scale dL/dX.  grad == NULL: forward only, no derivative map is written, the same
+ *   loss3 bits.
+ * Eleven launches (six forward only): one forward launch per scale (the next scale's pooled images, the derivative maps, one
+ * partial sum per workgroup), one finishing launch (partial sums added in a fixed order in double; v_s, M, the coefficients
+ * grad_scale dL/dv_s / N_s and the clamp, written to the workspace), one backward launch per scale from 5 down to 1 (a gather,
+ * every element one writer).  No atomics, no host read between launches: bit-identical from call to call, capturable in a
+ * hipGraph; a frame's MS_b depends on that frame's bytes only.  pred == tgt gives MS-SSIM = 1, MSE = 0 and a zero gradient exactly.
+ *   ws: nq_msssim_loss_ws_floats(B, C, H, W) floats (0 for arguments the entry refuses) =
+ *       B + 5 B C + B C T_1 + sum_s B C T_s + 3 sum_{s>1} B C h_s w_s + 3 sum_s B C N_s,  T_s = ceil((h_s - 10) / 8) ceil((w_s - 10) / 118).
+ * NQ_ERR_INVALID, before the device is touched, for null pred / tgt / loss3 / ws, non-positive sizes, min(H, W) <= 160, a
+ * negative or non-finite weight, both weights zero, a non-finite grad_scale and an element count past int64;
+ * NQ_ERR_UNSUPPORTED for B * C > 65535. */
+NQ_API int64_t nq_msssim_loss_ws_floats(int B, int C, int H, int W);
+NQ_API int nq_msssim_loss(const float* pred, const float* tgt, float* loss3, float* grad, float* ws, int B, int C, int H, int W,
+                   float w_mse, float w_ms, float grad_scale, nq_stream_t stream);
+
 /* Entropy-coded levels: 64-lane interleaved rANS, one frequency table per tensor (probabilities in units of
  * 1 / 4096), 32-bit states >= 2^16, 16-bit words.  The n levels (flat, C order) are cut into chunks of `chunk` symbols (a
  * multiple of 64, the last may be short); lane l of a chunk owns its symbols l, l + 64, ...  One wavefront decodes one chunk.

@@ -193,6 +193,8 @@ def _load():
     sig("nq_ssim_loss", I, P, P, P, P, P, I, I, I, I, F, F, F, P)
     sig("nq_ssim_loss_head_ws_floats", L, I, I, I, I)
     sig("nq_ssim_loss_head", I, P, P, P, P, P, P, P, P, I, I, I, I, F, F, F, P)
+    sig("nq_msssim_loss_ws_floats", L, I, I, I, I)
+    sig("nq_msssim_loss", I, P, P, P, P, P, I, I, I, I, F, F, F, P)
     sig("nq_rans_chunks", L, L, L)
     sig("nq_rans_decode", I, P, P, P, P, L, I, L, P, P, L, P, P, P)
     sig("nq_embed_symbols", I, P, P, P, L, L, L, I, I, P, P, P)
@@ -219,7 +221,7 @@ EXPORTS = (
     "nq_packed_words", "nq_pack_levels", "nq_unpack_dequant", "nq_frames_to_u8",
     "nq_yuv420_frame_bytes", "nq_frames_to_yuv420", "nq_yuv420_to_rgb_u8", "nq_yuv420_sse",
     "nq_yuv420_loss_ws_floats", "nq_yuv420_loss", "nq_ssim_loss_ws_floats", "nq_ssim_loss",
-    "nq_ssim_loss_head_ws_floats", "nq_ssim_loss_head",
+    "nq_ssim_loss_head_ws_floats", "nq_ssim_loss_head", "nq_msssim_loss_ws_floats", "nq_msssim_loss",
     "nq_rans_chunks", "nq_rans_decode",
     "nq_embed_symbols", "nq_embed_restore",
     "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",

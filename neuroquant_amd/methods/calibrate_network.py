@@ -17,6 +17,8 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     PSNR-Y / U / V and their 6:1:1 mean: DESIGN.md §19;
     --rec_loss ssim | Fusion1 | Fusion3 | Fusion5 calibrates on the reference's MSE + (1 - SSIM) losses instead of squared error
     (--rec_weights W_MSE W_SSIM: free weights) and every evaluation also logs the mean single-scale SSIM: DESIGN.md §21;
+    --rec_loss msssim calibrates on 1 - MS-SSIM, the five-scale figure every evaluation logs (--rec_ms_weights W_MSE W_MS: free
+    weights of MSE and 1 - MS-SSIM; frames whose smaller side exceeds 160): DESIGN.md §22;
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
     packed at their bit-width and entropy-coded levels; --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
@@ -150,14 +152,21 @@ def add_yuv_loss_args(p):
 SSIM_LOSSES = {'ssim': (0.0, 1.0), 'Fusion1': (0.3, 0.7), 'Fusion3': (0.5, 0.5), 'Fusion5': (0.7, 0.3)}
 
 
+# the MS-SSIM objective: the name --rec_loss and a config's `loss:` share, and its default (w_mse, w_ms)
+MSSSIM_LOSS, MSSSIM_WEIGHTS = 'msssim', (0.0, 1.0)
+
+
 def add_rec_loss_args(p):
     """The flags of the calibration's MSE + SSIM objective: a name of the reference's, or free weights."""
     g = p.add_mutually_exclusive_group()
-    g.add_argument('--rec_loss', type=str, default='l2', choices=['l2'] + list(SSIM_LOSSES),
+    g.add_argument('--rec_loss', type=str, default='l2', choices=['l2'] + list(SSIM_LOSSES) + [MSSSIM_LOSS],
                    help='reconstruction loss of the calibration: squared error, or w_mse * MSE + w_ssim * (1 - SSIM) with the '
-                        "reference's weights: " + ', '.join(f'{k} {v}' for k, v in SSIM_LOSSES.items()))
+                        "reference's weights: " + ', '.join(f'{k} {v}' for k, v in SSIM_LOSSES.items()) +
+                        f'; or {MSSSIM_LOSS}: 1 - MS-SSIM, the five-scale figure every evaluation logs (DESIGN.md §22)')
     g.add_argument('--rec_weights', type=float, nargs=2, default=None, metavar=('W_MSE', 'W_SSIM'),
                    help='free weights of the MSE + SSIM reconstruction loss')
+    g.add_argument('--rec_ms_weights', type=float, nargs=2, default=None, metavar=('W_MSE', 'W_MS'),
+                   help='free weights of the MSE + MS-SSIM reconstruction loss w_mse * MSE + w_ms * (1 - MS-SSIM)')
 
 
 def rec_loss_params(args):
@@ -170,7 +179,7 @@ def rec_loss_params(args):
         if len(w) != 2:
             raise ValueError(f'--rec_weights takes W_MSE W_SSIM, got {w!r}')
         w = ops.ssim_loss_args('--rec_weights', (1, 1, 11, 11), (1, 1, 11, 11), *w)   # finite, >= 0, a positive sum
-    elif name == 'l2':
+    elif name in ('l2', MSSSIM_LOSS):   # the MS-SSIM objective has a function of its own: rec_msssim_params
         return None
     elif name in SSIM_LOSSES:
         w = SSIM_LOSSES[name]
@@ -179,6 +188,25 @@ def rec_loss_params(args):
     if getattr(args, 'loss_domain', 'rgb') == 'yuv420':
         raise ValueError('the MSE + SSIM objective is defined on RGB frames: it does not combine with --loss_domain yuv420')
     return dict(w_mse=float(w[0]), w_ssim=float(w[1]))
+
+
+def rec_msssim_params(args):
+    """-> None unless --rec_loss msssim (weights (0, 1)) or --rec_ms_weights W_MSE W_MS is given, else dict(w_mse, w_ms) of
+    ops.msssim_loss_head_grad / model_reconstruction(msssim=...).  ValueError for both flags, bad weights and --loss_domain yuv420."""
+    name, w = getattr(args, 'rec_loss', None) or 'l2', getattr(args, 'rec_ms_weights', None)
+    if w is not None:
+        if name != 'l2' or getattr(args, 'rec_weights', None) is not None:
+            raise ValueError('--rec_loss, --rec_weights and --rec_ms_weights exclude each other')
+        if len(w) != 2:
+            raise ValueError(f'--rec_ms_weights takes W_MSE W_MS, got {w!r}')
+        w = ops.ms_ssim_loss_args('--rec_ms_weights', (1, 1, 161, 161), (1, 1, 161, 161), *w)   # finite, >= 0, a positive sum
+    elif name == MSSSIM_LOSS:
+        w = MSSSIM_WEIGHTS
+    else:
+        return None
+    if getattr(args, 'loss_domain', 'rgb') == 'yuv420':
+        raise ValueError('the MSE + MS-SSIM objective is defined on RGB frames: it does not combine with --loss_domain yuv420')
+    return dict(w_mse=float(w[0]), w_ms=float(w[1]))
 
 
 def yuv_loss_params(args):
@@ -253,11 +281,13 @@ YUV_METRIC_NAMES = ['psnr_y', 'psnr_u', 'psnr_v', 'psnr_yuv_611']    # added by 
 
 
 @torch.no_grad()
-def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
+def evaluate(model, cache: FrameCache, args, cfg, embeddings=None, msssim=None):
     """Per-frame decode + PSNR + MS-SSIM (reference calibrate_network.py:82-145); returns ([seen_psnr, unseen_psnr],
     embeddings) and leaves all four means on args.eval_metrics, keyed by METRIC_NAMES (as the reference leaves args.fps).
     Frames too small for five scales (min(H, W) <= 160) are evaluated for PSNR only: MS-SSIM is logged as n/a and stored
-    as NaN.  embeddings (N, c, h, w): frame i is decoded from row i instead of model.encode's output."""
+    as NaN.  embeddings (N, c, h, w): frame i is decoded from row i instead of model.encode's output.  msssim: dict(w_mse,
+    w_ms) of an MS-SSIM objective the caller optimises (the trainer's `loss: msssim`; the calibration driver's flags are read
+    from args): one more line names it beside the MS-SSIM it is after."""
     model.eval()
     n = len(cache)
     dev = cache.frames.device
@@ -312,6 +342,9 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None):
         s1 = torch.cat(ssim1).cpu().mean()
         args.eval_metrics[SSIM_METRIC_NAME] = s1
         logging.info('ssim objective {}: SSIM {}'.format(ssim_obj, RoundTensor(s1, 4)))
+    ms_obj = msssim if msssim is not None else rec_msssim_params(args)
+    if ms_obj is not None and with_ssim:   # over all frames: the figure that objective is after is the MS-SSIM logged above
+        logging.info('msssim objective ({}, {}): MS-SSIM {}'.format(ms_obj['w_mse'], ms_obj['w_ms'], RoundTensor(ssim.mean(), 4)))
     model.train()
     return res, embeds
 
@@ -398,13 +431,16 @@ def calibrate(args, cfg):
     ssim_obj = rec_loss_params(args)
     if ssim_obj is not None:
         logging.info('reconstruction loss: C * (w_mse * MSE + w_ssim * (1 - SSIM)), {}'.format(ssim_obj))
+    ms_obj = rec_msssim_params(args)
+    if ms_obj is not None:
+        logging.info('reconstruction loss: C * (w_mse * MSE + w_ms * (1 - MS-SSIM)), {}'.format(ms_obj))
     start = datetime.now()
     qnn.set_quant_state(weight_quant=True)
     model_reconstruction(qnn, cali_data=cali_data, gt=train_loader, arch=args.arch, batch_size=args.batch_size,
                          iters=args.iters_w, weight=args.weight, opt_mode='mse', hadamard=args.hadamard,
                          b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr,
                          loss_domain=loss_domain, yuv=yuv_loss_params(args) if loss_domain == 'yuv420' else None,
-                         ssim=ssim_obj)
+                         ssim=ssim_obj, msssim=ms_obj)
     torch.cuda.synchronize()
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
 

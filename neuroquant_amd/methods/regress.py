@@ -1,7 +1,7 @@
 """FP32 INR trainer (counterpart of the reference's methods/regress.py:151-322; SURVEY §8f-4, a "next" row).
 
-Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss, `loss: yuv420` or the
-reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5`, per-epoch
+Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss, `loss: yuv420`, the
+reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5` or `loss: msssim` (1 - MS-SSIM, optional `loss_weights`), per-epoch
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
 from the GPU-resident cache; the ConvNeXt encoder and Adam stay in PyTorch.  Evaluations report PSNR and MS-SSIM
@@ -22,7 +22,7 @@ import torch
 from ..models import HNeRV, NeRV
 from ..utils import CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger
 from .. import ops
-from .calibrate_network import (SSIM_LOSSES, add_yuv_args, add_yuv_loss_args, evaluate, load_frames, report_line, seed_all,
+from .calibrate_network import (MSSSIM_LOSS, MSSSIM_WEIGHTS, SSIM_LOSSES, add_yuv_args, add_yuv_loss_args, evaluate, load_frames, report_line, seed_all,
                                 yuv_loss_params)
 
 
@@ -73,10 +73,17 @@ def adjust_lr(optimizer, cur_epoch, args, eta_min=0.05):
 def loss_params(args, cfg):
     """cfg['loss'] -> None for 'l2', the keywords of ops.yuv420_loss for 'yuv420' (the weighted plane MSEs of the 8-bit YUV
     4:2:0 codes; --yuv_matrix, --yuv_range, --yuv_weights; evaluations then also report PSNR-Y / U / V), the keywords of
-    ops.ssim_loss for 'ssim' / 'Fusion1' / 'Fusion3' / 'Fusion5' (DESIGN.md §20); anything else raises."""
+    ops.ssim_loss for 'ssim' / 'Fusion1' / 'Fusion3' / 'Fusion5' (DESIGN.md §20), dict(w_mse, w_ms) of ops.ms_ssim_loss for
+    'msssim' (weights (0, 1), or the config's `loss_weights: [W_MSE, W_MS]`); anything else raises."""
     loss_name = cfg.get('loss', 'l2')
     if loss_name == 'l2':
         return None
+    if loss_name == MSSSIM_LOSS:
+        w = cfg.get('loss_weights', MSSSIM_WEIGHTS)
+        if not isinstance(w, (list, tuple)) or len(w) != 2:
+            raise ValueError(f'loss_weights takes [W_MSE, W_MS], got {w!r}')
+        w = ops.ms_ssim_loss_args('loss_weights', (1, 1, 161, 161), (1, 1, 161, 161), *w)   # finite, >= 0, a positive sum
+        return dict(w_mse=w[0], w_ms=w[1])
     if loss_name in SSIM_LOSSES:
         w_mse, w_ssim = SSIM_LOSSES[loss_name]
         return dict(w_mse=w_mse, w_ssim=w_ssim)
@@ -89,6 +96,8 @@ def loss_params(args, cfg):
 
 def step_loss(img_out, img, yuv=None):
     """the scalar one training step differentiates: per-channel mean of the loss (`yuv`: what loss_params returned)"""
+    if yuv is not None and 'w_ms' in yuv:
+        return ops.ms_ssim_loss(img_out, img, **yuv)
     if yuv is not None and 'w_ssim' in yuv:
         return ops.ssim_loss(img_out, img, **yuv)       # the reference's per-frame loss, then .mean(): nothing on top
     if yuv is not None:
@@ -110,8 +119,9 @@ def train(args, cfg):
     setup_logger(os.path.join(args.outf, time.strftime('%Y%m%d_%H%M%S') + '.log'))
     if args.weight != 'None':
         model.load_state_dict(torch.load(args.weight, map_location='cpu'), strict=False)
+    msssim = yuv if yuv is not None and 'w_ms' in yuv else None   # evaluations then log the objective's line
     if args.eval_only:
-        res, _ = evaluate(model, cache, args, cfg)
+        res, _ = evaluate(model, cache, args, cfg, msssim=msssim)
         logging.info(report_line('', args))
         return res
     optimizer = torch.optim.Adam(model.parameters(), weight_decay=0.)
@@ -134,7 +144,7 @@ def train(args, cfg):
                     datetime.now().strftime("%Y/%m/%d %H:%M:%S"), epoch + 1, cfg['epoch'], i + 1, len(loader), lr,
                     RoundTensor(torch.cat(psnrs).mean().cpu(), 2)))
         if (epoch + 1) % cfg.get('eval_freq', 30) == 0 or (cfg['epoch'] - epoch) in [1, 3, 5]:
-            res, _ = evaluate(model, cache, args, cfg)
+            res, _ = evaluate(model, cache, args, cfg, msssim=msssim)
             logging.info(f'Eval at epoch {epoch + 1}: pred_seen_psnr: {RoundTensor(res[0], 2)} | pred_seen_ssim: '
                          f'{RoundTensor(args.eval_metrics["pred_seen_ssim"], 4)}')
         torch.save(model.state_dict(), '{}/model_latest.pth'.format(args.outf))

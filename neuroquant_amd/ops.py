@@ -1965,6 +1965,119 @@ def ssim_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ss
     return loss3, head.dconv
 
 
+# ---- MSE + five-scale MS-SSIM (include/nq_hip.h: nq_msssim_loss) ----
+MSSSIM_LOSS_LAUNCHES = 11      # kernel launches of one nq_msssim_loss call with a gradient: 5 forward, 1 finish, 5 backward
+msssim_loss_head_launches = 0  # ops.msssim_loss_head_grad calls issued (or captured) by this process: the default paths issue none
+
+
+def ms_ssim_loss_args(what, pred_shape, tgt_shape, w_mse, w_ms):
+    """-> (w_mse, w_ms) as floats; ValueError naming `what` before anything is launched"""
+    if len(pred_shape) != 4 or min(pred_shape) <= 0 or min(pred_shape[2:]) <= 160:
+        raise ValueError(f"{what} takes (B, C, H, W) images whose smaller side exceeds (11 - 1) * 2**4 = 160, got "
+                         f"{tuple(pred_shape)}")
+    if tuple(tgt_shape) != tuple(pred_shape):
+        raise ValueError(f"{what}: pred {tuple(pred_shape)} and tgt {tuple(tgt_shape)} differ")
+    try:
+        w = (float(w_mse), float(w_ms))
+    except (TypeError, ValueError):
+        w = (-1.0, -1.0)
+    if not all(math.isfinite(v) and v >= 0.0 for v in w) or not sum(w) > 0.0:
+        raise ValueError(f"{what}: weights must be two finite numbers >= 0 with a positive sum, got {(w_mse, w_ms)!r}")
+    return w
+
+
+def _ms_ssim_loss_launch(what, pred, tgt, w_mse, w_ms, want_grad, grad_scale=1.0):
+    """-> (loss3, grad or None, ws): ws[:B] holds the per-frame MS-SSIM"""
+    if not isinstance(pred, torch.Tensor) or not isinstance(tgt, torch.Tensor):
+        raise ValueError(f"{what} takes two (B, C, H, W) tensors, got {type(pred)} and {type(tgt)}")
+    w = ms_ssim_loss_args(what, pred.shape, tgt.shape, w_mse, w_ms)
+    pred_d, tgt = _dev(pred.detach(), "pred"), _dev(tgt.detach(), "tgt")
+    B, C, H, W = pred_d.shape
+    loss3 = torch.empty(3, device=pred_d.device, dtype=torch.float32)
+    grad = torch.empty_like(pred_d) if want_grad else None
+    ws = torch.empty(_q("nq_msssim_loss_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
+    L.check(_timed("msssim_loss", lambda: L.lib().nq_msssim_loss(_p(pred_d), _p(tgt), _p(loss3), _p(grad), _p(ws), B, C, H, W,
+                                                                 w[0], w[1], float(grad_scale), _stream())), "msssim_loss")
+    return loss3, grad, ws
+
+
+def ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=True):
+    """One nq_msssim_loss call on images `pred`, `tgt` (B, C, H, W), min(H, W) > 160 -> (loss3, grad): loss3 = (L, mean MSE, mean
+    MS-SSIM) with L = mean_b [w_mse * MSE_b + w_ms * (1 - MS_b)], MS_b the five-scale MS-SSIM that ops.ms_ssim reports (the
+    definition of pytorch_msssim.ms_ssim(pred, tgt, data_range=1, size_average=False)); grad = dL/dpred, exact, or None with
+    want_grad=False (the forward launches alone: the same loss3 bits).  A (frame, channel) plane on which the relu of a scale
+    is active has M = 0 and, by this project's rule, no MS-SSIM gradient (autograd would give NaN).  Bit-identical from call
+    to call.  ValueError for a bad shape or bad weights before any launch."""
+    loss3, grad, _ = _ms_ssim_loss_launch("ms_ssim_loss", pred, tgt, w_mse, w_ms, want_grad)
+    return loss3, grad
+
+
+class _MsSsimLossFn(Function):
+    """L of ms_ssim_loss_raw as a scalar; backward is grad * g (as _SsimLossFn).  Where `pred` needs no gradient (torch.no_grad, a
+    detached image) the call is forward only: six launches, no derivative maps, the same loss bits."""
+
+    @staticmethod
+    def forward(ctx, pred, tgt, w_mse, w_ms):
+        loss3, grad = ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=ctx.needs_input_grad[0])
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return loss3[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None
+
+
+def ms_ssim_loss(pred, tgt, w_mse=0.0, w_ms=1.0):
+    """Differentiable L of ms_ssim_loss_raw (w.r.t. `pred`)."""
+    return _MsSsimLossFn.apply(pred, tgt, float(w_mse), float(w_ms))
+
+
+def msssim_loss_head_grad(img_out, tgt=None, cache_u8=None, idx=None, node=None, w_mse=0.0, w_ms=1.0):
+    """ssim_loss_head_grad for the MSE + MS-SSIM objective: -> (loss3, dimg) with loss3 = (C * L, mean MSE, mean MS-SSIM) (the
+    factor C puts weights (1, 0) on the scale of lp_loss(p = 2)) and `img_out.backward(dimg)` (or decoder_backward_steps(node,
+    dimg)) continuing the backward pass.  The target is `tgt` or the frames `cache_u8[idx] / 255`, gathered by
+    nq_gather_frames_u8.  With the hand-over slot of a tanh-headed decoder node, dimg is the gradient at the head conv's OUTPUT
+    (nq_tanh_out_backward of C * dL/dimg) and the head's bias gradient (nq_channel_sum of it) is handed over with it; otherwise
+    dimg = C * dL/dimg.  There is no fused head variant of this kernel.  Everything stays on the stream, nothing is read by the
+    host.  ValueError for a bad shape, target or weights before any launch."""
+    global msssim_loss_head_launches
+    if not isinstance(img_out, torch.Tensor):
+        raise ValueError(f"msssim_loss_head_grad takes (B, C, H, W) images, got {type(img_out)}")
+    if (tgt is None) == (cache_u8 is None):
+        raise ValueError("msssim_loss_head_grad takes exactly one of tgt and cache_u8 + idx")
+    if cache_u8 is not None:
+        if not isinstance(cache_u8, torch.Tensor) or cache_u8.dtype != torch.uint8 or cache_u8.dim() != 4 \
+                or not isinstance(idx, torch.Tensor) or idx.dim() != 1:
+            raise ValueError("msssim_loss_head_grad: the frame cache must be a uint8 (N, C, H, W) tensor with a 1-d idx")
+        tgt_shape = (idx.numel(),) + tuple(cache_u8.shape[1:])
+    else:
+        if not isinstance(tgt, torch.Tensor):
+            raise ValueError(f"msssim_loss_head_grad takes a (B, C, H, W) target, got {type(tgt)}")
+        tgt_shape = tgt.shape
+    w = ms_ssim_loss_args("msssim_loss_head_grad", img_out.shape, tgt_shape, w_mse, w_ms)
+    if not img_out.is_cuda:
+        raise RuntimeError("neuroquant_amd: msssim_loss_head_grad needs GPU tensors")
+    if cache_u8 is not None:
+        tgt = gather_frames_u8(cache_u8, idx)
+    C = img_out.shape[1]
+    msssim_loss_head_launches += 1
+    loss3, g, _ = _ms_ssim_loss_launch("msssim_loss_head_grad", img_out, tgt, w[0], w[1], True, grad_scale=float(C))
+    loss3[:1].mul_(float(C))       # the float L times C, one more rounding, on the stream
+    head = getattr(node if node is not None else getattr(img_out, "grad_fn", None), "nq_head", None)
+    if not isinstance(head, _HeadHandoff) or os.environ.get("NQ_FUSED_LOSS", "1") == "0":
+        return loss3, g
+    # (a result of ops.fused_head_loss that nobody asked for is dropped: this objective replaces it)
+    head.loss = None
+    img_d = _dev(img_out.detach(), "img_out")
+    head.dconv = torch.empty_like(g)
+    L.check(L.lib().nq_tanh_out_backward(_p(g), _p(img_d), _p(head.dconv), g.numel(), _stream()), "tanh_backward")
+    head.db = channel_sum(head.dconv)
+    head.version = head.dconv._version
+    return loss3, head.dconv
+
+
 def ssim(out, gt):
     """per-frame single-scale SSIM of (F, C, H, W) images -> (F,) fp32 (pytorch_msssim.ssim(out, gt, data_range=1,
     size_average=False)); a frame's value depends on that frame's bytes only.  Forward only (inputs are detached)."""

@@ -48,10 +48,11 @@ class LossFunction:
 
     def __init__(self, model: nn.Module, round_loss: str = 'relaxation', weight: float = 1., rec_loss: str = 'mse',
                  max_count: int = 2000, b_range: tuple = (10, 2), decay_start: float = 0.0, warmup: float = 0.0,
-                 p: float = 2., yuv: dict = None, ssim: dict = None):
+                 p: float = 2., yuv: dict = None, ssim: dict = None, msssim: dict = None):
         self.model = model
         self.yuv = dict(yuv or {})   # rec_loss 'yuv420': matrix, full_range, weights of ops.yuv420_loss
         self.ssim = dict(ssim or {})   # rec_loss 'ssim': w_mse, w_ssim of ops.ssim_loss
+        self.msssim = dict(msssim or {})   # rec_loss 'msssim': w_mse, w_ms of ops.ms_ssim_loss
         self.round = round_loss
         self.weight = weight
         self.rec = rec_loss
@@ -72,6 +73,8 @@ class LossFunction:
             rec_loss = ops.yuv420_loss(pred, tgt, **self.yuv)
         elif self.rec == 'ssim':   # on the scale of lp_loss, as model_reconstruction(ssim=...) logs it
             rec_loss = ops.ssim_loss(pred, tgt, **self.ssim) * pred.shape[1]
+        elif self.rec == 'msssim':   # on the scale of lp_loss, as model_reconstruction(msssim=...) logs it
+            rec_loss = ops.ms_ssim_loss(pred, tgt, **self.msssim) * pred.shape[1]
         elif self.rec == 'mse':
             rec_loss = lp_loss(pred, tgt, p=self.p)
         else:
@@ -179,7 +182,7 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                          iters: int = 20000, weight: float = 0.01, opt_mode: str = 'mse', hadamard: bool = True,
                          b_range: tuple = (20, 2), warmup: float = 0.0, p: float = 2.0, lr: float = 0.0015,
                          recorder: list = None, max_steps: int = None, step_hook=None, probe=None,
-                         loss_domain: str = 'rgb', yuv: dict = None, ssim: dict = None):
+                         loss_domain: str = 'rgb', yuv: dict = None, ssim: dict = None, msssim: dict = None):
     """Network-wise calibration, in place (reference calib_model.py:92-240).
 
     gt: any sized iterable of dict batches {'img' (B,3,H,W), 'idx' (B,), 'norm_idx'}; cali_data[idx] feeds the
@@ -192,7 +195,10 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
     DESIGN.md §19) with yuv = dict(matrix, full_range, weights) (bt709, limited range, 6:1:1 where absent); the logged `rec` is
     that loss.  ssim = dict(w_mse, w_ssim) replaces lp_loss by C * mean_b[w_mse MSE_b + w_ssim (1 - SSIM_b)], the reference's
     ssim / Fusion losses on the scale of lp_loss (ops.ssim_loss_head_grad; weights (1, 0) are lp_loss); the
-    logged `rec` is that loss; it does not combine with loss_domain 'yuv420'.  Everything else of the iteration is the same.
+    logged `rec` is that loss; it does not combine with loss_domain 'yuv420'.  msssim = dict(w_mse, w_ms) replaces lp_loss by
+    C * mean_b[w_mse MSE_b + w_ms (1 - MS_b)] with the five-scale MS-SSIM (ops.msssim_loss_head_grad; frames
+    whose smaller side exceeds 160); it combines neither with ssim nor with loss_domain 'yuv420'.  Everything else of the
+    iteration is the same.
     """
     if arch not in ('hnerv', 'nerv'):
         raise ValueError
@@ -213,6 +219,15 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
             raise ValueError("the SSIM objective is defined on RGB frames: it does not combine with loss_domain 'yuv420'")
         ssim = dict(zip(('w_mse', 'w_ssim'), ops.ssim_loss_args('model_reconstruction', (1, 1, 11, 11), (1, 1, 11, 11),
                                                                 ssim['w_mse'], ssim['w_ssim'])))
+    if msssim is not None:   # the same for the MS-SSIM objective
+        if not isinstance(msssim, dict) or set(msssim) != {'w_mse', 'w_ms'}:
+            raise ValueError(f"msssim takes dict(w_mse, w_ms), got {sorted(msssim) if isinstance(msssim, dict) else msssim!r}")
+        if ssim is not None:
+            raise ValueError("msssim and ssim are two objectives: give one")
+        if loss_domain == 'yuv420':
+            raise ValueError("the MS-SSIM objective is defined on RGB frames: it does not combine with loss_domain 'yuv420'")
+        msssim = dict(zip(('w_mse', 'w_ms'), ops.ms_ssim_loss_args('model_reconstruction', (1, 1, 161, 161), (1, 1, 161, 161),
+                                                                   msssim['w_mse'], msssim['w_ms'])))
     model.set_quant_state(True)
     device = next(model.parameters()).device
     layers = [_Layer(m, hadamard) for m in _quant_modules(model)]
@@ -367,7 +382,7 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
             node = None
             # (the loss tail runs behind the head convolution when the decoder is the fused stack: ops.fused_head_loss)
             # (... for lp_loss only: the YUV and the SSIM objective have their own launch behind the head)
-            if loss_domain == 'yuv420' or ssim is not None:
+            if loss_domain == 'yuv420' or ssim is not None or msssim is not None:
                 loss_req = contextlib.nullcontext()
             else:
                 loss_req = ops.fused_head_loss(cache_u8=img[0], idx=img[1]) if isinstance(img, tuple) else ops.fused_head_loss(tgt=img)
@@ -390,6 +405,11 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                 # MSE + SSIM instead: same hand-over, same targets
                 loss3, dimg = ops.ssim_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **ssim) \
                     if isinstance(img, tuple) else ops.ssim_loss_head_grad(img_out, tgt=img, node=node, **ssim)
+                fused = (loss3[0], dimg)
+            elif msssim is not None:
+                # MSE + MS-SSIM instead: same hand-over, same targets
+                loss3, dimg = ops.msssim_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **msssim) \
+                    if isinstance(img, tuple) else ops.msssim_loss_head_grad(img_out, tgt=img, node=node, **msssim)
                 fused = (loss3[0], dimg)
             else:
                 fused = ops.l2_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node) if isinstance(img, tuple) \
