@@ -756,6 +756,57 @@ NQ_API int64_t nq_bit_search_ws_bytes(int L, int K);
 NQ_API int nq_bit_search(const double* G, const uint64_t* size_bits, int L, int K, uint64_t budget_bits, double* best_omega,
                   uint64_t* best_index, void* ws, nq_stream_t stream);
 
+/* ---- rate-aware calibration: the entropy cost of the stored levels (additive: nq_abi_version() stays 7) ----
+ * THE definition.  For a weight tensor with n = rows * row_len elements, K = n_levels (4 .. 256), per-row or scalar delta / zp,
+ * everything per element in fp32 and uncontracted unless stated:
+ *   f_i    = floor(x_i / delta)                              the float expression of nq_adaround_forward
+ *   lo_i   = clamp((f_i + 0) + zp, 0, K - 1),  hi_i = clamp((f_i + 1) + zp, 0, K - 1)
+ *   l_i    = alpha_i >= 0 ? hi_i : lo_i                      the hard level: bit for bit the xq nq_adaround_forward(soft = 0) writes
+ *   c_k    = #{i : l_i = k}                                  int32
+ *   cost_k = log2((n + K) / (c_k + 1)) bits                  evaluated in double, rounded once to float (Laplace smoothing: an
+ *                                                            unused level has a finite price)
+ *   s = sigmoid(alpha_i), lin = 1.2 s - 0.1, h_i = clamp(lin, 0, 1), h'_i = (0 <= lin <= 1) ? 1.2 (s (1 - s)) : 0
+ *                                                            the expressions of nq_adaround_backward
+ *   R_soft = sum_i (1 - h_i) cost[lo_i] + h_i cost[hi_i]     bits
+ *   R_hard = sum_k c_k cost_k                                bits, cost_k the float table entry, summed in double for k ascending,
+ *                                                            rounded once to float; R_soft equals it when every h_i is 0 or 1
+ *   d(alpha)_i += ((gate * scale) * (cost[hi_i] - cost[lo_i])) * h'_i        the table is a constant of the derivative
+ * gate = dyn[1], the regulariser gate of nq_step_prologue's slots, read on the device, or 1 when dyn == NULL; callers pass
+ * scale = lambda / P with P the pixels of the clip (frames * H * W), which makes the term lambda * bpp.  gate * scale == 0 stores
+ * nothing to dalpha (it stays bit for bit what it was).  Only weight quantisers take part, as for the rounding regulariser; in a
+ * Hadamard model x / alpha are the padded transform-domain tensors: what the file stores.
+ *
+ * nq_level_rate: `segs` is a host array, the pointers inside are device pointers; lists longer than 16 tensors are chunked
+ * (seg_table.h).  Per chunk FOUR launches: (1) a histogram -- each workgroup counts the levels of its 4096 elements in LDS with
+ * integer LDS adds (8 padded copies of the table per wave, so that a dominating level costs an 8-way, not a 64-way, serialised
+ * add) and writes K partial counts to ws; (2) a finish -- one workgroup per tensor adds the partial counts in workgroup order and
+ * writes counts, cost and rate[1] = R_hard; (3) the rate pass -- one pass over x, alpha, delta, zp that adds the gradient into
+ * dalpha (skipped when dalpha == NULL) and writes one partial sum of R_soft per workgroup to ws; (4) a sum -- one workgroup adds
+ * each tensor's partials in a fixed order in double, writes rate[0] = R_soft and continues total[0] / total[1] = the float sums
+ * of R_soft / R_hard over the tensors in list order ((0 + r_0) + r_1 ...).  No global atomics, no float atomics, no host read
+ * between launches, no launch argument that depends on device data: bit-identical from call to call, capturable in a hipGraph.
+ *   ws: the sum over the call's tensors of nq_level_rate_ws_words(rows * row_len, n_levels) 4-byte words, 16-byte aligned;
+ *       nq_level_rate_ws_words(n, K) = ceil(n / 4096) * (K + 1), 0 for n <= 0 or K outside 4 .. 256 or a product past int64.
+ *       ws_words is what the caller allocated: less than the call needs is NQ_ERR_INVALID.
+ * NQ_ERR_INVALID, before the device is touched and whatever the position of the tensor in the list, for null pointers (dalpha and
+ * dyn may be NULL), non-positive sizes, a row past 2^31 - 1 elements, n_levels outside 4 .. 256, a negative or non-finite scale
+ * and an element count or workspace past int64. */
+typedef struct nq_rate_seg {
+  const float* x;      /* weights (rows x row_len) */
+  const float* alpha;
+  const float* delta;  /* (rows) when per_row, else (1) */
+  const float* zp;
+  float* dalpha;       /* d(alpha) to add the gradient to, or NULL */
+  int32_t* counts;     /* out: n_levels */
+  float* cost;         /* out: n_levels */
+  float* rate;         /* out: {R_soft, R_hard} */
+  int64_t rows, row_len;
+  int per_row, n_levels;
+} nq_rate_seg;
+NQ_API int64_t nq_level_rate_ws_words(int64_t n, int n_levels);
+NQ_API int nq_level_rate(const nq_rate_seg* segs, int nseg, float scale, const float* dyn, float* total, void* ws, int64_t ws_words,
+                  nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,13 @@ class AdamSeg(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64)]
 
 
+class RateSeg(Structure):
+    """nq_rate_seg (include/nq_hip.h): one weight tensor of a level-rate call."""
+    _fields_ = [("x", c_void_p), ("alpha", c_void_p), ("delta", c_void_p), ("zp", c_void_p), ("dalpha", c_void_p),
+                ("counts", c_void_p), ("cost", c_void_p), ("rate", c_void_p), ("rows", c_int64), ("row_len", c_int64),
+                ("per_row", c_int), ("n_levels", c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise NQLibraryError(
@@ -203,6 +210,8 @@ def _load():
     sig("nq_rows_dot", I, P, P, P, I, L, P, P)
     sig("nq_bit_search_ws_bytes", L, I, I)
     sig("nq_bit_search", I, P, P, I, I, ctypes.c_uint64, P, P, P, P)
+    sig("nq_level_rate_ws_words", L, L, I)
+    sig("nq_level_rate", I, POINTER(RateSeg), I, F, P, P, P, L, P)
     return lib
 
 
@@ -228,6 +237,7 @@ EXPORTS = (
     "nq_conv3_levels_supported", "nq_conv_forward3_levels",
     "nq_weight_layout3_f16", "nq_conv_forward3_levels_f16",
     "nq_conv_forward_plan", "nq_conv_wgrad_plan",
+    "nq_level_rate_ws_words", "nq_level_rate",
 )
 
 _lib = None

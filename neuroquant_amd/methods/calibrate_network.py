@@ -22,7 +22,10 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
     packed at their bit-width and entropy-coded levels; --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
-    and evaluates on the embeddings a player restores, and stores them as levels: DESIGN.md §17)
+    and evaluates on the embeddings a player restores, and stores them as levels: DESIGN.md §17;
+    --rate_lambda L (default 0: off) adds L * bits per pixel of the weight levels, priced by a static per-tensor model of the
+    hard levels, to the phase-2 objective (ops.level_rate; the pixels are those of the frame cache), logs 'rate: ..' lines and,
+    with --export_stream, the model's bytes beside the coded ones: DESIGN.md §23)
 """
 import argparse
 import logging
@@ -84,7 +87,11 @@ def parse_args(argv):
     p.add_argument('--embed_bits', type=int, default=None, choices=range(2, 9), metavar='2..8',
                    help='HNeRV: quantise the frame embeddings to this many bits (one scale per embedding channel); the calibration, '
                         'every evaluation after the FP one and --export_stream use the embeddings a player restores from the levels')
+    p.add_argument('--rate_lambda', type=float, default=0.0,
+                   help='weight of the rate term of phase 2: lambda * bits per pixel of the weight levels under a static '
+                        'per-tensor model of the hard levels (DESIGN.md §23); 0 = off')
     args = p.parse_args(argv)
+    rate_params(args, 1)   # a negative or non-finite --rate_lambda stops here
     if args.precision_file is not None:
         args.precision = read_precision_file(args.precision_file)
     elif args.precision is None:
@@ -207,6 +214,26 @@ def rec_msssim_params(args):
     if getattr(args, 'loss_domain', 'rgb') == 'yuv420':
         raise ValueError('the MSE + MS-SSIM objective is defined on RGB frames: it does not combine with --loss_domain yuv420')
     return dict(w_mse=float(w[0]), w_ms=float(w[1]))
+
+
+def rate_params(args, pixels):
+    """-> None for --rate_lambda 0 (off), else dict(weight, pixels) of model_reconstruction(rate=...); pixels = frames * H * W of
+    the frame cache.  ValueError for a negative or non-finite weight."""
+    lam = ops.level_rate_args('--rate_lambda', getattr(args, 'rate_lambda', 0.0) or 0.0)
+    return dict(weight=lam, pixels=int(pixels)) if lam > 0.0 else None
+
+
+@torch.no_grad()
+def hard_level_rate(qnn, hadamard):
+    """R_hard of the calibrated weight quantisers in bits (ops.level_rate_raw: the stored levels priced by the static model the
+    rate term optimises), summed over the layers; one host read."""
+    from ..quantization.calib_model import _quant_modules
+    items = []
+    for m in _quant_modules(qnn):
+        wq = m.weight_quantizer
+        items.append(((m.hadamard_weight if hadamard else m.org_weight).data, wq.alpha.data, wq.delta.data, wq.zero_point,
+                      wq.n_levels))
+    return float(ops.level_rate_raw(items, 0.0).total[1])
 
 
 def yuv_loss_params(args):
@@ -434,13 +461,16 @@ def calibrate(args, cfg):
     ms_obj = rec_msssim_params(args)
     if ms_obj is not None:
         logging.info('reconstruction loss: C * (w_mse * MSE + w_ms * (1 - MS-SSIM)), {}'.format(ms_obj))
+    rate_obj = rate_params(args, n * cache.frames.shape[-2] * cache.frames.shape[-1])
+    if rate_obj is not None:
+        logging.info('rate term: lambda * bits per pixel of the weight levels, {}'.format(rate_obj))
     start = datetime.now()
     qnn.set_quant_state(weight_quant=True)
     model_reconstruction(qnn, cali_data=cali_data, gt=train_loader, arch=args.arch, batch_size=args.batch_size,
                          iters=args.iters_w, weight=args.weight, opt_mode='mse', hadamard=args.hadamard,
                          b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr,
                          loss_domain=loss_domain, yuv=yuv_loss_params(args) if loss_domain == 'yuv420' else None,
-                         ssim=ssim_obj, msssim=ms_obj)
+                         ssim=ssim_obj, msssim=ms_obj, **(dict(rate=rate_obj) if rate_obj is not None else {}))
     torch.cuda.synchronize()
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
 
@@ -459,6 +489,11 @@ def calibrate(args, cfg):
                          'gap to entropy {} bytes)'.format(
                              args.export_stream, s['file_bytes'], round(s.get('bpp', float('nan')), 5), s['total_bytes_nominal'],
                              s['coding'], s['coded_level_bytes'], s['gap_to_entropy_bytes']))
+            if rate_obj is not None:
+                args.rate_hard_bytes = hard_level_rate(qnn, args.hadamard) / 8
+                logging.info('rate model: R_hard / 8 = {} bytes of weight levels (bit stream: coded levels {} bytes, entropy {} '
+                             'bytes, biases included)'.format(round(args.rate_hard_bytes, 1), s['coded_level_bytes'],
+                                                              s['entropy_level_bytes']))
             if 'embedding' in s:
                 e = s['embedding']
                 logging.info('bit stream embeddings: {} bits, stored {} ({} bytes; packed / rans / temporal: {})'.format(

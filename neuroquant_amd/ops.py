@@ -4,6 +4,7 @@ PyTorch is plumbing here: device memory, the current HIP stream and the autograd
 the hot path runs in the hand-written gfx950 kernels; there is NO CPU / eager fallback -- every op raises if
 its tensors are not fp32 HIP tensors or if libnqhip.so is missing.
 """
+import collections
 import contextlib
 import ctypes
 import functools
@@ -317,6 +318,89 @@ class FusedAdam:
         bc1, bc2 = 1 - beta1 ** self.t, 1 - beta2 ** self.t
         L.check(L.lib().nq_adam_step_multi(segs, len(todo), self.lr / bc1, beta1, beta2, eps, bc2 ** 0.5, _stream()),
                 "adam_step_multi")
+
+
+# ---- rate-aware calibration: the entropy cost of the stored levels (include/nq_hip.h: nq_level_rate) ----
+LEVEL_RATE_LAUNCHES = 4        # kernel launches of one nq_level_rate call per 16 tensors: histogram, finish, rate pass, sum
+level_rate_launches = 0        # ops.level_rate_raw calls issued (or captured) by this process: the default paths issue none
+LevelRate = collections.namedtuple("LevelRate", "counts cost rate total")
+
+
+def level_rate_args(what, scale, n_levels=()):
+    """ValueError unless scale is a finite number >= 0 and every n_levels lies in 4 .. 256 -> float(scale)."""
+    try:
+        s = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: scale must be a number, got {scale!r}")
+    if not math.isfinite(s) or s < 0.0:
+        raise ValueError(f"{what}: scale must be finite and >= 0, got {scale!r}")
+    for k in n_levels:
+        if not isinstance(k, int) or not 4 <= k <= 256:
+            raise ValueError(f"{what}: n_levels must be an int in 4 .. 256, got {k!r}")
+    return s
+
+
+def level_rate_raw(items, scale, dyn=None, dalphas=None):
+    """items: [(x, alpha, delta, zp, n_levels)], the weight tensors of a decoder with their rounding variables -> LevelRate(counts
+    [int32 (n_levels,)], cost [float (n_levels,)], rate (tensors, 2) = {R_soft, R_hard} bits per tensor, total (2,) = their sums
+    in list order), all on the device, nothing read by the host (nq_level_rate; the definition is in include/nq_hip.h).  dalphas
+    (a list of contiguous float tensors shaped like the alphas, entries may be None) receive += gate * scale * (cost[hi] -
+    cost[lo]) * h' in place; dyn (the device slots of the current step) supplies the gate, else 1.  Four launches per 16
+    tensors.  ValueError for a bad scale, level count or list before any launch; RuntimeError for CPU tensors."""
+    global level_rate_launches
+    items = list(items)
+    if not items:
+        raise ValueError("level_rate: no tensors")
+    if any(len(it) != 5 for it in items):
+        raise ValueError("level_rate: items are (x, alpha, delta, zp, n_levels)")
+    scale = level_rate_args("level_rate", scale, [it[4] for it in items])
+    if dalphas is not None and len(dalphas) != len(items):
+        raise ValueError(f"level_rate: {len(dalphas)} d(alpha) tensors for {len(items)} items")
+    segs = (L.RateSeg * len(items))()
+    keep, words, ks = [], 0, []
+    for i, (sg, (x, alpha, delta, zp, n_levels)) in enumerate(zip(segs, items)):
+        x, alpha, delta, zp = _dev(x, "x"), _dev(alpha, "alpha"), _dev(delta, "delta"), _dev(zp, "zp")
+        if alpha.numel() != x.numel():
+            raise ValueError("level_rate: alpha must have the shape of x")
+        da = None if dalphas is None else dalphas[i]
+        if da is not None:
+            _dev(da, "d(alpha)")
+            if not da.is_contiguous() or da.numel() != x.numel():
+                raise ValueError("level_rate: d(alpha) must be contiguous and shaped like alpha (it is updated in place)")
+        sg.rows, sg.row_len, sg.per_row = _rows(x, delta)
+        sg.n_levels = n_levels
+        if zp.numel() != delta.numel():
+            raise ValueError("level_rate: delta and zero_point must have the same size")
+        keep.append((x, alpha, delta, zp, da))
+        ks.append(n_levels)
+        words += _q("nq_level_rate_ws_words", x.numel(), n_levels)
+    dev = keep[0][0].device
+    if dyn is not None:
+        dyn = _dev(dyn, "dyn")
+        if dyn.numel() < 2:
+            raise ValueError("level_rate: dyn holds {reg_b, gate, ...}")
+    counts = torch.empty(sum(ks), device=dev, dtype=torch.int32)
+    cost = torch.empty(sum(ks), device=dev, dtype=torch.float32)
+    rate = torch.empty((len(items), 2), device=dev, dtype=torch.float32)
+    total = torch.empty(2, device=dev, dtype=torch.float32)
+    ws = torch.empty(words, device=dev, dtype=torch.int32)
+    counts_l, cost_l = list(counts.split(ks)), list(cost.split(ks))
+    for i, (sg, (x, alpha, delta, zp, da)) in enumerate(zip(segs, keep)):
+        sg.x, sg.alpha, sg.delta, sg.zp, sg.dalpha = _p(x), _p(alpha), _p(delta), _p(zp), _p(da)
+        sg.counts, sg.cost, sg.rate = _p(counts_l[i]), _p(cost_l[i]), _p(rate[i])
+    level_rate_launches += 1
+    _timed("level_rate", lambda: L.check(L.lib().nq_level_rate(segs, len(items), scale, _p(dyn), _p(total), _p(ws), words, _stream()),
+                                         "level_rate"))
+    return LevelRate(counts_l, cost_l, rate, total)
+
+
+def level_rate(items, weight, pixels, dyn=None, dalphas=None):
+    """The rate term of a calibration iteration: level_rate_raw with scale = weight / pixels (lambda * bits per pixel of the
+    clip: pixels = frames * H * W), the gradient added to dalphas in place."""
+    if not isinstance(pixels, int) or pixels <= 0:
+        raise ValueError(f"level_rate: pixels must be a positive int, got {pixels!r}")
+    weight = level_rate_args("level_rate", weight)
+    return level_rate_raw(items, weight / pixels, dyn=dyn, dalphas=dalphas)
 
 
 class _UAQFn(Function):

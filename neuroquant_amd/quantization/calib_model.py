@@ -182,7 +182,8 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                          iters: int = 20000, weight: float = 0.01, opt_mode: str = 'mse', hadamard: bool = True,
                          b_range: tuple = (20, 2), warmup: float = 0.0, p: float = 2.0, lr: float = 0.0015,
                          recorder: list = None, max_steps: int = None, step_hook=None, probe=None,
-                         loss_domain: str = 'rgb', yuv: dict = None, ssim: dict = None, msssim: dict = None):
+                         loss_domain: str = 'rgb', yuv: dict = None, ssim: dict = None, msssim: dict = None,
+                         rate: dict = None):
     """Network-wise calibration, in place (reference calib_model.py:92-240).
 
     gt: any sized iterable of dict batches {'img' (B,3,H,W), 'idx' (B,), 'norm_idx'}; cali_data[idx] feeds the
@@ -199,6 +200,13 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
     C * mean_b[w_mse MSE_b + w_ms (1 - MS_b)] with the five-scale MS-SSIM (ops.msssim_loss_head_grad; frames
     whose smaller side exceeds 160); it combines neither with ssim nor with loss_domain 'yuv420'.  Everything else of the
     iteration is the same.
+    rate = dict(weight=lambda, pixels=P) adds lambda * R_soft / P to the phase-2 objective: the entropy cost, under a static
+    per-tensor model, of the levels the weight quantisers would store (ops.level_rate; P = frames * H * W of the
+    clip, so the term is lambda * bits per pixel).  Phase 2 then takes the unfused parameter side (d(alpha), the rate kernels
+    adding into the weight tensors' d(alpha), Adam), which is bit-identical to the fused one: weight 0 gives the alphas of
+    rate=None, and rate=None launches nothing new.  The term is gated like the regulariser (off during the warm-up), is local to
+    a rank (not reduced: replicas stay identical) and combines with every objective above.  A second log line follows the
+    'Total loss' line: 'rate: lambda*bpp .., soft .. bits, hard .. bytes'.
     """
     if arch not in ('hnerv', 'nerv'):
         raise ValueError
@@ -228,6 +236,13 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
             raise ValueError("the MS-SSIM objective is defined on RGB frames: it does not combine with loss_domain 'yuv420'")
         msssim = dict(zip(('w_mse', 'w_ms'), ops.ms_ssim_loss_args('model_reconstruction', (1, 1, 161, 161), (1, 1, 161, 161),
                                                                    msssim['w_mse'], msssim['w_ms'])))
+    if rate is not None:   # bad keys, a bad weight and bad pixels stop here, before the first iteration
+        if not isinstance(rate, dict) or set(rate) != {'weight', 'pixels'}:
+            raise ValueError(f"rate takes dict(weight, pixels), got {sorted(rate) if isinstance(rate, dict) else rate!r}")
+        px = rate['pixels']
+        if isinstance(px, bool) or not isinstance(px, int) or px <= 0:
+            raise ValueError(f"rate: pixels must be a positive int (frames * H * W), got {px!r}")
+        rate = dict(weight=ops.level_rate_args('model_reconstruction(rate=)', rate['weight']), pixels=px)
     model.set_quant_state(True)
     device = next(model.parameters()).device
     layers = [_Layer(m, hadamard) for m in _quant_modules(model)]
@@ -450,7 +465,7 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                     logging.info('Total loss:\t{:.4f} (rec:{:.4f}, round:{:.4f})\tb={:.2f}\tcount={}'.format(
                         total, float(rec), rl_f, b, count))
             grads = []
-            if ada and fuse_had and probe is None and os.environ.get("NQ_FUSED_ADAM", "1") != "0":
+            if ada and fuse_had and probe is None and rate is None and os.environ.get("NQ_FUSED_ADAM", "1") != "0":
                 # H on the zero-padded gradients + d(alpha) + regulariser gradient + Adam of all layers in ONE launch: the
                 # transform-domain gradient never goes to memory
                 items = []
@@ -472,12 +487,22 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                     items.append((L.src, gW, wq.alpha.data, wq.delta.data, wq.zero_point, wq.n_levels,
                                   weight if (reg_on or dyn is not None) else 0.0))
                     items.append((L.bias, gb, bq.alpha.data, bq.delta.data, bq.zero_point, bq.n_levels, 0.0))
-                if probe is None and os.environ.get("NQ_FUSED_ADAM", "1") != "0":
+                if probe is None and rate is None and os.environ.get("NQ_FUSED_ADAM", "1") != "0":
                     # nobody looks at d(alpha): backward of the fake-quant + regulariser gradient + Adam in ONE pass
                     ops.adaround_adam_multi(items, opt, b, dyn=dyn)
                     grads = None
                 else:
                     grads = ops.adaround_backward_multi(items, b, dyn=dyn)
+                    if rate is not None:
+                        # + lambda / P * dR_soft/dalpha on the weight tensors (the even entries), gated like the regulariser:
+                        # on the device by dyn[1], else by passing a zero weight during the warm-up
+                        lr_ = ops.level_rate([(it[0], it[2], it[3], it[4], it[5]) for it in items[0::2]],
+                                             rate['weight'] if (reg_on or dyn is not None) else 0.0, rate['pixels'], dyn=dyn,
+                                             dalphas=grads[0::2])
+                        if want_log and count % 500 == 0:
+                            soft, hard = (float(v) for v in lr_.total)
+                            logging.info('rate: lambda*bpp {:.6f}, soft {:.1f} bits, hard {:.1f} bytes'.format(
+                                rate['weight'] * soft / rate['pixels'], soft, hard / 8))
             else:   # d(delta) of all 14 tensors in one launch
                 gWs = ops.fwht_channels_multi([(L.W.grad, L.n, L.n) for L in layers]) if hadamard else None
                 items = []
