@@ -12,13 +12,11 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     (--precision_file bits.json takes the bit-widths from `bit_assign --budget_bytes N --out bits.json`;
     --synthetic N uses N synthetic Bunny-shaped frames instead of --data_path; --data_path clip.y4m / clip.yuv reads an 8-bit
     YUV 4:2:0 clip instead of a directory of PNGs (--yuv_size, --yuv_matrix, --yuv_range, --yuv_frames; DESIGN.md §16);
-    --loss_domain yuv420 calibrates on the weighted plane MSEs of the 8-bit YUV 4:2:0 codes instead of RGB squared error
-    (--yuv_weights WY WU WV, default 6 1 1; matrix and range from --yuv_matrix / --yuv_range) and every evaluation also logs
-    PSNR-Y / U / V and their 6:1:1 mean: DESIGN.md §19;
-    --rec_loss ssim | Fusion1 | Fusion3 | Fusion5 calibrates on the reference's MSE + (1 - SSIM) losses instead of squared error
-    (--rec_weights W_MSE W_SSIM: free weights) and every evaluation also logs the mean single-scale SSIM: DESIGN.md §21;
-    --rec_loss msssim calibrates on 1 - MS-SSIM, the five-scale figure every evaluation logs (--rec_ms_weights W_MSE W_MS: free
-    weights of MSE and 1 - MS-SSIM; frames whose smaller side exceeds 160): DESIGN.md §22;
+    the reconstruction objective is one entry of objective.TABLE (objective_of), squared error unless asked:
+    --loss_domain yuv420 (--yuv_weights WY WU WV, default 6 1 1; matrix and range from --yuv_matrix / --yuv_range: §19),
+    --rec_loss ssim | Fusion1 | Fusion3 | Fusion5 or --rec_weights W_MSE W_SSIM (the reference's MSE + (1 - SSIM) losses: §21),
+    --rec_loss msssim or --rec_ms_weights W_MSE W_MS (1 - MS-SSIM; frames whose smaller side exceeds 160: §22); every evaluation
+    then also logs the figure that objective is after;
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
     packed at their bit-width and entropy-coded levels; --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
@@ -41,7 +39,8 @@ import torch
 from ..models import HNeRV, NeRV
 from ..quantization import QuantModel, model_reconstruction
 from ..utils import (CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger, synthetic_frames)
-from .. import ops
+from .. import objective, ops
+from ..objective import SSIM_METRIC_NAME, YUV_METRIC_NAMES   # added to the metrics by the SSIM / the YUV 4:2:0 objective
 
 
 def parse_args(argv):
@@ -176,44 +175,46 @@ def add_rec_loss_args(p):
                    help='free weights of the MSE + MS-SSIM reconstruction loss w_mse * MSE + w_ms * (1 - MS-SSIM)')
 
 
-def rec_loss_params(args):
-    """-> None for the squared error (--rec_loss l2, no --rec_weights), else dict(w_mse, w_ssim) of ops.ssim_loss_head_grad /
-    model_reconstruction(ssim=...).  ValueError for an unknown name, both flags, bad weights and --loss_domain yuv420."""
-    name, w = getattr(args, 'rec_loss', None) or 'l2', getattr(args, 'rec_weights', None)
-    if w is not None:
-        if name != 'l2':
-            raise ValueError('--rec_loss and --rec_weights exclude each other')
-        if len(w) != 2:
-            raise ValueError(f'--rec_weights takes W_MSE W_SSIM, got {w!r}')
-        w = ops.ssim_loss_args('--rec_weights', (1, 1, 11, 11), (1, 1, 11, 11), *w)   # finite, >= 0, a positive sum
-    elif name in ('l2', MSSSIM_LOSS):   # the MS-SSIM objective has a function of its own: rec_msssim_params
-        return None
+def objective_of(args):
+    """The reconstruction objective the flags ask for (objective.Objective): --loss_domain yuv420 with the yuv_*
+    flags, --rec_loss ssim / Fusion* or --rec_weights, --rec_loss msssim or --rec_ms_weights, else the squared error.  ValueError for
+    an unknown name, flags that exclude each other, bad weights and --loss_domain yuv420 beside an objective defined on RGB frames."""
+    name = getattr(args, 'rec_loss', None) or 'l2'
+    free = [(flag, obj) for flag, obj in (('rec_weights', 'ssim'), ('rec_ms_weights', MSSSIM_LOSS)) if getattr(args, flag, None) is not None]
+    if len(free) + (name != 'l2') > 1:
+        raise ValueError('--rec_loss, --rec_weights and --rec_ms_weights exclude each other')
+    if free:
+        (flag, name), w = free[0], getattr(args, free[0][0])
     elif name in SSIM_LOSSES:
-        w = SSIM_LOSSES[name]
-    else:
+        flag, name, w = 'rec_loss', 'ssim', SSIM_LOSSES[name]
+    elif name == MSSSIM_LOSS:
+        flag, w = 'rec_loss', MSSSIM_WEIGHTS
+    elif name != 'l2':
         raise ValueError(f"rec_loss must be one of {['l2'] + list(SSIM_LOSSES)}, got {name!r}")
-    if getattr(args, 'loss_domain', 'rgb') == 'yuv420':
-        raise ValueError('the MSE + SSIM objective is defined on RGB frames: it does not combine with --loss_domain yuv420')
-    return dict(w_mse=float(w[0]), w_ssim=float(w[1]))
+    yuv420 = getattr(args, 'loss_domain', 'rgb') == 'yuv420'
+    if name == 'l2':
+        return objective.resolve('yuv420', yuv_loss_params(args), '--loss_domain yuv420') if yuv420 else objective.resolve('l2')
+    keys = tuple(objective.TABLE[name]['defaults'])
+    if len(w) != len(keys):
+        raise ValueError(f"--{flag} takes {' '.join(k.upper() for k in keys)}, got {w!r}")
+    if yuv420:
+        raise ValueError(f"the MSE + {objective.TABLE[name]['title']} objective is defined on RGB frames: it does not combine with "
+                         '--loss_domain yuv420')
+    return objective.resolve(name, dict(zip(keys, w)), '--' + flag)
+
+
+def rec_loss_params(args):
+    """-> None unless the flags ask for an MSE + SSIM objective (--rec_loss ssim / Fusion*, --rec_weights), else dict(w_mse,
+    w_ssim) of model_reconstruction(ssim=...); objective_of's refusals."""
+    obj = objective_of(args)
+    return dict(obj.params) if obj.name == 'ssim' else None
 
 
 def rec_msssim_params(args):
     """-> None unless --rec_loss msssim (weights (0, 1)) or --rec_ms_weights W_MSE W_MS is given, else dict(w_mse, w_ms) of
-    ops.msssim_loss_head_grad / model_reconstruction(msssim=...).  ValueError for both flags, bad weights and --loss_domain yuv420."""
-    name, w = getattr(args, 'rec_loss', None) or 'l2', getattr(args, 'rec_ms_weights', None)
-    if w is not None:
-        if name != 'l2' or getattr(args, 'rec_weights', None) is not None:
-            raise ValueError('--rec_loss, --rec_weights and --rec_ms_weights exclude each other')
-        if len(w) != 2:
-            raise ValueError(f'--rec_ms_weights takes W_MSE W_MS, got {w!r}')
-        w = ops.ms_ssim_loss_args('--rec_ms_weights', (1, 1, 161, 161), (1, 1, 161, 161), *w)   # finite, >= 0, a positive sum
-    elif name == MSSSIM_LOSS:
-        w = MSSSIM_WEIGHTS
-    else:
-        return None
-    if getattr(args, 'loss_domain', 'rgb') == 'yuv420':
-        raise ValueError('the MSE + MS-SSIM objective is defined on RGB frames: it does not combine with --loss_domain yuv420')
-    return dict(w_mse=float(w[0]), w_ms=float(w[1]))
+    model_reconstruction(msssim=...); objective_of's refusals."""
+    obj = objective_of(args)
+    return dict(obj.params) if obj.name == MSSSIM_LOSS else None
 
 
 def rate_params(args, pixels):
@@ -303,8 +304,6 @@ def load_frames(args, cfg, device):
 
 
 METRIC_NAMES = ['pred_seen_psnr', 'pred_seen_ssim', 'pred_unseen_psnr', 'pred_unseen_ssim']   # reference args.metric_names
-SSIM_METRIC_NAME = 'ssim_single_scale'    # added by an MSE + SSIM objective (--rec_loss / --rec_weights)
-YUV_METRIC_NAMES = ['psnr_y', 'psnr_u', 'psnr_v', 'psnr_yuv_611']    # added by --loss_domain yuv420 (the player's keys)
 
 
 @torch.no_grad()
@@ -319,13 +318,10 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None, msssim=None):
     n = len(cache)
     dev = cache.frames.device
     with_ssim = min(cache.frames.shape[-2:]) > 160
-    # --loss_domain yuv420: also the figure that objective is after, PSNR of the 8-bit Y / U / V planes of the output against
-    # those of the cached ground truth (both through ops.frames_to_yuv420), in the player's format
-    yuv = yuv_loss_params(args) if getattr(args, 'loss_domain', 'rgb') == 'yuv420' else None
-    psnr_yuv = []
-    # --rec_loss ssim / Fusion* / --rec_weights: also the figure that objective is after, the single-scale SSIM (ops.ssim)
-    ssim_obj = rec_loss_params(args)
-    ssim1 = []
+    # also the figure the objective is after (objective.TABLE): PSNR-Y / U / V for --loss_domain yuv420, the single-scale SSIM
+    # for --rec_loss ssim / Fusion* / --rec_weights, one more line beside the MS-SSIM for an MS-SSIM objective
+    obj = objective.resolve(MSSSIM_LOSS, msssim, 'evaluate(msssim=)') if msssim is not None else objective_of(args)
+    extra = []
     psnr, ssim, embeds, dec_times = [], [], [], []
     for i in range(n):
         idx = torch.tensor([i], device=dev)
@@ -340,12 +336,9 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None, msssim=None):
         psnr.append(ops.frame_psnr(out, img))
         if with_ssim:
             ssim.append(ops.ms_ssim(out, img))
-        if yuv is not None:
-            h, w = img.shape[-2:]
-            psnr_yuv.append(ops.yuv420_psnr(ops.frames_to_yuv420(out, yuv['matrix'], yuv['full_range']),
-                                            ops.frames_to_yuv420(img, yuv['matrix'], yuv['full_range']), h, w))
-        if ssim_obj is not None:
-            ssim1.append(ops.ssim(out, img))
+        fig = obj.eval_frame(out, img)
+        if fig is not None:
+            extra.append(fig)
         if i % args.print_freq == 0 or i == n - 1:
             logging.info('[{}], Eval at Step [{}/{}], FPS {}, PSNR {}, MS-SSIM {}'.format(
                 datetime.now().strftime("%Y/%m/%d %H:%M:%S"), i + 1, n,
@@ -359,19 +352,10 @@ def evaluate(model, cache: FrameCache, args, cfg, embeddings=None, msssim=None):
     res = [psnr[seen].mean() if seen else torch.zeros(()), psnr[unseen].mean() if unseen else torch.zeros(())]
     args.eval_metrics = dict(zip(METRIC_NAMES, [res[0], ssim[seen].mean() if seen else torch.zeros(()),
                                                 res[1], ssim[unseen].mean() if unseen else torch.zeros(())]))
-    if yuv is not None:   # over all frames, as the player reports them: means of decibels, 6:1:1 per frame
-        p = torch.cat(psnr_yuv).cpu()                  # (frames, 3) float64
-        y, u, v = p.mean(0)
-        m611 = ((6.0 * p[:, 0] + p[:, 1] + p[:, 2]) / 8.0).mean()
-        args.eval_metrics.update(dict(zip(YUV_METRIC_NAMES, [y, u, v, m611])))
-        logging.info('yuv420: PSNR-Y {} U {} V {} | 6:1:1 {}'.format(*(RoundTensor(t, 2) for t in (y, u, v, m611))))
-    if ssim_obj is not None:   # over all frames
-        s1 = torch.cat(ssim1).cpu().mean()
-        args.eval_metrics[SSIM_METRIC_NAME] = s1
-        logging.info('ssim objective {}: SSIM {}'.format(ssim_obj, RoundTensor(s1, 4)))
-    ms_obj = msssim if msssim is not None else rec_msssim_params(args)
-    if ms_obj is not None and with_ssim:   # over all frames: the figure that objective is after is the MS-SSIM logged above
-        logging.info('msssim objective ({}, {}): MS-SSIM {}'.format(ms_obj['w_mse'], ms_obj['w_ms'], RoundTensor(ssim.mean(), 4)))
+    more, line = obj.eval_report(torch.cat(extra).cpu() if extra else None, ssim.mean() if with_ssim else None)   # over all frames
+    args.eval_metrics.update(more)
+    if line is not None:
+        logging.info(line)
     model.train()
     return res, embeds
 
@@ -452,15 +436,9 @@ def calibrate(args, cfg):
     report('Weight quantization w/o opt', evaluate(qnn, cache, args, cfg, embeddings=stored)[0])
 
     logging.info('average bit-width: {}'.format(args.qbits))
-    loss_domain = getattr(args, 'loss_domain', 'rgb')
-    if loss_domain == 'yuv420':
-        logging.info('reconstruction loss: YUV 4:2:0 plane MSEs, {}'.format(yuv_loss_params(args)))
-    ssim_obj = rec_loss_params(args)
-    if ssim_obj is not None:
-        logging.info('reconstruction loss: C * (w_mse * MSE + w_ssim * (1 - SSIM)), {}'.format(ssim_obj))
-    ms_obj = rec_msssim_params(args)
-    if ms_obj is not None:
-        logging.info('reconstruction loss: C * (w_mse * MSE + w_ms * (1 - MS-SSIM)), {}'.format(ms_obj))
+    obj = objective_of(args)
+    if obj.log_line() is not None:
+        logging.info(obj.log_line())
     rate_obj = rate_params(args, n * cache.frames.shape[-2] * cache.frames.shape[-1])
     if rate_obj is not None:
         logging.info('rate term: lambda * bits per pixel of the weight levels, {}'.format(rate_obj))
@@ -469,8 +447,7 @@ def calibrate(args, cfg):
     model_reconstruction(qnn, cali_data=cali_data, gt=train_loader, arch=args.arch, batch_size=args.batch_size,
                          iters=args.iters_w, weight=args.weight, opt_mode='mse', hadamard=args.hadamard,
                          b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr,
-                         loss_domain=loss_domain, yuv=yuv_loss_params(args) if loss_domain == 'yuv420' else None,
-                         ssim=ssim_obj, msssim=ms_obj, **(dict(rate=rate_obj) if rate_obj is not None else {}))
+                         **obj.engine_kwargs(), **(dict(rate=rate_obj) if rate_obj is not None else {}))
     torch.cuda.synchronize()
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
 

@@ -1,7 +1,7 @@
 """FP32 INR trainer (counterpart of the reference's methods/regress.py:151-322; SURVEY §8f-4, a "next" row).
 
-Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, L2 loss, `loss: yuv420`, the
-reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5` or `loss: msssim` (1 - MS-SSIM, optional `loss_weights`), per-epoch
+Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, a config's `loss:` = one objective of
+objective.TABLE: `l2`, `yuv420`, the reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5`, or `msssim`, per-epoch
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
 from the GPU-resident cache; the ConvNeXt encoder and Adam stay in PyTorch.  Evaluations report PSNR and MS-SSIM
@@ -21,7 +21,7 @@ import torch
 
 from ..models import HNeRV, NeRV
 from ..utils import CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger
-from .. import ops
+from .. import objective, ops
 from .calibrate_network import (MSSSIM_LOSS, MSSSIM_WEIGHTS, SSIM_LOSSES, add_yuv_args, add_yuv_loss_args, evaluate, load_frames, report_line, seed_all,
                                 yuv_loss_params)
 
@@ -82,8 +82,7 @@ def loss_params(args, cfg):
         w = cfg.get('loss_weights', MSSSIM_WEIGHTS)
         if not isinstance(w, (list, tuple)) or len(w) != 2:
             raise ValueError(f'loss_weights takes [W_MSE, W_MS], got {w!r}')
-        w = ops.ms_ssim_loss_args('loss_weights', (1, 1, 161, 161), (1, 1, 161, 161), *w)   # finite, >= 0, a positive sum
-        return dict(w_mse=w[0], w_ms=w[1])
+        return objective.resolve(MSSSIM_LOSS, dict(w_mse=w[0], w_ms=w[1]), 'loss_weights').params   # finite, >= 0, a positive sum
     if loss_name in SSIM_LOSSES:
         w_mse, w_ssim = SSIM_LOSSES[loss_name]
         return dict(w_mse=w_mse, w_ssim=w_ssim)
@@ -95,20 +94,15 @@ def loss_params(args, cfg):
 
 
 def step_loss(img_out, img, yuv=None):
-    """the scalar one training step differentiates: per-channel mean of the loss (`yuv`: what loss_params returned)"""
-    if yuv is not None and 'w_ms' in yuv:
-        return ops.ms_ssim_loss(img_out, img, **yuv)
-    if yuv is not None and 'w_ssim' in yuv:
-        return ops.ssim_loss(img_out, img, **yuv)       # the reference's per-frame loss, then .mean(): nothing on top
-    if yuv is not None:
-        return ops.yuv420_loss(img_out, img, **yuv) / 3
-    return ops.l2_loss(img_out, img) / img.shape[1]     # F.mse_loss(...).flatten(1).mean(1).mean()
+    """the scalar one training step differentiates: per-channel mean of the loss (`yuv`: what loss_params returned, or the Objective
+    resolved from it; l2 is F.mse_loss(...).flatten(1).mean(1).mean(), the SSIM losses the reference's per-frame loss, then .mean())"""
+    return objective.of_params(yuv).step_loss(img_out, img)
 
 
 def train(args, cfg):
     if not torch.cuda.is_available():
         raise RuntimeError('neuroquant_amd needs an AMD GPU')
-    yuv = loss_params(args, cfg)
+    obj = objective.of_params(loss_params(args, cfg))
     device = 'cuda'
     cache = FrameCache(load_frames(args, cfg, device))
     n = len(cache)
@@ -119,7 +113,7 @@ def train(args, cfg):
     setup_logger(os.path.join(args.outf, time.strftime('%Y%m%d_%H%M%S') + '.log'))
     if args.weight != 'None':
         model.load_state_dict(torch.load(args.weight, map_location='cpu'), strict=False)
-    msssim = yuv if yuv is not None and 'w_ms' in yuv else None   # evaluations then log the objective's line
+    msssim = obj.params if obj.name == MSSSIM_LOSS else None   # evaluations then log the objective's line
     if args.eval_only:
         res, _ = evaluate(model, cache, args, cfg, msssim=msssim)
         logging.info(report_line('', args))
@@ -134,7 +128,7 @@ def train(args, cfg):
             lr = adjust_lr(optimizer, (epoch + float(i) / len(loader)) / cfg['epoch'], args)
             img = sample['img']
             img_out, _, _ = model(img if args.arch == 'hnerv' else sample['norm_idx'])
-            loss = step_loss(img_out, img, yuv)
+            loss = step_loss(img_out, img, obj)
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             optimizer.step()

@@ -1727,42 +1727,43 @@ def decoder_stack(emb, spec: DecoderSpec, weights):
 
 
 # ------------------------------------------------------------------------------------------ loss / metrics / frames
-class _L2LossFn(Function):
-    """lp_loss(pred, tgt, p=2): sum over channels, mean over batch*H*W (reference quantizer.py:66-71)."""
+class _ScalarLossFn(Function):
+    """A scalar loss of `pred` whose backward is grad * g.  launch(pred, tgt, want_grad) -> (loss, grad or None) issues the kernels;
+    want_grad = `pred` needs a gradient (a launcher may compute the gradient regardless: its launches are its own affair)."""
 
     @staticmethod
-    def forward(ctx, pred, tgt):
-        pred, tgt = _dev(pred, "pred"), _dev(tgt, "tgt")
-        n = pred.numel()
-        mean_count = n // pred.shape[1]
-        loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        dpred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
-        ws = torch.empty(_q("nq_reduce_ws_floats", n), device=pred.device, dtype=torch.float32)
-        L.check(L.lib().nq_l2_loss(_p(pred), _p(tgt), _p(loss), _p(dpred), _p(ws), n, mean_count, 1.0, _stream()), "l2_loss")
-        ctx.save_for_backward(dpred)
+    def forward(ctx, pred, tgt, launch):
+        loss, grad = launch(pred, tgt, ctx.needs_input_grad[0])
+        if grad is not None:
+            ctx.save_for_backward(grad)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        (dpred,) = ctx.saved_tensors
-        return dpred * g, None
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def _l2_loss_launch(pred, tgt, want_grad):
+    """lp_loss(pred, tgt, p=2): sum over channels, mean over batch*H*W (reference quantizer.py:66-71), and its gradient"""
+    pred_d, tgt = _dev(pred.detach(), "pred"), _dev(tgt, "tgt")
+    n = pred_d.numel()
+    loss = torch.empty((), device=pred_d.device, dtype=torch.float32)
+    dpred = torch.empty_like(pred_d) if want_grad else None
+    ws = torch.empty(_q("nq_reduce_ws_floats", n), device=pred_d.device, dtype=torch.float32)
+    L.check(L.lib().nq_l2_loss(_p(pred_d), _p(tgt), _p(loss), _p(dpred), _p(ws), n, n // pred_d.shape[1], 1.0, _stream()),
+            "l2_loss")
+    return loss, dpred
 
 
 def l2_loss(pred, tgt):
-    return _L2LossFn.apply(pred, tgt)
+    return _ScalarLossFn.apply(pred, tgt, _l2_loss_launch)
 
 
 def l2_loss_and_grad(pred, tgt):
     """(loss, d loss / d pred) from ONE kernel, outside autograd: `pred.backward(dpred)` then feeds the decoder node
     directly (no ones-tensor, no elementwise multiply by the upstream gradient)."""
-    pred_d, tgt = _dev(pred.detach(), "pred"), _dev(tgt, "tgt")
-    n = pred_d.numel()
-    loss = torch.empty((), device=pred_d.device, dtype=torch.float32)
-    dpred = torch.empty_like(pred_d)
-    ws = torch.empty(_q("nq_reduce_ws_floats", n), device=pred_d.device, dtype=torch.float32)
-    L.check(L.lib().nq_l2_loss(_p(pred_d), _p(tgt), _p(loss), _p(dpred), _p(ws), n, n // pred_d.shape[1], 1.0, _stream()),
-            "l2_loss")
-    return loss, dpred
+    return _l2_loss_launch(pred, tgt, True)
 
 
 class _HeadHandoff:
@@ -1776,6 +1777,49 @@ class _HeadHandoff:
         self.dconv = self.db = self.version = self.loss = None
 
 
+def _handoff(pred, node=None):
+    """The hand-over slot of the decoder node behind `pred` (node: the manual node of decoder_forward_manual, whose image has no
+    autograd history), or None: only the tensor a tanh-headed decoder node returned carries one, and NQ_FUSED_LOSS=0 hides it."""
+    head = getattr(node if node is not None else getattr(pred, "grad_fn", None), "nq_head", None)
+    return head if isinstance(head, _HeadHandoff) and os.environ.get("NQ_FUSED_LOSS", "1") != "0" else None
+
+
+def _hand_over(head, dconv, db):
+    """Leave the gradient at the head conv's output and the head's bias gradient in the slot -> dconv.  (A result of
+    ops.fused_head_loss that nobody asked for is dropped: the objective that hands over replaces it.)"""
+    head.loss = None
+    head.dconv, head.db, head.version = dconv, db, dconv._version
+    return dconv
+
+
+def _loss_target(what, pred, tgt, cache_u8, idx, typed=False):
+    """The target of a loss launch on images `pred`: exactly one of float frames `tgt` and frames cache_u8[idx] / 255 of the uint8
+    frame cache -> (tgt, cache_u8, idx) with the form not given None, tgt float32 and contiguous on the GPU, idx int64 and
+    contiguous on pred's device.  ValueError for both, neither, or a target of another shape than pred.  A bad cache is a
+    RuntimeError, except typed=True (the SSIM launchers): ValueError for a wrong type or shape, RuntimeError for a cache that is
+    not contiguous on the GPU.  The VALUES of idx stay on the device, unchecked: inside [0, N) is the caller's responsibility."""
+    if (tgt is None) == (cache_u8 is None):
+        raise ValueError(f"{what} takes exactly one of tgt and cache_u8 + idx")
+    if cache_u8 is None:
+        if not typed:
+            tgt = _dev(tgt, "tgt")
+        elif not isinstance(tgt, torch.Tensor):
+            raise ValueError(f"{what} takes a (B, C, H, W) target, got {type(tgt)}")
+        if tuple(tgt.shape) != tuple(pred.shape):
+            raise ValueError(f"{what}: pred {tuple(pred.shape)} and tgt {tuple(tgt.shape)} differ")
+        return _dev(tgt.detach(), "tgt"), None, None
+    bad = not isinstance(cache_u8, torch.Tensor) or cache_u8.dtype != torch.uint8 or cache_u8.dim() != 4 \
+        or not isinstance(idx, torch.Tensor) or (typed and idx.dim() != 1)
+    if bad and typed:
+        raise ValueError(f"{what}: the frame cache must be a uint8 (N, C, H, W) tensor with a 1-d idx")
+    tgt_shape = None if bad else (idx.numel(),) + tuple(cache_u8.shape[1:])
+    if typed and tgt_shape != tuple(pred.shape):
+        raise ValueError(f"{what}: pred {tuple(pred.shape)} and tgt {tgt_shape} differ")
+    if tgt_shape != tuple(pred.shape) or not cache_u8.is_cuda or not cache_u8.is_contiguous():
+        raise RuntimeError("frame cache must be a contiguous uint8 GPU tensor of the image's shape")
+    return None, cache_u8, idx.to(device=pred.device, dtype=torch.int64).contiguous()
+
+
 def l2_loss_tanh_head_raw(pred, tgt=None, cache_u8=None, idx=None):
     """One nq_l2_loss_tanh_head launch on an image `pred` = tanh(conv)*0.5+0.5: -> (loss, dconv, db) with lp_loss(pred,
     tgt, p=2), the gradient at the conv OUTPUT (tanh backward applied) and its per-channel sums (the head's bias
@@ -1787,21 +1831,13 @@ def l2_loss_tanh_head_raw(pred, tgt=None, cache_u8=None, idx=None):
     B, C, H, W = pred_d.shape
     if (H * W) % 4096 != 0 or C > 1024:
         return None
-    if cache_u8 is not None:
-        if not cache_u8.is_cuda or cache_u8.dtype != torch.uint8 or not cache_u8.is_contiguous() \
-                or tuple(cache_u8.shape[1:]) != (C, H, W) or idx.numel() != B:
-            raise RuntimeError("frame cache must be a contiguous uint8 GPU tensor of the image's shape")
-        idx = idx.to(device=pred_d.device, dtype=torch.int64).contiguous()
-    else:
-        tgt = _dev(tgt, "tgt")
+    tgt, cache_u8, idx = _loss_target("l2_loss_tanh_head", pred_d, tgt, cache_u8, idx)
     n = pred_d.numel()
     loss = torch.empty((), device=pred_d.device, dtype=torch.float32)
     dconv = torch.empty_like(pred_d)
     db = torch.empty(C, device=pred_d.device, dtype=torch.float32)
     ws = torch.empty(2 * _q("nq_reduce_ws_floats", n), device=pred_d.device, dtype=torch.float32)
-    L.check(L.lib().nq_l2_loss_tanh_head(_p(pred_d), _p(tgt) if cache_u8 is None else None,
-                                         _p(cache_u8) if cache_u8 is not None else None,
-                                         _p(idx) if cache_u8 is not None else None, _p(loss), _p(dconv), _p(db), _p(ws),
+    L.check(L.lib().nq_l2_loss_tanh_head(_p(pred_d), _p(tgt), _p(cache_u8), _p(idx), _p(loss), _p(dconv), _p(db), _p(ws),
                                          B, C, H * W, n // C, 1.0, _stream()), "l2_loss_tanh_head")
     return loss, dconv, db
 
@@ -1814,20 +1850,14 @@ def l2_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, node=None):
     uint8 frame cache).  The hand-over lives on pred's own autograd node, so g belongs to THIS decoder call only and
     must reach backward() as returned.  Returns None when `pred` is not such an image (no graph recorded, another
     producer) or the fused kernel does not apply; the caller then uses l2_loss_and_grad."""
-    # only the tensor a tanh-headed decoder node returned carries a hand-over slot (node: the manual node of
-    # decoder_forward_manual, whose image has no autograd history)
-    head = getattr(node if node is not None else pred.grad_fn, "nq_head", None)
-    if not isinstance(head, _HeadHandoff) or os.environ.get("NQ_FUSED_LOSS", "1") == "0":
+    head = _handoff(pred, node)
+    if head is None:
         return None
     if head.loss is not None:   # computed behind the head convolution (ops.fused_head_loss): nothing to launch
         loss, head.loss = head.loss, None
         return loss, head.dconv
     out = l2_loss_tanh_head_raw(pred, tgt, cache_u8, idx)
-    if out is None:
-        return None
-    loss, head.dconv, head.db = out
-    head.version = head.dconv._version
-    return loss, head.dconv
+    return None if out is None else (out[0], _hand_over(head, out[1], out[2]))
 
 
 # ---- the same tail in the 8-bit YUV 4:2:0 domain (DESIGN.md §19; include/nq_hip.h: nq_yuv420_loss) ----
@@ -1835,18 +1865,32 @@ YUV_LOSS_WEIGHTS = (6.0, 1.0, 1.0)
 yuv420_loss_launches = 0    # nq_yuv420_loss launches issued (or captured) by this process: the default paths issue none
 
 
+def _loss_weights(what, weights, n):
+    """-> the weights of a loss as floats; ValueError naming `what` unless they are n finite numbers >= 0 with a positive sum"""
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        w = ()
+    if len(w) != n or not all(math.isfinite(v) and v >= 0.0 for v in w) or not sum(w) > 0.0:
+        raise ValueError(f"{what}: weights must be {('two', 'three')[n - 2]} finite numbers >= 0 with a positive sum, got {weights!r}")
+    return w
+
+
+def _mse_plus_args(what, pred_shape, tgt_shape, weights, least, sizes):
+    """the checks of an MSE + (1 - similarity) loss on images whose sides are at least `least` -> its two weights as floats"""
+    if len(pred_shape) != 4 or min(pred_shape[:2]) <= 0 or min(pred_shape[2:]) < least:
+        raise ValueError(f"{what} takes (B, C, H, W) images {sizes}, got {tuple(pred_shape)}")
+    if tuple(tgt_shape) != tuple(pred_shape):
+        raise ValueError(f"{what}: pred {tuple(pred_shape)} and tgt {tuple(tgt_shape)} differ")
+    return _loss_weights(what, weights, 2)
+
+
 def yuv420_loss_args(what, shape, matrix, full_range, weights):
     """-> (matrix code, range code, (wy, wu, wv)); ValueError naming `what` before anything is launched"""
     if len(shape) != 4 or shape[1] != 3 or shape[0] <= 0:
         raise ValueError(f"{what} takes (B, 3, H, W) images, got {tuple(shape)}")
     _, m, fr = _yuv_args(what, shape[2], shape[3], matrix, full_range)
-    try:
-        w = tuple(float(v) for v in weights)
-    except (TypeError, ValueError):
-        w = ()
-    if len(w) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in w) or not sum(w) > 0.0:
-        raise ValueError(f"{what}: weights must be three finite numbers >= 0 with a positive sum, got {weights!r}")
-    return m, fr, w
+    return m, fr, _loss_weights(what, weights, 3)
 
 
 def yuv420_loss_raw(pred, tgt=None, cache_u8=None, idx=None, matrix="bt709", full_range=False, weights=YUV_LOSS_WEIGHTS,
@@ -1862,48 +1906,27 @@ def yuv420_loss_raw(pred, tgt=None, cache_u8=None, idx=None, matrix="bt709", ful
     m, fr, w = yuv420_loss_args("yuv420_loss", pred.shape, matrix, full_range, weights)
     pred_d = _dev(pred.detach(), "pred")
     B, C, H, W = pred_d.shape
-    if (tgt is None) == (cache_u8 is None):
-        raise ValueError("yuv420_loss takes exactly one of tgt and cache_u8 + idx")
-    if cache_u8 is not None:
-        if not cache_u8.is_cuda or cache_u8.dtype != torch.uint8 or not cache_u8.is_contiguous() \
-                or tuple(cache_u8.shape[1:]) != (C, H, W) or idx is None or idx.numel() != B:
-            raise RuntimeError("frame cache must be a contiguous uint8 GPU tensor of the image's shape")
-        idx = idx.to(device=pred_d.device, dtype=torch.int64).contiguous()
-    else:
-        tgt = _dev(tgt, "tgt")
-        if tgt.shape != pred_d.shape:
-            raise ValueError(f"yuv420_loss: pred {tuple(pred_d.shape)} and tgt {tuple(tgt.shape)} differ")
+    tgt, cache_u8, idx = _loss_target("yuv420_loss", pred_d, tgt, cache_u8, idx)
     loss4 = torch.empty(4, device=pred_d.device, dtype=torch.float32)
     grad = torch.empty_like(pred_d)
     db = torch.empty(3, device=pred_d.device, dtype=torch.float32) if head else None
     ws = torch.empty(_q("nq_yuv420_loss_ws_floats", B, H, W), device=pred_d.device, dtype=torch.float32)
     yuv420_loss_launches += 1
     L.check(_timed("yuv420_loss", lambda: L.lib().nq_yuv420_loss(
-        _p(pred_d), _p(tgt) if cache_u8 is None else None, _p(cache_u8) if cache_u8 is not None else None,
-        _p(idx) if cache_u8 is not None else None, _p(loss4), _p(grad), _p(db), _p(ws), B, H, W, m, fr, w[0], w[1], w[2], 1.0,
+        _p(pred_d), _p(tgt), _p(cache_u8), _p(idx), _p(loss4), _p(grad), _p(db), _p(ws), B, H, W, m, fr, w[0], w[1], w[2], 1.0,
         _stream())), "yuv420_loss")
     return loss4, grad, db
-
-
-class _YuvLossFn(Function):
-    """L of yuv420_loss_raw as a scalar; backward is grad * g (as _L2LossFn)."""
-
-    @staticmethod
-    def forward(ctx, pred, tgt, matrix, full_range, weights):
-        loss4, grad, _ = yuv420_loss_raw(pred, tgt=tgt, matrix=matrix, full_range=full_range, weights=weights)
-        ctx.save_for_backward(grad)
-        return loss4[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None, None, None
 
 
 def yuv420_loss(pred, tgt, matrix="bt709", full_range=False, weights=YUV_LOSS_WEIGHTS):
     """Differentiable L of yuv420_loss_raw (w.r.t. `pred`): the weighted plane MSEs of the 8-bit YUV 4:2:0 codes, on the scale
     of l2_loss (the trainer divides both by 3)."""
-    return _YuvLossFn.apply(pred, tgt, matrix, bool(full_range), tuple(weights))
+    full_range, weights = bool(full_range), tuple(weights)
+
+    def launch(pred, tgt, want_grad):
+        loss4, grad, _ = yuv420_loss_raw(pred, tgt=tgt, matrix=matrix, full_range=full_range, weights=weights)
+        return loss4[0].clone(), grad
+    return _ScalarLossFn.apply(pred, tgt, launch)
 
 
 def yuv420_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, matrix="bt709", full_range=False,
@@ -1912,15 +1935,9 @@ def yuv420_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, matrix="bt709
     g)) continues the backward pass.  When `pred` carries the hand-over slot of a tanh-headed decoder node, g is the
     gradient at the head conv's OUTPUT and the head's bias gradient is handed over with it; otherwise g = dL/dpred and the
     ordinary backward runs.  Never None: the kernel has no tiling restriction."""
-    head = getattr(node if node is not None else pred.grad_fn, "nq_head", None)
-    if not isinstance(head, _HeadHandoff) or os.environ.get("NQ_FUSED_LOSS", "1") == "0":
-        loss4, g, _ = yuv420_loss_raw(pred, tgt, cache_u8, idx, matrix, full_range, weights, head=False)
-        return loss4, g
-    # (a result of ops.fused_head_loss that nobody asked for is dropped: this objective replaces it)
-    head.loss = None
-    loss4, head.dconv, head.db = yuv420_loss_raw(pred, tgt, cache_u8, idx, matrix, full_range, weights, head=True)
-    head.version = head.dconv._version
-    return loss4, head.dconv
+    head = _handoff(pred, node)
+    loss4, g, db = yuv420_loss_raw(pred, tgt, cache_u8, idx, matrix, full_range, weights, head=head is not None)
+    return loss4, (g if head is None else _hand_over(head, g, db))
 
 
 # ---- MSE + single-scale SSIM, the reference's ssim / Fusion1 / 3 / 5 losses (DESIGN.md §20; include/nq_hip.h: nq_ssim_loss) ----
@@ -1929,31 +1946,22 @@ SSIM_LOSS_TILE = (8, 118)   # rows x columns a workgroup of csrc/ssim_loss.hip o
 
 def ssim_loss_args(what, pred_shape, tgt_shape, w_mse, w_ssim):
     """-> (w_mse, w_ssim) as floats; ValueError naming `what` before anything is launched"""
-    if len(pred_shape) != 4 or min(pred_shape[:2]) <= 0 or min(pred_shape[2:]) < 11:
-        raise ValueError(f"{what} takes (B, C, H, W) images with H, W >= 11, got {tuple(pred_shape)}")
-    if tuple(tgt_shape) != tuple(pred_shape):
-        raise ValueError(f"{what}: pred {tuple(pred_shape)} and tgt {tuple(tgt_shape)} differ")
-    try:
-        w = (float(w_mse), float(w_ssim))
-    except (TypeError, ValueError):
-        w = (-1.0, -1.0)
-    if not all(math.isfinite(v) and v >= 0.0 for v in w) or not sum(w) > 0.0:
-        raise ValueError(f"{what}: weights must be two finite numbers >= 0 with a positive sum, got {(w_mse, w_ssim)!r}")
-    return w
+    return _mse_plus_args(what, pred_shape, tgt_shape, (w_mse, w_ssim), 11, "with H, W >= 11")
 
 
-def _ssim_loss_launch(what, pred, tgt, w_mse, w_ssim, want_grad):
-    """-> (loss3, grad or None, ws): ws[:B] holds the per-frame SSIM"""
+def _mse_plus_launch(entry, what, pred, tgt, w_mse, w_sim, want_grad, grad_scale=1.0):
+    """One nq_ssim_loss / nq_msssim_loss call (entry "ssim_loss" / "msssim_loss") -> (loss3, grad or None, ws): ws[:B] holds the
+    per-frame SSIM / MS-SSIM"""
     if not isinstance(pred, torch.Tensor) or not isinstance(tgt, torch.Tensor):
         raise ValueError(f"{what} takes two (B, C, H, W) tensors, got {type(pred)} and {type(tgt)}")
-    w = ssim_loss_args(what, pred.shape, tgt.shape, w_mse, w_ssim)
+    w = (ssim_loss_args if entry == "ssim_loss" else ms_ssim_loss_args)(what, pred.shape, tgt.shape, w_mse, w_sim)
     pred_d, tgt = _dev(pred.detach(), "pred"), _dev(tgt.detach(), "tgt")
     B, C, H, W = pred_d.shape
     loss3 = torch.empty(3, device=pred_d.device, dtype=torch.float32)
     grad = torch.empty_like(pred_d) if want_grad else None
-    ws = torch.empty(_q("nq_ssim_loss_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
-    L.check(_timed("ssim_loss", lambda: L.lib().nq_ssim_loss(_p(pred_d), _p(tgt), _p(loss3), _p(grad), _p(ws), B, C, H, W, w[0],
-                                                             w[1], 1.0, _stream())), "ssim_loss")
+    ws = torch.empty(_q(f"nq_{entry}_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
+    L.check(_timed(entry, lambda: getattr(L.lib(), "nq_" + entry)(_p(pred_d), _p(tgt), _p(loss3), _p(grad), _p(ws), B, C, H, W, w[0],
+                                                                  w[1], float(grad_scale), _stream())), entry)
     return loss3, grad, ws
 
 
@@ -1963,28 +1971,18 @@ def ssim_loss_raw(pred, tgt, w_mse, w_ssim, want_grad=True):
     size_average=False) (11-tap Gaussian window, valid filtering; reference utils.py:119-130); grad = dL/dpred, exact, or None
     with want_grad=False (the forward launch alone: the same loss3 bits).  Bit-identical from call to call.  ValueError for a bad
     shape or bad weights before any launch."""
-    loss3, grad, _ = _ssim_loss_launch("ssim_loss", pred, tgt, w_mse, w_ssim, want_grad)
+    loss3, grad, _ = _mse_plus_launch("ssim_loss", "ssim_loss", pred, tgt, w_mse, w_ssim, want_grad)
     return loss3, grad
-
-
-class _SsimLossFn(Function):
-    """L of ssim_loss_raw as a scalar; backward is grad * g (as _YuvLossFn)."""
-
-    @staticmethod
-    def forward(ctx, pred, tgt, w_mse, w_ssim):
-        loss3, grad = ssim_loss_raw(pred, tgt, w_mse, w_ssim)
-        ctx.save_for_backward(grad)
-        return loss3[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None, None
 
 
 def ssim_loss(pred, tgt, w_mse=0.0, w_ssim=1.0):
     """Differentiable L of ssim_loss_raw (w.r.t. `pred`): the reference's per-frame loss followed by .mean()."""
-    return _SsimLossFn.apply(pred, tgt, float(w_mse), float(w_ssim))
+    w_mse, w_ssim = float(w_mse), float(w_ssim)
+
+    def launch(pred, tgt, want_grad):
+        loss3, grad = ssim_loss_raw(pred, tgt, w_mse, w_ssim)
+        return loss3[0].clone(), grad
+    return _ScalarLossFn.apply(pred, tgt, launch)
 
 
 ssim_loss_head_launches = 0    # nq_ssim_loss_head calls issued (or captured) by this process: the default paths issue none
@@ -2001,34 +1999,17 @@ def ssim_loss_head_raw(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ssi
     global ssim_loss_head_launches
     if not isinstance(pred, torch.Tensor):
         raise ValueError(f"ssim_loss_head takes (B, C, H, W) images, got {type(pred)}")
-    if (tgt is None) == (cache_u8 is None):
-        raise ValueError("ssim_loss_head takes exactly one of tgt and cache_u8 + idx")
-    if cache_u8 is not None:
-        if not isinstance(cache_u8, torch.Tensor) or cache_u8.dtype != torch.uint8 or cache_u8.dim() != 4 \
-                or not isinstance(idx, torch.Tensor) or idx.dim() != 1:
-            raise ValueError("ssim_loss_head: the frame cache must be a uint8 (N, C, H, W) tensor with a 1-d idx")
-        tgt_shape = (idx.numel(),) + tuple(cache_u8.shape[1:])
-    else:
-        if not isinstance(tgt, torch.Tensor):
-            raise ValueError(f"ssim_loss_head takes a (B, C, H, W) target, got {type(tgt)}")
-        tgt_shape = tgt.shape
-    w = ssim_loss_args("ssim_loss_head", pred.shape, tgt_shape, w_mse, w_ssim)
+    w = ssim_loss_args("ssim_loss_head", pred.shape, pred.shape, w_mse, w_ssim)
+    tgt, cache_u8, idx = _loss_target("ssim_loss_head", pred, tgt, cache_u8, idx, typed=True)
     pred_d = _dev(pred.detach(), "pred")
     B, C, H, W = pred_d.shape
-    if cache_u8 is not None:
-        if not cache_u8.is_cuda or not cache_u8.is_contiguous():
-            raise RuntimeError("frame cache must be a contiguous uint8 GPU tensor of the image's shape")
-        idx = idx.to(device=pred_d.device, dtype=torch.int64).contiguous()
-    else:
-        tgt = _dev(tgt.detach(), "tgt")
     loss3 = torch.empty(3, device=pred_d.device, dtype=torch.float32)
     grad = torch.empty_like(pred_d)
     db = torch.empty(C, device=pred_d.device, dtype=torch.float32) if head else None
     ws = torch.empty(_q("nq_ssim_loss_head_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
     ssim_loss_head_launches += 1
     L.check(_timed("ssim_loss_head", lambda: L.lib().nq_ssim_loss_head(
-        _p(pred_d), _p(tgt) if cache_u8 is None else None, _p(cache_u8) if cache_u8 is not None else None,
-        _p(idx) if cache_u8 is not None else None, _p(loss3), _p(grad), _p(db), _p(ws), B, C, H, W, w[0], w[1], float(C),
+        _p(pred_d), _p(tgt), _p(cache_u8), _p(idx), _p(loss3), _p(grad), _p(db), _p(ws), B, C, H, W, w[0], w[1], float(C),
         _stream())), "ssim_loss_head")
     return loss3, grad, db
 
@@ -2038,15 +2019,9 @@ def ssim_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ss
     g)) continues the backward pass.  When `pred` carries the hand-over slot of a tanh-headed decoder node, g is the
     gradient at the head conv's OUTPUT and the head's bias gradient is handed over with it; otherwise g = C * dL/dpred and the
     ordinary backward runs.  Never None: the kernel has no tiling restriction."""
-    head = getattr(node if node is not None else getattr(pred, "grad_fn", None), "nq_head", None)
-    if not isinstance(head, _HeadHandoff) or os.environ.get("NQ_FUSED_LOSS", "1") == "0":
-        loss3, g, _ = ssim_loss_head_raw(pred, tgt, cache_u8, idx, w_mse, w_ssim, head=False)
-        return loss3, g
-    # (a result of ops.fused_head_loss that nobody asked for is dropped: this objective replaces it)
-    head.loss = None
-    loss3, head.dconv, head.db = ssim_loss_head_raw(pred, tgt, cache_u8, idx, w_mse, w_ssim, head=True)
-    head.version = head.dconv._version
-    return loss3, head.dconv
+    head = _handoff(pred, node)
+    loss3, g, db = ssim_loss_head_raw(pred, tgt, cache_u8, idx, w_mse, w_ssim, head=head is not None)
+    return loss3, (g if head is None else _hand_over(head, g, db))
 
 
 # ---- MSE + five-scale MS-SSIM (DESIGN.md §22; include/nq_hip.h: nq_msssim_loss) ----
@@ -2056,33 +2031,7 @@ msssim_loss_head_launches = 0  # ops.msssim_loss_head_grad calls issued (or capt
 
 def ms_ssim_loss_args(what, pred_shape, tgt_shape, w_mse, w_ms):
     """-> (w_mse, w_ms) as floats; ValueError naming `what` before anything is launched"""
-    if len(pred_shape) != 4 or min(pred_shape) <= 0 or min(pred_shape[2:]) <= 160:
-        raise ValueError(f"{what} takes (B, C, H, W) images whose smaller side exceeds (11 - 1) * 2**4 = 160, got "
-                         f"{tuple(pred_shape)}")
-    if tuple(tgt_shape) != tuple(pred_shape):
-        raise ValueError(f"{what}: pred {tuple(pred_shape)} and tgt {tuple(tgt_shape)} differ")
-    try:
-        w = (float(w_mse), float(w_ms))
-    except (TypeError, ValueError):
-        w = (-1.0, -1.0)
-    if not all(math.isfinite(v) and v >= 0.0 for v in w) or not sum(w) > 0.0:
-        raise ValueError(f"{what}: weights must be two finite numbers >= 0 with a positive sum, got {(w_mse, w_ms)!r}")
-    return w
-
-
-def _ms_ssim_loss_launch(what, pred, tgt, w_mse, w_ms, want_grad, grad_scale=1.0):
-    """-> (loss3, grad or None, ws): ws[:B] holds the per-frame MS-SSIM"""
-    if not isinstance(pred, torch.Tensor) or not isinstance(tgt, torch.Tensor):
-        raise ValueError(f"{what} takes two (B, C, H, W) tensors, got {type(pred)} and {type(tgt)}")
-    w = ms_ssim_loss_args(what, pred.shape, tgt.shape, w_mse, w_ms)
-    pred_d, tgt = _dev(pred.detach(), "pred"), _dev(tgt.detach(), "tgt")
-    B, C, H, W = pred_d.shape
-    loss3 = torch.empty(3, device=pred_d.device, dtype=torch.float32)
-    grad = torch.empty_like(pred_d) if want_grad else None
-    ws = torch.empty(_q("nq_msssim_loss_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
-    L.check(_timed("msssim_loss", lambda: L.lib().nq_msssim_loss(_p(pred_d), _p(tgt), _p(loss3), _p(grad), _p(ws), B, C, H, W,
-                                                                 w[0], w[1], float(grad_scale), _stream())), "msssim_loss")
-    return loss3, grad, ws
+    return _mse_plus_args(what, pred_shape, tgt_shape, (w_mse, w_ms), 161, "whose smaller side exceeds (11 - 1) * 2**4 = 160")
 
 
 def ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=True):
@@ -2092,30 +2041,19 @@ def ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=True):
     want_grad=False (the forward launches alone: the same loss3 bits).  A (frame, channel) plane on which the relu of a scale
     is active has M = 0 and, by this project's rule, no MS-SSIM gradient (autograd would give NaN).  Bit-identical from call
     to call.  ValueError for a bad shape or bad weights before any launch."""
-    loss3, grad, _ = _ms_ssim_loss_launch("ms_ssim_loss", pred, tgt, w_mse, w_ms, want_grad)
+    loss3, grad, _ = _mse_plus_launch("msssim_loss", "ms_ssim_loss", pred, tgt, w_mse, w_ms, want_grad)
     return loss3, grad
 
 
-class _MsSsimLossFn(Function):
-    """L of ms_ssim_loss_raw as a scalar; backward is grad * g (as _SsimLossFn).  Where `pred` needs no gradient (torch.no_grad, a
-    detached image) the call is forward only: six launches, no derivative maps, the same loss bits."""
-
-    @staticmethod
-    def forward(ctx, pred, tgt, w_mse, w_ms):
-        loss3, grad = ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=ctx.needs_input_grad[0])
-        if grad is not None:
-            ctx.save_for_backward(grad)
-        return loss3[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None, None
-
-
 def ms_ssim_loss(pred, tgt, w_mse=0.0, w_ms=1.0):
-    """Differentiable L of ms_ssim_loss_raw (w.r.t. `pred`)."""
-    return _MsSsimLossFn.apply(pred, tgt, float(w_mse), float(w_ms))
+    """Differentiable L of ms_ssim_loss_raw (w.r.t. `pred`).  Where `pred` needs no gradient (torch.no_grad, a detached image) the
+    call is forward only: six launches, no derivative maps, the same loss bits."""
+    w_mse, w_ms = float(w_mse), float(w_ms)
+
+    def launch(pred, tgt, want_grad):
+        loss3, grad = ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=want_grad)
+        return loss3[0].clone(), grad
+    return _ScalarLossFn.apply(pred, tgt, launch)
 
 
 def msssim_loss_head_grad(img_out, tgt=None, cache_u8=None, idx=None, node=None, w_mse=0.0, w_ms=1.0):
@@ -2129,43 +2067,29 @@ def msssim_loss_head_grad(img_out, tgt=None, cache_u8=None, idx=None, node=None,
     global msssim_loss_head_launches
     if not isinstance(img_out, torch.Tensor):
         raise ValueError(f"msssim_loss_head_grad takes (B, C, H, W) images, got {type(img_out)}")
-    if (tgt is None) == (cache_u8 is None):
-        raise ValueError("msssim_loss_head_grad takes exactly one of tgt and cache_u8 + idx")
-    if cache_u8 is not None:
-        if not isinstance(cache_u8, torch.Tensor) or cache_u8.dtype != torch.uint8 or cache_u8.dim() != 4 \
-                or not isinstance(idx, torch.Tensor) or idx.dim() != 1:
-            raise ValueError("msssim_loss_head_grad: the frame cache must be a uint8 (N, C, H, W) tensor with a 1-d idx")
-        tgt_shape = (idx.numel(),) + tuple(cache_u8.shape[1:])
-    else:
-        if not isinstance(tgt, torch.Tensor):
-            raise ValueError(f"msssim_loss_head_grad takes a (B, C, H, W) target, got {type(tgt)}")
-        tgt_shape = tgt.shape
-    w = ms_ssim_loss_args("msssim_loss_head_grad", img_out.shape, tgt_shape, w_mse, w_ms)
+    w = ms_ssim_loss_args("msssim_loss_head_grad", img_out.shape, img_out.shape, w_mse, w_ms)
+    tgt, cache_u8, idx = _loss_target("msssim_loss_head_grad", img_out, tgt, cache_u8, idx, typed=True)
     if not img_out.is_cuda:
         raise RuntimeError("neuroquant_amd: msssim_loss_head_grad needs GPU tensors")
     if cache_u8 is not None:
         tgt = gather_frames_u8(cache_u8, idx)
     C = img_out.shape[1]
     msssim_loss_head_launches += 1
-    loss3, g, _ = _ms_ssim_loss_launch("msssim_loss_head_grad", img_out, tgt, w[0], w[1], True, grad_scale=float(C))
+    loss3, g, _ = _mse_plus_launch("msssim_loss", "msssim_loss_head_grad", img_out, tgt, w[0], w[1], True, grad_scale=float(C))
     loss3[:1].mul_(float(C))       # the float L times C, one more rounding, on the stream
-    head = getattr(node if node is not None else getattr(img_out, "grad_fn", None), "nq_head", None)
-    if not isinstance(head, _HeadHandoff) or os.environ.get("NQ_FUSED_LOSS", "1") == "0":
+    head = _handoff(img_out, node)
+    if head is None:
         return loss3, g
-    # (a result of ops.fused_head_loss that nobody asked for is dropped: this objective replaces it)
-    head.loss = None
     img_d = _dev(img_out.detach(), "img_out")
-    head.dconv = torch.empty_like(g)
-    L.check(L.lib().nq_tanh_out_backward(_p(g), _p(img_d), _p(head.dconv), g.numel(), _stream()), "tanh_backward")
-    head.db = channel_sum(head.dconv)
-    head.version = head.dconv._version
-    return loss3, head.dconv
+    dconv = torch.empty_like(g)
+    L.check(L.lib().nq_tanh_out_backward(_p(g), _p(img_d), _p(dconv), g.numel(), _stream()), "tanh_backward")
+    return loss3, _hand_over(head, dconv, channel_sum(dconv))
 
 
 def ssim(out, gt):
     """per-frame single-scale SSIM of (F, C, H, W) images -> (F,) fp32 (pytorch_msssim.ssim(out, gt, data_range=1,
     size_average=False)); a frame's value depends on that frame's bytes only.  Forward only (inputs are detached)."""
-    _, _, ws = _ssim_loss_launch("ssim", out, gt, 0.0, 1.0, False)
+    _, _, ws = _mse_plus_launch("ssim_loss", "ssim", out, gt, 0.0, 1.0, False)
     return ws[:out.shape[0]].clone()
 
 

@@ -21,7 +21,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import objective, ops
 from ..utils import allreduce_mean_
 from .data_utils import LinearTempDecay
 from .quant_layer import QuantModule
@@ -50,12 +50,13 @@ class LossFunction:
                  max_count: int = 2000, b_range: tuple = (10, 2), decay_start: float = 0.0, warmup: float = 0.0,
                  p: float = 2., yuv: dict = None, ssim: dict = None, msssim: dict = None):
         self.model = model
-        self.yuv = dict(yuv or {})   # rec_loss 'yuv420': matrix, full_range, weights of ops.yuv420_loss
-        self.ssim = dict(ssim or {})   # rec_loss 'ssim': w_mse, w_ssim of ops.ssim_loss
-        self.msssim = dict(msssim or {})   # rec_loss 'msssim': w_mse, w_ms of ops.ms_ssim_loss
+        self.yuv, self.ssim, self.msssim = dict(yuv or {}), dict(ssim or {}), dict(msssim or {})
         self.round = round_loss
         self.weight = weight
         self.rec = rec_loss
+        # every rec_loss but 'mse' is an objective of objective.TABLE, on the scale of lp_loss as model_reconstruction logs it
+        given = dict(yuv420=self.yuv, ssim=self.ssim, msssim=self.msssim)
+        self.obj = objective.resolve(rec_loss, given[rec_loss], 'LossFunction') if rec_loss in given else None
         self.loss_start = max_count * warmup
         self.p = p
         self.temp_decay = LinearTempDecay(max_count, rel_start_decay=warmup + (1 - warmup) * decay_start,
@@ -69,14 +70,10 @@ class LossFunction:
 
     def __call__(self, pred, tgt, grad=None):
         self.count += 1
-        if self.rec == 'yuv420':
-            rec_loss = ops.yuv420_loss(pred, tgt, **self.yuv)
-        elif self.rec == 'ssim':   # on the scale of lp_loss, as model_reconstruction(ssim=...) logs it
-            rec_loss = ops.ssim_loss(pred, tgt, **self.ssim) * pred.shape[1]
-        elif self.rec == 'msssim':   # on the scale of lp_loss, as model_reconstruction(msssim=...) logs it
-            rec_loss = ops.ms_ssim_loss(pred, tgt, **self.msssim) * pred.shape[1]
-        elif self.rec == 'mse':
+        if self.rec == 'mse':
             rec_loss = lp_loss(pred, tgt, p=self.p)
+        elif self.obj is not None:
+            rec_loss = self.obj.lp_loss(pred, tgt)
         else:
             raise NotImplementedError(f'rec_loss {self.rec!r}: the drivers hard-code opt_mode="mse"')
         b = self.temp_decay(self.count)
@@ -105,11 +102,6 @@ class _Layer:
         self.c_in = m.weight.shape[1]
         self.bias = m.bias.data
         self.W = self.b = None
-
-    def forward_uaq(self):
-        wq, bq = self.m.weight_quantizer, self.m.bias_quantizer
-        Wq = ops.uaq_forward(self.src, wq.delta.data, wq.zero_point, wq.n_levels)
-        self._finish(Wq, ops.uaq_forward(self.bias, bq.delta.data, bq.zero_point, bq.n_levels))
 
     def forward_ada(self):
         wq, bq = self.m.weight_quantizer, self.m.bias_quantizer
@@ -192,14 +184,12 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
     before every iteration (bench.py uses both to time exactly K steps).  probe(phase, layers, grads) is called after
     the backward pass and before the optimiser step with phase 'uaq' | 'ada', the engine's per-layer records (L.W.grad /
     L.b.grad = dL/dW^, dL/db^) and the list of parameter gradients in optimiser order (gradient parity tests).
-    loss_domain 'yuv420' replaces lp_loss by the weighted plane MSEs of the 8-bit YUV 4:2:0 codes (ops.yuv420_loss_head_grad,
-    DESIGN.md §19) with yuv = dict(matrix, full_range, weights) (bt709, limited range, 6:1:1 where absent); the logged `rec` is
-    that loss.  ssim = dict(w_mse, w_ssim) replaces lp_loss by C * mean_b[w_mse MSE_b + w_ssim (1 - SSIM_b)], the reference's
-    ssim / Fusion losses on the scale of lp_loss (ops.ssim_loss_head_grad; weights (1, 0) are lp_loss); the
-    logged `rec` is that loss; it does not combine with loss_domain 'yuv420'.  msssim = dict(w_mse, w_ms) replaces lp_loss by
-    C * mean_b[w_mse MSE_b + w_ms (1 - MS_b)] with the five-scale MS-SSIM (ops.msssim_loss_head_grad; frames
-    whose smaller side exceeds 160); it combines neither with ssim nor with loss_domain 'yuv420'.  Everything else of the
-    iteration is the same.
+    loss_domain, yuv, ssim and msssim choose the reconstruction objective, one entry of objective.TABLE, in place
+    of lp_loss; the logged `rec` is that loss and everything else of the iteration is the same.  loss_domain "yuv420": the
+    weighted plane MSEs of the 8-bit YUV 4:2:0 codes with yuv = dict(matrix, full_range, weights) (bt709, limited
+    range, 6:1:1 where absent).  ssim = dict(w_mse, w_ssim): C * mean_b[w_mse MSE_b + w_ssim (1 - SSIM_b)], the reference's ssim /
+    Fusion losses on the scale of lp_loss.  msssim = dict(w_mse, w_ms): the same with the five-scale MS-SSIM
+    (frames whose smaller side exceeds 160).  Those two combine neither with "yuv420" nor with each other.
     rate = dict(weight=lambda, pixels=P) adds lambda * R_soft / P to the phase-2 objective: the entropy cost, under a static
     per-tensor model, of the levels the weight quantisers would store (ops.level_rate; P = frames * H * W of the
     clip, so the term is lambda * bits per pixel).  Phase 2 then takes the unfused parameter side (d(alpha), the rate kernels
@@ -212,37 +202,9 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
         raise ValueError
     if opt_mode != 'mse' or p != 2.0:
         raise NotImplementedError('only opt_mode="mse", p=2 is on the calibration path')
-    if loss_domain not in ('rgb', 'yuv420'):
-        raise ValueError(f"loss_domain must be 'rgb' or 'yuv420', got {loss_domain!r}")
-    yuv = dict(yuv or {})
-    if set(yuv) - {'matrix', 'full_range', 'weights'}:
-        raise ValueError(f"yuv takes matrix, full_range and weights, got {sorted(yuv)}")
-    if loss_domain == 'yuv420':   # a bad matrix or bad weights stop here, before the first iteration
-        ops.yuv420_loss_args('model_reconstruction', (1, 3, 2, 2), yuv.get('matrix', 'bt709'), yuv.get('full_range', False),
-                             yuv.get('weights', ops.YUV_LOSS_WEIGHTS))
-    if ssim is not None:   # bad keys, bad weights and the YUV combination stop here, before the first iteration
-        if not isinstance(ssim, dict) or set(ssim) != {'w_mse', 'w_ssim'}:
-            raise ValueError(f"ssim takes dict(w_mse, w_ssim), got {sorted(ssim) if isinstance(ssim, dict) else ssim!r}")
-        if loss_domain == 'yuv420':
-            raise ValueError("the SSIM objective is defined on RGB frames: it does not combine with loss_domain 'yuv420'")
-        ssim = dict(zip(('w_mse', 'w_ssim'), ops.ssim_loss_args('model_reconstruction', (1, 1, 11, 11), (1, 1, 11, 11),
-                                                                ssim['w_mse'], ssim['w_ssim'])))
-    if msssim is not None:   # the same for the MS-SSIM objective
-        if not isinstance(msssim, dict) or set(msssim) != {'w_mse', 'w_ms'}:
-            raise ValueError(f"msssim takes dict(w_mse, w_ms), got {sorted(msssim) if isinstance(msssim, dict) else msssim!r}")
-        if ssim is not None:
-            raise ValueError("msssim and ssim are two objectives: give one")
-        if loss_domain == 'yuv420':
-            raise ValueError("the MS-SSIM objective is defined on RGB frames: it does not combine with loss_domain 'yuv420'")
-        msssim = dict(zip(('w_mse', 'w_ms'), ops.ms_ssim_loss_args('model_reconstruction', (1, 1, 161, 161), (1, 1, 161, 161),
-                                                                   msssim['w_mse'], msssim['w_ms'])))
-    if rate is not None:   # bad keys, a bad weight and bad pixels stop here, before the first iteration
-        if not isinstance(rate, dict) or set(rate) != {'weight', 'pixels'}:
-            raise ValueError(f"rate takes dict(weight, pixels), got {sorted(rate) if isinstance(rate, dict) else rate!r}")
-        px = rate['pixels']
-        if isinstance(px, bool) or not isinstance(px, int) or px <= 0:
-            raise ValueError(f"rate: pixels must be a positive int (frames * H * W), got {px!r}")
-        rate = dict(weight=ops.level_rate_args('model_reconstruction(rate=)', rate['weight']), pixels=px)
+    # bad keys, bad weights and what does not combine stop here, before the first iteration
+    obj = objective.from_kwargs(loss_domain, yuv, ssim, msssim)
+    rate = objective.rate_kwarg(rate)
     model.set_quant_state(True)
     device = next(model.parameters()).device
     layers = [_Layer(m, hadamard) for m in _quant_modules(model)]
@@ -375,65 +337,26 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
                 fq = ops.adaround_fwht_multi(items)
                 for i, L in enumerate(layers):
                     L._finish(fq[2 * i], fq[2 * i + 1], transformed=True)
-            elif ada:   # all 14 fake-quantised tensors in one launch
-                fq = ops.adaround_forward_multi(
-                    [it for L in layers for it in L.ada_items()])
-                if hadamard:   # H(Q(H w)) of every layer in one launch (quant_layer.py:70-71)
-                    had = ops.fwht_channels_multi([(fq[2 * i], L.n, L.c_in) for i, L in enumerate(layers)])
-                    for i, L in enumerate(layers):
-                        L._finish(had[i], fq[2 * i + 1], transformed=True)
-                else:
-                    for i, L in enumerate(layers):
-                        L._finish(fq[2 * i], fq[2 * i + 1])
-            else:   # phase 1: the UAQ fake-quant of all 14 tensors in one launch (+ one FWHT launch with Hadamard)
-                fq = ops.uaq_forward_multi([it for L in layers for it in L.uaq_items()])
-                if hadamard:
-                    had = ops.fwht_channels_multi([(fq[2 * i], L.n, L.c_in) for i, L in enumerate(layers)])
-                    for i, L in enumerate(layers):
-                        L._finish(had[i], fq[2 * i + 1], transformed=True)
-                else:
-                    for i, L in enumerate(layers):
-                        L._finish(fq[2 * i], fq[2 * i + 1])
+            else:   # all 14 fake-quantised tensors in one launch: AdaRound in phase 2, UAQ in phase 1
+                fq = ops.adaround_forward_multi([it for L in layers for it in L.ada_items()]) if ada \
+                    else ops.uaq_forward_multi([it for L in layers for it in L.uaq_items()])
+                # H(Q(H w)) of every layer in one more launch with Hadamard (quant_layer.py:70-71)
+                had = ops.fwht_channels_multi([(fq[2 * i], L.n, L.c_in) for i, L in enumerate(layers)]) if hadamard else None
+                for i, L in enumerate(layers):
+                    L._finish(fq[2 * i] if had is None else had[i], fq[2 * i + 1], transformed=True)
             node = None
-            # (the loss tail runs behind the head convolution when the decoder is the fused stack: ops.fused_head_loss)
-            # (... for lp_loss only: the YUV and the SSIM objective have their own launch behind the head)
-            if loss_domain == 'yuv420' or ssim is not None or msssim is not None:
-                loss_req = contextlib.nullcontext()
-            else:
-                loss_req = ops.fused_head_loss(cache_u8=img[0], idx=img[1]) if isinstance(img, tuple) else ops.fused_head_loss(tgt=img)
-            with loss_req:
+            # (lp_loss only: its tail runs behind the head convolution when the decoder is the fused stack, ops.fused_head_loss)
+            with obj.head_request(img):
                 if staged is None:
                     img_out, _, _ = model(inputs)
                 else:   # the same decoder node, driven by hand (weights as model._wb_override set them, in layer order)
                     spec, provs = fused_stack
                     img_out, node = ops.decoder_forward_manual(inputs, spec, [p() for p in provs],
                                                                two_phase=os.environ.get("NQ_DP_OVERLAP", "1") != "0")
-            # lp_loss p=2 (quantizer.py:66-71) and its gradient; behind a tanh-headed fused decoder the loss kernel also
-            # applies the tanh backward and sums the head's bias gradient (ops.l2_loss_head_grad), reading the target
-            # straight from the uint8 frame cache when the batch came as (frames_u8, indices)
-            if loss_domain == 'yuv420':
-                # the weighted plane MSEs of the 8-bit 4:2:0 codes instead: same hand-over, same targets
-                loss4, dimg = ops.yuv420_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **yuv) \
-                    if isinstance(img, tuple) else ops.yuv420_loss_head_grad(img_out, tgt=img, node=node, **yuv)
-                fused = (loss4[0], dimg)
-            elif ssim is not None:
-                # MSE + SSIM instead: same hand-over, same targets
-                loss3, dimg = ops.ssim_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **ssim) \
-                    if isinstance(img, tuple) else ops.ssim_loss_head_grad(img_out, tgt=img, node=node, **ssim)
-                fused = (loss3[0], dimg)
-            elif msssim is not None:
-                # MSE + MS-SSIM instead: same hand-over, same targets
-                loss3, dimg = ops.msssim_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node, **msssim) \
-                    if isinstance(img, tuple) else ops.msssim_loss_head_grad(img_out, tgt=img, node=node, **msssim)
-                fused = (loss3[0], dimg)
-            else:
-                fused = ops.l2_loss_head_grad(img_out, cache_u8=img[0], idx=img[1], node=node) if isinstance(img, tuple) \
-                    else ops.l2_loss_head_grad(img_out, tgt=img, node=node)
-            if fused is None:
-                if isinstance(img, tuple):
-                    img = ops.gather_frames_u8(img[0], img[1])
-                fused = ops.l2_loss_and_grad(img_out, img)
-            rec, dimg = fused
+            # the objective and its gradient (lp_loss p=2, quantizer.py:66-71, unless asked otherwise); behind a tanh-headed fused
+            # decoder its kernel also applies the tanh backward and sums the head's bias gradient (the hand-over of ops.*_head_grad),
+            # reading the target straight from the uint8 frame cache when the batch came as (frames_u8, indices)
+            rec, dimg = obj.head_grad(img_out, img, node)
             if staged is None:
                 img_out.backward(dimg)
             else:
