@@ -55,6 +55,39 @@ NQ_API const char* nq_error_string(int code);
 NQ_API int nq_scale_init_max(const float* x, int64_t rows, int64_t row_len, int n_levels, float* delta, float* zp,
                       nq_stream_t stream);
 
+/* UniformAffineQuantizer.init_quantization_scale, 'mse' / 'l1' / 'gaussian' (quantizer.py:170-220, 227-234).
+ * THE DEFINITION, shared by the kernels (csrc/scale_init.hip), ops and the tests' restatement (tests/scale_init_ref.py).
+ * A row is one output channel, or the whole tensor (rows=1); it has n = row_len elements; K = n_levels.
+ *
+ * Search ('mse': p = 3.5, 'l1': p = 1).  All fp32, uncontracted, IEEE division, round-half-even, unless marked double:
+ *   x_max, x_min   the row's maximum and minimum (0 is NOT included, unlike 'max')
+ *   candidates i = 0..9:   f_i = (float)(1.0 - i*0.05) [double inside], hi = x_max*f_i, lo = x_min*f_i,
+ *                          delta_i = max((hi - lo) / (float)(K - 1), 1e-8f), zp_i = rint((-lo) / delta_i)
+ *   per element:           q = clamp(rint(x / delta_i) + zp_i, 0, K - 1), xq = (q - zp_i)*delta_i, t = |x - xq|
+ *   score [double]:        s_i = (sum of term) / n, term = (double)t for p = 1, pow((double)t, p) otherwise
+ *   winner:                the lowest i with s_i < s_j for every earlier j, starting from 1e10 (strict <, as the reference).
+ *                          A row none of whose scores is below 1e10 (a NaN or Inf in the row) has no winner: choice = -1 and
+ *                          delta = zp = NaN.
+ * The reference sums the scores in fp32; the double sum is this project's definition, so that the result does not depend on
+ * an order of summation.
+ *
+ * 'gaussian', the reference's quirk kept -- the VARIANCE where a standard deviation was surely meant, so it clips hard:
+ *   mu = mean, var = unbiased variance (divisor n - 1), two passes (the mean, then the squared deviations from the unrounded
+ *   mean), accumulated in double, each rounded once to fp32;  x_min = min(mu - 6*var, 0), x_max = max(mu + 6*var, 0),
+ *   delta = max((x_max - x_min) / (float)(K - 1), 1e-8f), zp = rint((-x_min) / delta).  A row of one element has no variance:
+ *   NaN, as in the reference.
+ *
+ * delta, zp: rows floats.  choice: rows int32.  scores (may be NULL): rows x 10 doubles.  stats (may be NULL): rows x {mu, var}.
+ * ws: at least nq_scale_init_ws_bytes(rows, row_len) bytes, 8-byte aligned; that query returns NQ_ERR_INVALID for sizes the
+ * entries refuse.  2 <= n_levels <= 65536, p finite and > 0.  The launch plan depends on (rows, row_len) only and nothing is
+ * accumulated atomically: two calls on the same data give the same bits.  One launch for rows of up to 8192 elements (x read
+ * once), three for longer rows, which are cut into pieces of 8192 elements (x read twice). */
+NQ_API int64_t nq_scale_init_ws_bytes(int64_t rows, int64_t row_len);
+NQ_API int nq_scale_init_search(const float* x, int64_t rows, int64_t row_len, int n_levels, double p, float* delta, float* zp,
+                         int* choice, double* scores, void* ws, nq_stream_t stream);
+NQ_API int nq_scale_init_gaussian(const float* x, int64_t rows, int64_t row_len, int n_levels, float* delta, float* zp, float* stats,
+                           void* ws, nq_stream_t stream);
+
 /* UniformAffineQuantizer.forward (quantizer.py:117-119): y = (clamp(rint(x/delta)+zp, 0, L-1) - zp)*delta. */
 NQ_API int nq_uaq_forward(const float* x, const float* delta, const float* zp, float* y, int64_t rows, int64_t row_len,
                    int per_row, int n_levels, nq_stream_t stream);

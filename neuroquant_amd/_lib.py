@@ -116,6 +116,9 @@ def _load():
                              "(`make -C neuroquant_amd/csrc`)")
     sig("nq_error_string", c_char_p, I)
     sig("nq_scale_init_max", I, P, L, L, I, P, P, P)
+    sig("nq_scale_init_ws_bytes", L, L, L)
+    sig("nq_scale_init_search", I, P, L, L, I, ctypes.c_double, P, P, P, P, P, P)
+    sig("nq_scale_init_gaussian", I, P, L, L, I, P, P, P, P, P)
     sig("nq_uaq_forward", I, P, P, P, P, L, L, I, I, P)
     sig("nq_uaq_backward", I, P, P, P, P, P, P, L, L, I, I, P)
     sig("nq_adaround_init", I, P, P, P, P, P, P, L, L, I, P)
@@ -238,6 +241,7 @@ EXPORTS = (
     "nq_weight_layout3_f16", "nq_conv_forward3_levels_f16",
     "nq_conv_forward_plan", "nq_conv_wgrad_plan",
     "nq_level_rate_ws_words", "nq_level_rate",
+    "nq_scale_init_ws_bytes", "nq_scale_init_search", "nq_scale_init_gaussian",
 )
 
 _lib = None

@@ -247,7 +247,7 @@ def size_tables(numels, bit_choices, entropy_bits=None):
 @torch.no_grad()
 def perturbation_table(model, bit_choices, args):
     """-> (table, hists, sizes): table[l][c] = v_l(c) = W_l - Q_c(W_l), bit for bit what QuantModel.get_perturbation()[l] is
-    after set_bitwidth([c] * L) and the lazy-init forward, from the same kernels (ops.scale_init_max, ops.uaq_forward_multi)
+    after set_bitwidth([c] * L) and the lazy-init forward, from the same kernels (ops.scale_init with --init's method, ops.uaq_forward_multi)
     without a QuantModel copy or a decoder forward; hists[l][c] = (weight, bias) level histograms of the hard UAQ levels
     (what export_quantized would store); sizes = size_tables(...).  With args.hadamard the scales come from the transformed,
     zero-padded weight and are applied to the weight itself, as QuantModule.get_weight_perturbation does."""
@@ -257,11 +257,11 @@ def perturbation_table(model, bit_choices, args):
     srcs = [ops.hadamard_weight_of(m.weight.data) if args.hadamard else m.weight.data for m in convs]
     for c in bit_choices:
         nl = 2 ** int(c)
-        scales = [ops.scale_init_max(src, nl, args.channel_wise) for src in srcs]
+        scales = [ops.scale_init(src, nl, args.channel_wise, args.init) for src in srcs]
         fq = ops.uaq_forward_multi([(m.weight.data, d, z, nl) for m, (d, z) in zip(convs, scales)])
         for l, (m, src, (d, z), q) in enumerate(zip(convs, srcs, scales, fq)):
             table[l].append(m.weight.data - q)
-            bd, bz = ops.scale_init_max(m.bias.data, nl, args.channel_wise)
+            bd, bz = ops.scale_init(m.bias.data, nl, args.channel_wise, args.init)
             wl, bl = _hard_levels(src, d, z, nl), _hard_levels(m.bias.data, bd, bz, nl)
             hists[l].append((torch.bincount(wl.flatten().long(), minlength=nl), torch.bincount(bl.flatten().long(), minlength=nl)))
             ent[l].append(_entropy_bits(wl, nl) + _entropy_bits(bl, nl))

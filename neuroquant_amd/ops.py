@@ -104,21 +104,121 @@ def _rows(x: torch.Tensor, scale: torch.Tensor):
 
 
 # ------------------------------------------------------------------------------------------ quantisers
+def _scale_rows(x: torch.Tensor, channel_wise: bool):
+    """(rows, result shape) of a scale init: a row is an output channel of a channel-wise 4-D weight, else the whole tensor
+    (reference quantizer.py:127-152)."""
+    if channel_wise:
+        if x.dim() == 4:
+            return x.shape[0], (-1, 1, 1, 1)
+        if x.dim() == 1:
+            return 1, (-1,)
+        raise ValueError
+    return 1, ()
+
+
 def scale_init_max(x: torch.Tensor, n_levels: int, channel_wise: bool):
     """UniformAffineQuantizer.init_quantization_scale 'max' (reference quantizer.py:127-168)."""
     x = _dev(x.detach(), "x")
-    if channel_wise:
-        if x.dim() == 4:
-            rows, shape = x.shape[0], (-1, 1, 1, 1)
-        elif x.dim() == 1:
-            rows, shape = 1, (-1,)
-        else:
-            raise ValueError
-    else:
-        rows, shape = 1, ()
+    rows, shape = _scale_rows(x, channel_wise)
     delta = torch.empty(rows, device=x.device, dtype=torch.float32)
     zp = torch.empty_like(delta)
     L.check(L.lib().nq_scale_init_max(_p(x), rows, x.numel() // rows, n_levels, _p(delta), _p(zp), _stream()), "scale_init")
+    return delta.view(shape), zp.view(shape)
+
+
+SCALE_SEARCH_P = {"mse": 3.5, "l1": 1.0}   # the reference's lp_loss exponent / F.l1_loss (quantizer.py:181, 215)
+SCALE_CANDIDATES = 10
+
+
+def _scale_init_args(what, x, n_levels):
+    if isinstance(n_levels, bool) or not isinstance(n_levels, int) or not 2 <= n_levels <= 65536:
+        raise ValueError(f"{what}: n_levels must be an int in [2, 65536], got {n_levels!r}")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.numel() == 0:
+        raise ValueError(f"{what}: x is a non-empty (rows, row_len) tensor")
+    x = _dev(x.detach(), "x")
+    rows, row_len = x.shape
+    nbytes = _q("nq_scale_init_ws_bytes", rows, row_len)
+    if nbytes <= 0:
+        raise ValueError(f"{what}: {rows} rows of {row_len} elements are more than one launch holds")
+    return x, rows, row_len, torch.empty((nbytes + 7) // 8, device=x.device, dtype=torch.float64)
+
+
+def _scale_init_out(what, out, specs, device):
+    """out= of the raw scale inits: every buffer is on x's device, contiguous, of the entry's dtype and exact size (the C entry
+    writes them unchecked); a None is allowed only where the entry takes NULL."""
+    if len(out) != len(specs):
+        raise ValueError(f"{what}: out holds {len(specs)} buffers")
+    for t, (name, dtype, numel, optional) in zip(out, specs):
+        if t is None and optional:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or t.numel() != numel
+                or not t.is_contiguous()):
+            raise ValueError(f"{what}: out buffer {name} must be a contiguous {dtype} tensor of {numel} elements on {device}")
+    return out
+
+
+def scale_init_search_raw(x, n_levels, p, want_scores=True, out=None):
+    """x (rows, row_len) -> delta, zp [float (rows,)], choice [int32 (rows,), -1: no candidate scored below 1e10], scores
+    [float64 (rows, 10) or None]: the ten-candidate range search of include/nq_hip.h (nq_scale_init_search), on the device,
+    nothing read by the host.  out: (delta, zp, choice, scores) buffers to write instead of fresh ones (checked: device,
+    dtype, size, contiguity; scores may be None)."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or p <= 0:
+        raise ValueError(f"scale_init_search: p must be a finite positive number, got {p!r}")
+    x, rows, row_len, ws = _scale_init_args("scale_init_search", x, n_levels)
+    if out is None:
+        delta = torch.empty(rows, device=x.device, dtype=torch.float32)
+        zp = torch.empty_like(delta)
+        choice = torch.empty(rows, device=x.device, dtype=torch.int32)
+        scores = torch.empty((rows, SCALE_CANDIDATES), device=x.device, dtype=torch.float64) if want_scores else None
+    else:
+        delta, zp, choice, scores = _scale_init_out("scale_init_search", out, (
+            ("delta", torch.float32, rows, False), ("zp", torch.float32, rows, False), ("choice", torch.int32, rows, False),
+            ("scores", torch.float64, rows * SCALE_CANDIDATES, True)), x.device)
+    L.check(L.lib().nq_scale_init_search(_p(x), rows, row_len, n_levels, float(p), _p(delta), _p(zp), _p(choice), _p(scores),
+                                         _p(ws), _stream()), "scale_init_search")
+    return delta, zp, choice, scores
+
+
+def scale_init_gaussian_raw(x, n_levels, want_stats=True, out=None):
+    """x (rows, row_len) -> delta, zp [float (rows,)], stats [float (rows, 2) = {mean, unbiased variance} or None]
+    (nq_scale_init_gaussian).  out: (delta, zp, stats) buffers to write instead of fresh ones (checked likewise; stats may be None)."""
+    x, rows, row_len, ws = _scale_init_args("scale_init_gaussian", x, n_levels)
+    if out is None:
+        delta = torch.empty(rows, device=x.device, dtype=torch.float32)
+        zp = torch.empty_like(delta)
+        stats = torch.empty((rows, 2), device=x.device, dtype=torch.float32) if want_stats else None
+    else:
+        delta, zp, stats = _scale_init_out("scale_init_gaussian", out, (
+            ("delta", torch.float32, rows, False), ("zp", torch.float32, rows, False), ("stats", torch.float32, 2 * rows, True)), x.device)
+    L.check(L.lib().nq_scale_init_gaussian(_p(x), rows, row_len, n_levels, _p(delta), _p(zp), _p(stats), _p(ws), _stream()),
+            "scale_init_gaussian")
+    return delta, zp, stats
+
+
+def scale_init(x: torch.Tensor, n_levels: int, channel_wise: bool, method: str = "max"):
+    """UniformAffineQuantizer.init_quantization_scale for every scale_method the reference implements (quantizer.py:127-225):
+    'max' (any name holding it, as the reference tests) is scale_init_max, unchanged; 'mse' / 'l1' search ten clipped ranges
+    per row, 'gaussian' takes mean -+ 6 * variance (include/nq_hip.h).  Result shapes as for 'max'.  One host read per call of
+    a searched or gaussian init: a row without a finite result (a NaN or Inf in it) is a ValueError that names the row."""
+    if not isinstance(method, str):
+        raise NotImplementedError(f"scale_method {method!r}")
+    if "max" in method:
+        return scale_init_max(x, n_levels, channel_wise)
+    if method not in SCALE_SEARCH_P and method != "gaussian":
+        raise NotImplementedError(f"scale_method {method!r}: the reference implements max, mse, gaussian and l1")
+    rows, shape = _scale_rows(x, channel_wise)
+    x2 = _dev(x.detach(), "x").view(rows, -1)
+    if method == "gaussian":
+        delta, zp, _ = scale_init_gaussian_raw(x2, n_levels, want_stats=False)
+        bad = ~torch.isfinite(delta)
+        if bool(bad.any()):
+            raise ValueError(f"scale init 'gaussian': row {int(bad.nonzero()[0])} of {rows} has no finite mean and variance "
+                             "(a NaN or Inf in it, or a single element)")
+    else:
+        delta, zp, choice, _ = scale_init_search_raw(x2, n_levels, SCALE_SEARCH_P[method], want_scores=False)
+        if int(choice.min()) < 0:
+            raise ValueError(f"scale init {method!r}: row {int((choice < 0).nonzero()[0])} of {rows} has no candidate with a "
+                             "score below 1e10 (a NaN or Inf in it)")
     return delta.view(shape), zp.view(shape)
 
 

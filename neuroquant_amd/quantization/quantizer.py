@@ -1,7 +1,9 @@
 """Quantisers with the reference's interface (quantization/quantizer.py) on HIP kernels.
 
-Only what the network-wise calibration path reaches is implemented: UniformAffineQuantizer with
-scale_method 'max' and AdaRoundQuantizer with round_mode 'learned_hard_sigmoid' (SURVEY.md §2 row 5).
+Only what the network-wise calibration path reaches is implemented: UniformAffineQuantizer, asymmetric, with every
+scale_method the reference implements -- 'max', and 'mse' / 'l1' / 'gaussian' on the scale-init kernels (ops.scale_init,
+DESIGN.md §25; 'l2' is refused as the reference refuses it) -- and AdaRoundQuantizer with round_mode 'learned_hard_sigmoid'
+(SURVEY.md §2 row 5).
 """
 import logging
 import time
@@ -62,11 +64,9 @@ class UniformAffineQuantizer(nn.Module):
         return x_ans
 
     def init_quantization_scale(self, x: torch.Tensor, channel_wise: bool = False):
-        if 'max' not in self.scale_method:
-            raise NotImplementedError(f"scale_method {self.scale_method!r}: only 'max' is on the calibration path")
         if self.sym:
             raise NotImplementedError('symmetric quantisation is not on the calibration path')
-        return ops.scale_init_max(x, self.n_levels, channel_wise)
+        return ops.scale_init(x, self.n_levels, channel_wise, self.scale_method)
 
     def bitwidth_refactor(self, refactored_bit: int):
         assert 2 <= refactored_bit <= 8, 'bitwidth not supported'
