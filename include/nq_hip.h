@@ -746,6 +746,31 @@ NQ_API int nq_rans_decode(const uint16_t* words, const uint32_t* states, const u
                    int n_bits, int64_t chunk, const float* delta, const float* zp, int64_t row_len, uint8_t* levels, float* w,
                    nq_stream_t stream);
 
+/* ---- the encoder of that code (additive: nq_abi_version() stays 7) ----
+ * levels: n levels, one byte each (flat, C order); a level that does not fit n_bits bits is MASKED to them, as in
+ * nq_pack_levels.  The four outputs are the four sections nq_rans_decode takes, bit for bit what the host encoder of DESIGN.md
+ * §12.1 writes for the same levels.  All pointers are device pointers; the library allocates nothing.
+ *   nq_rans_encode_ws_bytes  bytes of the workspace both entries take (16-byte aligned): the partial histograms, one word
+ *                            count per chunk and, per chunk, a scratch region of min(chunk, n rounded up to 64) words.  0 for
+ *                            arguments the entries refuse.  Pure host function.
+ *   nq_rans_table            freq[2^n_bits] = the normalised histogram of the levels (sum 4096, an occurring level keeps f >= 1;
+ *                            the three integer steps of §12.1).  Two launches: partial histograms in LDS, one per workgroup, no
+ *                            global atomics; one workgroup adds them in a fixed order and normalises.  Uses the first part of
+ *                            the workspace only, whatever the chunk.
+ *   nq_rans_encode           freq as nq_rans_table wrote it for THESE levels (a level whose f is 0 encodes to garbage, never
+ *                            to a fault).  states: 64 per chunk (a lane without a symbol stores 2^16); offsets: chunks + 1,
+ *                            offsets[chunks] = the number of words; words: room for n (a symbol costs at most one), the first
+ *                            offsets[chunks] are written.  Three launches: one wavefront encodes one chunk into the tail of its
+ *                            scratch region, one workgroup scans the counts, a copy moves the tails into place.
+ * Bit-identical from call to call.  NQ_ERR_INVALID, before the device is touched, for null pointers, n <= 0, n_bits outside
+ * 1..8, chunk <= 0 or not a multiple of 64 (nq_rans_encode), a workspace that is too small or not 16-byte aligned;
+ * NQ_ERR_UNSUPPORTED for n >= 2^32 (32-bit counts and offsets) or more than 2^31 - 1 workgroups. */
+NQ_API int64_t nq_rans_encode_ws_bytes(int64_t n, int n_bits, int64_t chunk);
+NQ_API int nq_rans_table(const uint8_t* levels, int64_t n, int n_bits, uint16_t* freq, void* ws, int64_t ws_bytes,
+                  nq_stream_t stream);
+NQ_API int nq_rans_encode(const uint8_t* levels, int64_t n, int n_bits, int64_t chunk, const uint16_t* freq, uint32_t* states,
+                   uint32_t* offsets, uint16_t* words, void* ws, int64_t ws_bytes, nq_stream_t stream);
+
 /* ---- quantised, temporally coded frame embeddings (additive: nq_abi_version() stays 7) ----
  * x is (N, C, HW) fp32: N frames, C embedding channels, HW positions, E = C * HW values per frame; delta / zp hold one value
  * per channel.  level[t][e] = clamp(rint(x[t][e] / delta[c]) + zp[c], 0, 2^n_bits - 1) with c = e / HW, in fp32 and

@@ -207,6 +207,9 @@ def _load():
     sig("nq_msssim_loss", I, P, P, P, P, P, I, I, I, I, F, F, F, P)
     sig("nq_rans_chunks", L, L, L)
     sig("nq_rans_decode", I, P, P, P, P, L, I, L, P, P, L, P, P, P)
+    sig("nq_rans_encode_ws_bytes", L, L, I, L)
+    sig("nq_rans_table", I, P, L, I, P, P, L, P)
+    sig("nq_rans_encode", I, P, L, I, L, P, P, P, P, P, L, P)
     sig("nq_embed_symbols", I, P, P, P, L, L, L, I, I, P, P, P)
     sig("nq_embed_restore", I, P, P, P, L, L, L, I, I, P, P)
     sig("nq_rows_dot_ws_bytes", L, I, L)
@@ -234,7 +237,7 @@ EXPORTS = (
     "nq_yuv420_frame_bytes", "nq_frames_to_yuv420", "nq_yuv420_to_rgb_u8", "nq_yuv420_sse",
     "nq_yuv420_loss_ws_floats", "nq_yuv420_loss", "nq_ssim_loss_ws_floats", "nq_ssim_loss",
     "nq_ssim_loss_head_ws_floats", "nq_ssim_loss_head", "nq_msssim_loss_ws_floats", "nq_msssim_loss",
-    "nq_rans_chunks", "nq_rans_decode",
+    "nq_rans_chunks", "nq_rans_decode", "nq_rans_encode_ws_bytes", "nq_rans_table", "nq_rans_encode",
     "nq_embed_symbols", "nq_embed_restore",
     "nq_rows_dot_ws_bytes", "nq_rows_dot", "nq_bit_search_ws_bytes", "nq_bit_search",
     "nq_conv3_levels_supported", "nq_conv_forward3_levels",

@@ -10,7 +10,8 @@ model's evaluation bit for bit.
 
 By default (`coding="packed"`) the file realises the NOMINAL size (bits x parameters).  `coding="rans"` / `"auto"` store the
 levels entropy coded instead (§12): a 64-lane interleaved rANS code with one frequency table per tensor, encoded here on the
-host (`rans_encode`) and decoded at open by a HIP kernel, one wavefront per chunk.  The weights a player rebuilds are the same
+host (`rans_encode`) or, with `encoder="gpu"`, by a HIP kernel (`ops.rans_encode`, §26: the same bytes), and decoded at open
+by a HIP kernel, one wavefront per chunk.  The weights a player rebuilds are the same
 floats either way.  Scales and soft biases are not coded.
 
 HNeRV's frame embeddings are fp32 by default.  `embedding_bits=` stores them as levels of 2..8 bits with one
@@ -33,6 +34,7 @@ MAGIC = b"NQV1"
 VERSION = 1
 _DTYPES = {"u16": "<u2", "u32": "<u4", "f16": "<f2", "f32": "<f4"}
 CODINGS = ("packed", "rans", "auto")
+ENCODERS = ("host", "gpu")   # who runs the rANS encoder: `rans_encode` below, or `ops.rans_encode` (HIP); same bytes
 # rANS constants (csrc/rans.hip holds the same three)
 RANS_PROB_BITS = 12
 RANS_M = 1 << RANS_PROB_BITS
@@ -51,6 +53,11 @@ def _align4(n):
 def _check_chunk(chunk, what):
     if not isinstance(chunk, int) or chunk <= 0 or chunk % RANS_LANES:
         raise ValueError(f"{what}: chunk must be a positive multiple of {RANS_LANES}, got {chunk!r}")
+
+
+def _check_encoder(encoder, what):
+    if encoder not in ENCODERS:
+        raise ValueError(f"{what}: encoder must be one of {ENCODERS}, got {encoder!r}")
 
 
 def _check_bits(bits, lo, hi, what):
@@ -320,8 +327,12 @@ def _packed_section(name, levels_u8, n_bits):
     return [(f"{name}.levels", "u32", ops.pack_levels(levels_u8, n_bits).cpu().numpy().view(np.uint32))]
 
 
-def _rans_sections(name, levels_u8, n_bits, chunk):
-    return [(f"{name}.{k}", tag, a) for (k, tag), a in zip(_RANS_PARTS, rans_encode(levels_u8.cpu().numpy(), n_bits, chunk))]
+def _rans_sections(name, levels_u8, n_bits, chunk, encoder="host"):
+    if encoder == "gpu":   # encoded where the levels are; the four sections come back as the unsigned types of the file
+        parts = [t.cpu().numpy().view(_DTYPES[tag]) for t, (_, tag) in zip(ops.rans_encode(levels_u8, int(n_bits), chunk), _RANS_PARTS)]
+    else:
+        parts = rans_encode(levels_u8.cpu().numpy(), n_bits, chunk)
+    return [(f"{name}.{k}", tag, a) for (k, tag), a in zip(_RANS_PARTS, parts)]
 
 
 def _section_bytes(sections):
@@ -380,13 +391,15 @@ _EMBED_KINDS = ("embedding_scales",) * 2 + ("embedding_levels",) + ("embedding_r
 
 
 @torch.no_grad()
-def encode_embeddings(x, bits, mode, chunk=DEFAULT_CHUNK):
+def encode_embeddings(x, bits, mode, chunk=DEFAULT_CHUNK, encoder="host"):
     """The embeddings x (fp32 tensor / list, or a QuantisedEmbeddings of the same `bits`) as one of EMBED_MODES would store
     them -> (the header's `embedding` entry, sections [(name, tag, array)]).  'packed': all N * E levels at their bit-width;
     'rans': frame 0's levels packed, the other frames' levels rANS coded; 'temporal': frame 0's levels packed, the
-    frame-to-frame differences modulo 2^bits rANS coded.  A single frame is always stored packed."""
+    frame-to-frame differences modulo 2^bits rANS coded.  A single frame is always stored packed.  encoder: one of ENCODERS,
+    who runs the rANS encoder; the sections are the same bytes."""
     if mode not in EMBED_MODES:
         raise ValueError(f"mode must be one of {EMBED_MODES}, got {mode!r}")
+    _check_encoder(encoder, "encode_embeddings")
     q = x if isinstance(x, QuantisedEmbeddings) else quantise_embeddings(x, bits)
     if q.bits != bits:
         raise ValueError(f"embeddings were quantised to {q.bits} bits, asked to store {bits}")
@@ -399,7 +412,7 @@ def encode_embeddings(x, bits, mode, chunk=DEFAULT_CHUNK):
     sections += _packed_section("embeddings", symbols if coding == "packed" else symbols[0], bits)
     if coding == "rans":
         entry["rans_chunk"] = chunk
-        sections += _rans_sections("embeddings", symbols[1:], bits, chunk)
+        sections += _rans_sections("embeddings", symbols[1:], bits, chunk, encoder)
     return entry, sections
 
 
@@ -414,10 +427,10 @@ def restore_embeddings(emb, device):
     return ops.embed_restore(sym, delta, zp, emb["shape"], emb["bits"], emb["temporal"])
 
 
-def _embedding_stream_sections(q, chunk, frames, device):
+def _embedding_stream_sections(q, chunk, frames, device, encoder="host"):
     """write_stream's part for quantised embeddings -> (entry, sections, {mode: bytes}): all three modes, the smallest kept and
     read back from the very arrays the file will hold by the player's own functions: q.restored must come out bit for bit."""
-    built = {m: encode_embeddings(q, q.bits, m, chunk) for m in EMBED_MODES}
+    built = {m: encode_embeddings(q, q.bits, m, chunk, encoder) for m in EMBED_MODES}
     sizes = {m: _section_bytes(s) for m, (_, s) in built.items()}
     entry, sections = built[smallest_embedding_mode(sizes)]
     header = dict(arch="hnerv", frames=frames, embedding_shape=list(q.shape), embedding=entry)
@@ -427,7 +440,7 @@ def _embedding_stream_sections(q, chunk, frames, device):
 
 
 # ------------------------------------------------------------------------------------------ writer
-def _layer_side(q, x, name, prefix, kind, coding, chunk):
+def _layer_side(q, x, name, prefix, kind, coding, chunk, encoder="host"):
     """One side of a layer, its weight (prefix '', kind 'weight') or its hard bias ('bias_', 'bias'): tensor x under quantiser q
     as level sections in the coding chosen, then two scale sections -> ([(kind in the size summary, section)], the layer
     entry's keys, entropy of the levels in bits).  The player's own host check and device decode read the level sections back
@@ -441,7 +454,7 @@ def _layer_side(q, x, name, prefix, kind, coding, chunk):
     levels = _levels(q, x)
     chosen, secs = "packed", _packed_section(name, levels, q.n_bits)
     if coding != "packed":
-        coded = _rans_sections(name, levels, q.n_bits, chunk)
+        coded = _rans_sections(name, levels, q.n_bits, chunk, encoder)
         if coding == "rans" or _section_bytes(coded) < _section_bytes(secs):
             chosen, secs = "rans", coded
     stored = _stored_levels(_as_stored(secs), name, x.numel(), int(q.n_bits), chosen, chunk, "write_stream")
@@ -467,7 +480,7 @@ def _check_decoder_shape(arch, cfg):
 
 @torch.no_grad()
 def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft", coding="packed", chunk=DEFAULT_CHUNK,
-                 embedding_bits=None):
+                 embedding_bits=None, encoder="host"):
     """Write the calibrated `qnn` to `path`.  embeddings: HNeRV's per-frame input embeddings (tensor (N, c, h, w) or the list
     `evaluate()` returned); NeRV stores none and needs `frames`.  bias: 'soft' stores the fp32 bias the evaluated model uses,
     'hard' its integer decision (export.py's module docstring).  coding: 'packed' stores every level tensor at its bit-width,
@@ -479,13 +492,17 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
     bits in whichever of EMBED_MODES takes the fewest bytes.  The frames such a file decodes to are those of the
     model on the RESTORED embeddings (summary['embedding_restored']).  A caller that evaluated the model on them passes the
     `QuantisedEmbeddings` it took them from as `embeddings` (quantising a restored tensor a second time derives other scales);
-    what is written is decoded again on the GPU and compared with exactly that tensor."""
+    what is written is decoded again on the GPU and compared with exactly that tensor.
+    encoder: 'host' (default) runs the rANS encoder in numpy on levels copied to the host, 'gpu' runs it in HIP on the device
+    (`ops.rans_encode`) for every weight, hard-bias and embedding tensor that is coded.  The file is the same
+    bytes either way, and so is every check made before it is written."""
     from .quantization.quant_layer import QuantModule
     from .quantization.quantizer import AdaRoundQuantizer
     if bias not in ("soft", "hard"):
         raise ValueError(f"bias must be 'soft' or 'hard', got {bias!r}")
     if coding not in CODINGS:
         raise ValueError(f"coding must be one of {CODINGS}, got {coding!r}")
+    _check_encoder(encoder, "write_stream")
     if coding != "packed":
         _check_chunk(chunk, "write_stream")
     _check_decoder_shape(arch, cfg)
@@ -521,7 +538,7 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
         lay = dict(shape=list(m.weight.shape), c_in_stored=int(src.shape[1]))
         sides = [(wq, src, f"w{i}", "", "weight")] + ([(bq, m.bias.data, f"b{i}", "bias_", "bias")] if bias == "hard" else [])
         for side in sides:
-            secs, entry, e = _layer_side(*side, coding, chunk)
+            secs, entry, e = _layer_side(*side, coding, chunk, encoder)
             sections += secs
             lay.update(entry)
             entropy_bits += e
@@ -536,7 +553,7 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
         if qemb is None:
             sections.append(("embeddings", ("embeddings", "f32", emb.cpu().numpy())))
         else:
-            header["embedding"], secs, emb_sizes = _embedding_stream_sections(qemb, chunk, int(frames), emb.device)
+            header["embedding"], secs, emb_sizes = _embedding_stream_sections(qemb, chunk, int(frames), emb.device, encoder)
             sections += zip(_EMBED_KINDS, secs)
     header, size = _write_container(path, header, [s for _, s in sections])
     kinds = {}

@@ -19,7 +19,8 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     then also logs the figure that objective is after;
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
-    packed at their bit-width and entropy-coded levels; --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
+    packed at their bit-width and entropy-coded levels, --stream_encoder host | gpu who encodes them (numpy, or the HIP encoder
+    of DESIGN.md §26: the same bytes); --embed_bits B (HNeRV) quantises the frame embeddings to B bits, calibrates
     and evaluates on the embeddings a player restores, and stores them as levels: DESIGN.md §17;
     --rate_lambda L (default 0: off) adds L * bits per pixel of the weight levels, priced by a static per-tensor model of the
     hard levels, to the phase-2 objective (ops.level_rate; the pixels are those of the frame cache), logs 'rate: ..' lines and,
@@ -83,6 +84,9 @@ def parse_args(argv):
                    help='write the calibrated model as a packed bit stream (.nqv, neuroquant_amd/bitstream.py) to this path')
     p.add_argument('--stream_coding', type=str, default='packed', choices=['packed', 'rans', 'auto'],
                    help='levels of --export_stream: packed at their bit-width, rANS coded, or whichever is smaller per tensor')
+    p.add_argument('--stream_encoder', type=str, default='host', choices=['host', 'gpu'],
+                   help='who runs the rANS encoder of --export_stream: numpy on the host, or the HIP encoder on the device '
+                        '(DESIGN.md §26); the file is the same bytes')
     p.add_argument('--embed_bits', type=int, default=None, choices=range(2, 9), metavar='2..8',
                    help='HNeRV: quantise the frame embeddings to this many bits (one scale per embedding channel); the calibration, '
                         'every evaluation after the FP one and --export_stream use the embeddings a player restores from the levels')
@@ -461,7 +465,7 @@ def calibrate(args, cfg):
             from ..bitstream import write_stream
             s = write_stream(qnn, args.export_stream, args.arch, cfg, frames=n,
                              embeddings=(qemb if qemb is not None else cali_data) if args.arch == 'hnerv' else None,
-                             coding=getattr(args, 'stream_coding', 'packed'))
+                             coding=getattr(args, 'stream_coding', 'packed'), encoder=getattr(args, 'stream_encoder', 'host'))
             logging.info('bit stream: {} ({} bytes, {} bpp; nominal {} bytes; coding {}: levels {} bytes, '
                          'gap to entropy {} bytes)'.format(
                              args.export_stream, s['file_bytes'], round(s.get('bpp', float('nan')), 5), s['total_bytes_nominal'],

@@ -2432,6 +2432,41 @@ def rans_decode_dequant(words, states, offsets, freq, delta: torch.Tensor, zp: t
     return w
 
 
+RANS_DEFAULT_CHUNK = 32768   # bitstream.DEFAULT_CHUNK
+
+
+def rans_encode(levels_u8: torch.Tensor, n_bits: int, chunk: int = RANS_DEFAULT_CHUNK):
+    """uint8 levels on the GPU (any shape, taken flat) -> (freq, states, offsets, words): the four sections of a coded tensor
+    as device tensors, bit for bit what `bitstream.rans_encode` gives for the same levels.  16-bit sections
+    come as int16 and 32-bit ones as int32, the bit patterns of the file's u16 / u32: what `rans_decode` takes.  `words` is cut
+    to the number of words, which costs one 4-byte read-back.  ValueError for what the host encoder refuses: no levels,
+    n_bits outside 1..8, a chunk that is not a positive multiple of 64, a level that does not fit n_bits bits."""
+    lv = _dev_as(levels_u8, torch.uint8, "levels").reshape(-1)
+    n = lv.numel()
+    if n == 0:
+        raise ValueError("rans_encode: no levels to code")
+    if not isinstance(n_bits, int) or isinstance(n_bits, bool) or not 1 <= n_bits <= 8:
+        raise ValueError(f"rans_encode: n_bits must be an integer in 1..8, got {n_bits!r}")
+    if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk <= 0 or chunk % 64:
+        raise ValueError(f"rans_encode: chunk must be a positive multiple of 64, got {chunk!r}")
+    if int(lv.max()) >= 1 << n_bits:
+        raise ValueError(f"rans_encode: level {int(lv.max())} does not fit {n_bits} bits")
+    lib, chunks = L.lib(), rans_chunks(n, chunk)
+    ws_bytes = int(lib.nq_rans_encode_ws_bytes(n, n_bits, chunk))
+    if ws_bytes <= 0:
+        raise ValueError(f"rans_encode: {n} levels are more than the 32-bit word offsets of a coded tensor can address")
+    dev = lv.device
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    freq = torch.empty(1 << n_bits, device=dev, dtype=torch.int16)
+    states = torch.empty(64 * chunks, device=dev, dtype=torch.int32)
+    offsets = torch.empty(chunks + 1, device=dev, dtype=torch.int32)
+    words = torch.empty(n, device=dev, dtype=torch.int16)
+    L.check(lib.nq_rans_table(_p(lv), n, n_bits, _p(freq), _p(ws), ws_bytes, _stream()), "rans_table")
+    L.check(lib.nq_rans_encode(_p(lv), n, n_bits, chunk, _p(freq), _p(states), _p(offsets), _p(words), _p(ws), ws_bytes,
+                               _stream()), "rans_encode")
+    return freq, states, offsets, words[:int(offsets[-1]) & 0xFFFFFFFF]
+
+
 # ------------------------------------------------------------------------------------------ quantised embeddings (DESIGN.md §17)
 def _embed_args(what, shape, delta, zp, n_bits, temporal):
     shape = tuple(int(s) for s in shape)

@@ -14,7 +14,13 @@ StreamDecoder open time of each file (host clock around read + validate + upload
 over --opens opens, the three files taking turns) and decode frames/s at B = 1 (host clock around 4 sweeps over all frames,
 median of 5 windows).  --parent FILE times the StreamDecoder of another copy of neuroquant_amd/bitstream.py (the parent
 commit's) on the packed file and on the first coded one (coding rans, chunk 4096) in the same run, taking turns with the
-current one.  Prints ONE JSON object and writes it to --out.  Needs the GPU."""
+current one.  Prints ONE JSON object and writes it to --out.  Needs the GPU.
+
+    python tools/bench_entropy.py --encoder [--out profiles/rans_encode.json] [--repeats 7] [--parent FILE]
+
+times the encoders instead, on the trained model only: `ops.rans_encode` against `bitstream.rans_encode` per
+tensor at chunk 4096 / 32768 / 262144, `write_stream` with encoder "gpu" and "host" for coding rans and auto, and the default
+packed export (with --parent: against the parent commit's bitstream.py, taking turns)."""
 import argparse
 import importlib.util
 import json
@@ -127,7 +133,102 @@ def measure(qnn, emb, opens, parent, tmp, tag):
     return res
 
 
+ENCODER_CHUNKS = [4096, 32768, 262144]
+
+
+def _host_ms(fn, repeats):
+    """ms per call of fn, host clock around work that ends synchronised; one untimed call first"""
+    fn()
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def write_stream_(qnn, path, cfg, emb, **kw):
+    from neuroquant_amd.bitstream import write_stream
+    return write_stream(qnn, path, "hnerv", cfg, embeddings=emb, **kw)
+
+
+def measure_encoders(qnn, emb, repeats, parent, tmp):
+    """--encoder: the HIP rANS encoder against the host one on the trained model's level tensors.  Per chunk and
+    tensor: ops.rans_encode (levels already on the device; includes its 4-byte read-back) against bitstream.rans_encode
+    including the copy of the levels to the host, the two taking turns; write_stream wall time with both encoders for coding
+    rans and auto; and the default packed export, against the parent commit's bitstream.py where --parent names one."""
+    from neuroquant_amd import bitstream, ops
+    from neuroquant_amd.export import _levels
+    mods = qnn.quant_modules()
+    tensors = [(_levels(m.weight_quantizer, m.hadamard_weight if m.hadamard else m.weight.data).reshape(-1).contiguous(),
+                int(m.weight_quantizer.n_bits)) for m in mods]
+    res = dict(levels=[int(t.numel()) for t, _ in tensors], bits=[b for _, b in tensors], repeats=repeats, chunks=[])
+    cfg = dict(HNERV_3M)
+    for chunk in ENCODER_CHUNKS:
+        row, tot = dict(chunk=chunk, tensors=[]), {"gpu": [0.0] * repeats, "host": [0.0] * repeats}
+        for i, (lv, b) in enumerate(tensors):
+            got = [t.cpu().numpy() for t in ops.rans_encode(lv, b, chunk)]
+            want = bitstream.rans_encode(lv.cpu().numpy(), b, chunk)
+            same = all(np.array_equal(g.view(w.dtype), w) for g, w in zip(got, want))
+            t = {"gpu": [], "host": []}
+            for _ in range(repeats + 1):                      # the two encoders take turns; the first round is the warm-up
+                t["gpu"].append(_host_ms(lambda: ops.rans_encode(lv, b, chunk), 1)[0])
+                t["host"].append(_host_ms(lambda: bitstream.rans_encode(lv.cpu().numpy(), b, chunk), 1)[0])
+            for k in tot:
+                tot[k] = [x + y for x, y in zip(tot[k], t[k][1:])]
+            row["tensors"].append(dict(tensor="w%d" % i, levels=int(lv.numel()), n_bits=b, words=int(want[3].size),
+                                       identical=bool(same), gpu_ms=stats(t["gpu"][1:]), host_ms=stats(t["host"][1:])))
+        row["total_gpu_ms"], row["total_host_ms"] = stats(tot["gpu"]), stats(tot["host"])
+        row["write_stream_ms"] = {}
+        for coding in ("rans", "auto"):
+            t = {"gpu": [], "host": []}
+            for _ in range(repeats + 1):
+                for enc in t:
+                    path = os.path.join(tmp, "enc_%s_%s_%d.nqv" % (coding, enc, chunk))
+                    t[enc].append(_host_ms(lambda: write_stream_(qnn, path, cfg, emb, coding=coding, chunk=chunk, encoder=enc), 1)[0])
+            same = open(os.path.join(tmp, "enc_%s_gpu_%d.nqv" % (coding, chunk)), "rb").read() == \
+                open(os.path.join(tmp, "enc_%s_host_%d.nqv" % (coding, chunk)), "rb").read()
+            row["write_stream_ms"][coding] = dict(gpu=stats(t["gpu"][1:]), host=stats(t["host"][1:]), files_identical=bool(same))
+        res["chunks"].append(row)
+    # the default export launches nothing new
+    writers = {"current": bitstream.write_stream}
+    if parent:
+        spec = importlib.util.spec_from_file_location("neuroquant_amd._bitstream_parent", parent)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        writers["parent"] = mod.write_stream
+    t = {k: [] for k in writers}
+    for _ in range(3 * repeats + 1):
+        for k, w in writers.items():
+            path = os.path.join(tmp, "packed_%s.nqv" % k)
+            t[k].append(_host_ms(lambda: w(qnn, path, "hnerv", cfg, embeddings=emb), 1)[0])
+    res["packed_write_stream_ms"] = {k: stats(v[1:]) for k, v in t.items()}
+    return res
+
+
 def main(argv):
+    if "--encoder" in argv:
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--encoder", action="store_true", help="time the HIP rANS encoder against the host one (DESIGN.md §26)")
+        ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rans_encode.json"))
+        ap.add_argument("--repeats", type=int, default=7)
+        ap.add_argument("--parent", default=None, help="the parent commit's neuroquant_amd/bitstream.py: its packed export is timed too")
+        a = ap.parse_args(argv)
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_entropy needs the GPU (nothing is measured without one)")
+        logging.getLogger().setLevel(logging.WARNING)
+        with tempfile.TemporaryDirectory() as tmp:
+            qnn, emb = build_trained(48)
+            res = dict(device=torch.cuda.get_device_name(0), model="HNeRV-3M 640x1280, tests/golden/hnerv3m_bunny8real_f16.npz, 48 "
+                       "calibration iterations", timing="host clock, synchronised before and after each call; ms; median / min / max",
+                       **measure_encoders(qnn, emb, a.repeats, a.parent, tmp))
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+        return
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "entropy.json"))
     ap.add_argument("--opens", type=int, default=15)
