@@ -865,6 +865,46 @@ NQ_API int64_t nq_level_rate_ws_words(int64_t n, int n_levels);
 NQ_API int nq_level_rate(const nq_rate_seg* segs, int nseg, float scale, const float* dyn, float* total, void* ws, int64_t ws_words,
                   nq_stream_t stream);
 
+/* ---- ConvNeXt encoder block of the trainer, forward and backward (additive: nq_abi_version() stays 7) ----
+ * THE definition: reference models/_layers.py Block.forward with gamma present.  x (N, C, H, W) fp32 NCHW, C a multiple of 8
+ * in 8 .. 64, any N, H, W >= 1; dw_w (C, 1, 7, 7), dw_b (C), ln_w (C), ln_b (C), w1 (4C, C), b1 (4C), w2 (C, 4C), b2 (C),
+ * gamma (C); everything in fp32, per pixel p = (n, h, w):
+ *   u[c]    = dw_b[c] + sum_{i,j < 7} x[n][c][h + i - 3][w + j - 3] dw_w[c][i][j]       zero outside the image
+ *   mu      = mean_c u,  var = mean_c (u - mu)^2,  rstd = 1 / sqrt(var + 1e-6),  xhat[c] = (u[c] - mu) rstd
+ *   a[c]    = xhat[c] ln_w[c] + ln_b[c]
+ *   h[j]    = b1[j] + sum_c w1[j][c] a[c]           j < 4C
+ *   m[c]    = b2[c] + sum_j w2[c][j] gelu(h[j])     gelu the exact-erf GELU of the conv epilogues
+ *   out[c]  = x[c] + gamma[c] m[c]
+ * Backward, for the upstream gradient dy (N, C, H, W), with g[c] = gamma[c] dy[c]:
+ *   d gamma[c] = sum_p dy[c] m[c]            d b2[c]   = sum_p g[c]             d w2[c][j] = sum_p g[c] gelu(h[j])
+ *   dh[j]      = (sum_c w2[c][j] g[c]) gelu'(h[j])     d b1[j] = sum_p dh[j]    d w1[j][c] = sum_p dh[j] a[c]
+ *   da[c]      = sum_j w1[j][c] dh[j]        d ln_w[c] = sum_p da[c] xhat[c]    d ln_b[c]  = sum_p da[c]
+ *   dxh[c]     = da[c] ln_w[c],  du[c] = rstd (dxh[c] - mean_c dxh - xhat[c] mean_c (dxh xhat))
+ *   d dw_b[c]  = sum_p du[c]                 d dw_w[c][i][j] = sum_p du[c] x[n][c][h + i - 3][w + j - 3]
+ *   dx[n][c][h][w] = dy + sum_{i,j} du[n][c][h - i + 3][w - j + 3] dw_w[c][i][j]
+ * The two pointwise products, their transposes and the three weight-gradient products (d w1, d w2, and m again for d gamma)
+ * run on the fp32 16x16x4 MFMA.  h never leaves the chip: the backward computes it again from what the forward saved, xhat
+ * (N, H, W, C: channels-last, the one tensor of x's size) and rstd (N, H, W).  No tensor is permuted in memory.
+ *
+ * nq_convnext_block_forward: two launches, writes out, xhat, rstd.  nq_convnext_block_backward: five launches, writes dx and the
+ * nine parameter gradients (overwritten, not accumulated); every parameter gradient is the sum, in double and in partial order,
+ * of per-workgroup (per-wave) partial sums in ws -- no atomics, bit-identical from call to call; nothing is allocated, no
+ * host read: capturable in a hipGraph.
+ *   ws: nq_convnext_block_ws_bytes(N, C, H, W) = 4 (P C + 4 G C + 4 S (8 C C + 4 C) + 50 T C) bytes with P = N H W pixels,
+ *       Q = ceil(ceil(P / 16) / 4), G = min(Q, 256), S = min(Q, 16), T = N ceil(H / 8) ceil(W / 32): du, the per-channel
+ *       partials, the d w1 | d w2 | d b1 partials and the depthwise partials.  0 for arguments the entries refuse.
+ * NQ_ERR_INVALID, before anything is launched, for C outside {8, 16, .., 64}, a non-positive N, H or W, a null or (tensors
+ * read as float4) misaligned pointer, ws_bytes below the query; NQ_ERR_UNSUPPORTED for N > 65535 or more than 2^31 - 1 tiles. */
+NQ_API int64_t nq_convnext_block_ws_bytes(int N, int C, int H, int W);
+NQ_API int nq_convnext_block_forward(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
+                              const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma, float* out,
+                              float* xhat, float* rstd, int N, int C, int H, int W, nq_stream_t stream);
+NQ_API int nq_convnext_block_backward(const float* dy, const float* x, const float* xhat, const float* rstd, const float* dw_w,
+                               const float* ln_w, const float* ln_b, const float* w1, const float* b1, const float* w2,
+                               const float* b2, const float* gamma, float* dx, float* d_dw_w, float* d_dw_b, float* d_ln_w,
+                               float* d_ln_b, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_gamma, void* ws,
+                               int64_t ws_bytes, int N, int C, int H, int W, nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

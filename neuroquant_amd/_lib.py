@@ -218,6 +218,9 @@ def _load():
     sig("nq_bit_search", I, P, P, I, I, ctypes.c_uint64, P, P, P, P)
     sig("nq_level_rate_ws_words", L, L, I)
     sig("nq_level_rate", I, POINTER(RateSeg), I, F, P, P, P, L, P)
+    sig("nq_convnext_block_ws_bytes", L, I, I, I, I)
+    sig("nq_convnext_block_forward", I, *[P] * 13, I, I, I, I, P)
+    sig("nq_convnext_block_backward", I, *[P] * 23, L, I, I, I, I, P)
     return lib
 
 
@@ -245,6 +248,7 @@ EXPORTS = (
     "nq_conv_forward_plan", "nq_conv_wgrad_plan",
     "nq_level_rate_ws_words", "nq_level_rate",
     "nq_scale_init_ws_bytes", "nq_scale_init_search", "nq_scale_init_gaussian",
+    "nq_convnext_block_ws_bytes", "nq_convnext_block_forward", "nq_convnext_block_backward",
 )
 
 _lib = None

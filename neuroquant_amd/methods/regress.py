@@ -4,7 +4,8 @@ Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hy
 objective.TABLE: `l2`, `yuv420`, the reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5`, or `msssim`, per-epoch
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
-from the GPU-resident cache; the ConvNeXt encoder and Adam stay in PyTorch.  Evaluations report PSNR and MS-SSIM
+from the GPU-resident cache; Adam and, by default, the ConvNeXt encoder stay in PyTorch (`--enc_kernels hip` runs the
+encoder's Blocks on csrc/convnext.hip).  Evaluations report PSNR and MS-SSIM
 (ops.ms_ssim); tensorboard is not produced.
 
     python -m neuroquant_amd.methods.regress --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny
@@ -42,6 +43,8 @@ def parse_args(argv):
     p.add_argument('--lr_type', type=str, default='cosine_0.1_1_0.1')
     p.add_argument('--weight', default='None', type=str)
     p.add_argument('--eval_only', action='store_true', default=False)
+    p.add_argument('--enc_kernels', choices=('torch', 'hip'), default='torch',
+                   help="what runs the HNeRV encoder's ConvNeXt blocks: PyTorch ops, or the HIP block of csrc/convnext.hip")
     return p.parse_args(argv)
 
 
@@ -108,6 +111,8 @@ def train(args, cfg):
     n = len(cache)
     train_ind, args.val_ind_list = data_split(list(range(n)), [int(x) for x in args.data_split.split('_')], False, 0)
     loader = CacheLoader(cache, train_ind, cfg['batch_size'], seed=args.seed)
+    if args.arch == 'hnerv':
+        cfg = dict(cfg, enc_kernels=getattr(args, 'enc_kernels', 'torch'))   # a flag, not a config line: the reference's YAML files stay usable
     model = (HNeRV if args.arch == 'hnerv' else NeRV)(cfg).to(device)
     os.makedirs(args.outf, exist_ok=True)
     setup_logger(os.path.join(args.outf, time.strftime('%Y%m%d_%H%M%S') + '.log'))

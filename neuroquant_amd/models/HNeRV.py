@@ -16,7 +16,7 @@ class HNeRV(nn.Module):
         self.fc_h = int(np.prod(cfg['enc_strides']) // np.prod(cfg['dec_strides']))
         self.fc_w = int(np.prod(cfg['enc_strides']) // np.prod(cfg['dec_strides']))
         self.encoder = ConvNeXt(stage_blocks=cfg['stage_block'], strds=cfg['enc_strides'], dims=cfg['enc_channel'],
-                                drop_path_rate=0)
+                                drop_path_rate=0, kernels=cfg.get('enc_kernels', 'torch'))
         in_channel = cfg['dec_in_channel']
         dec_layers = [nn.Conv2d(cfg['enc_channel'][-1], in_channel, 1, 1, 0)]
         for ks, stride in zip(cfg['dec_kernels'], cfg['dec_strides']):

@@ -2,7 +2,8 @@
 reference's checkpoints load unchanged (e.g. `decoder.3.conv.0.weight`, `encoder.stages.1.0.pwconv1.weight`).
 
 The decoder block is the hot path: once wrapped by QuantModel it runs on the fused HIP conv+PixelShuffle+GELU
-kernel.  The ConvNeXt encoder is a one-time precompute and stays plain PyTorch.
+kernel.  The ConvNeXt encoder is a one-time precompute for calibration and plain PyTorch by default (SURVEY.md §2 row 7);
+the trainer can put its Blocks on the HIP kernels of csrc/convnext.hip (`kernels='hip'`).
 """
 from math import ceil, pi
 
@@ -103,11 +104,17 @@ class LayerNorm(nn.Module):
         return self.weight[:, None, None] * x + self.bias[:, None, None]
 
 
+BLOCK_KERNELS = ('torch', 'hip')
+
+
 class Block(nn.Module):
     """ConvNeXt block: 7x7 depthwise conv -> LN -> 1x1 (4x) -> GELU -> 1x1 -> layer scale -> residual."""
 
-    def __init__(self, dim, drop_path=0., layer_scale_init_value=1e-6):
+    def __init__(self, dim, drop_path=0., layer_scale_init_value=1e-6, kernels='torch'):
         super().__init__()
+        if kernels not in BLOCK_KERNELS:
+            raise ValueError(f"Block kernels must be one of {BLOCK_KERNELS}, got {kernels!r}")
+        self.kernels = kernels
         self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
         self.norm = LayerNorm(dim, eps=1e-6)
         self.pwconv1 = nn.Linear(dim, 4 * dim)
@@ -118,8 +125,17 @@ class Block(nn.Module):
         if drop_path > 0.:
             raise NotImplementedError("stochastic depth is not used by the shipped configs (drop_path_rate=0)")
         self.drop_path = nn.Identity()
+        if kernels == 'hip':   # no silent fallback: a block the kernels cannot serve is refused here
+            from .. import ops
+            if dim not in ops.CONVNEXT_WIDTHS or self.gamma is None:
+                raise ValueError(f"Block(dim={dim}, kernels='hip'): the HIP block serves a multiple of 8 up to 64 channels "
+                                 "with layer scale")
 
     def forward(self, x):
+        if self.kernels == 'hip':
+            from .. import ops
+            return ops.convnext_block(x, self.dwconv.weight, self.dwconv.bias, self.norm.weight, self.norm.bias,
+                                      self.pwconv1.weight, self.pwconv1.bias, self.pwconv2.weight, self.pwconv2.bias, self.gamma)
         y = self.dwconv(x).permute(0, 2, 3, 1)
         y = self.pwconv2(self.act(self.pwconv1(self.norm(y))))
         if self.gamma is not None:
@@ -131,7 +147,7 @@ class ConvNeXt(nn.Module):
     """HNeRV frame encoder (reference _layers.py:134-193): per stage a strided patchify conv + `stage_blocks` Blocks."""
 
     def __init__(self, stage_blocks=0, strds=[2, 2, 2, 2], dims=[96, 192, 384, 768], in_chans=3, drop_path_rate=0.,
-                 layer_scale_init_value=1e-6):
+                 layer_scale_init_value=1e-6, kernels='torch'):
         super().__init__()
         self.downsample_layers = nn.ModuleList()
         self.stages = nn.ModuleList()
@@ -144,7 +160,7 @@ class ConvNeXt(nn.Module):
                 down = nn.Sequential(nn.Conv2d(in_chans, dims[0], kernel_size=strds[i], stride=strds[i]),
                                      LayerNorm(dims[0], eps=1e-6, data_format="channels_first"))
             self.downsample_layers.append(down)
-            self.stages.append(nn.Sequential(*[Block(dim=dims[i], layer_scale_init_value=layer_scale_init_value)
+            self.stages.append(nn.Sequential(*[Block(dim=dims[i], layer_scale_init_value=layer_scale_init_value, kernels=kernels)
                                                for _ in range(stage_blocks)]))
         self.apply(self._init_weights)
 

@@ -2541,3 +2541,77 @@ def bit_search(G: torch.Tensor, size_bits: torch.Tensor, budget_bits: int):
             "bit_search")
     ix = int(index) & 0xFFFFFFFFFFFFFFFF
     return float(omega), (None if ix == 0xFFFFFFFFFFFFFFFF else ix)
+
+
+# ------------------------------------------------------------------------------------------ ConvNeXt encoder block
+CONVNEXT_WIDTHS = tuple(range(8, 65, 8))    # the channel counts csrc/convnext.hip is built for
+_CONVNEXT_PARAMS = ("dw_w", "dw_b", "ln_w", "ln_b", "w1", "b1", "w2", "b2", "gamma")
+
+
+def convnext_block_args(what, x, dw_w, dw_b, ln_w, ln_b, w1, b1, w2, b2, gamma):
+    """-> (N, C, H, W); ValueError naming `what` and the argument, before anything is launched and without a GPU, unless x is an
+    fp32 (N, C, H, W) tensor with C in CONVNEXT_WIDTHS and the nine parameters are fp32 tensors of the Block's shapes"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError(f"{what}: x must be an (N, C, H, W) tensor, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    N, C, H, W = x.shape
+    if C not in CONVNEXT_WIDTHS:
+        raise ValueError(f"{what}: x has C = {C} channels, the kernels serve a multiple of 8 up to 64")
+    shapes = dict(dw_w=(C, 1, 7, 7), dw_b=(C,), ln_w=(C,), ln_b=(C,), w1=(4 * C, C), b1=(4 * C,), w2=(C, 4 * C), b2=(C,), gamma=(C,))
+    for name, t in zip(("x",) + _CONVNEXT_PARAMS, (x, dw_w, dw_b, ln_w, ln_b, w1, b1, w2, b2, gamma)):
+        if t is None:
+            raise ValueError(f"{what}: {name} is missing (a block without layer scale is not built)")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if name != "x" and tuple(t.shape) != shapes[name]:
+            raise ValueError(f"{what}: {name} must be {shapes[name]} for C = {C}, got {tuple(t.shape)}")
+    return N, C, H, W
+
+
+def convnext_block_raw(x, *params):
+    """One nq_convnext_block_forward call -> (out, xhat, rstd): xhat (N, H, W, C) and rstd (N, H, W) are what the backward reads"""
+    N, C, H, W = convnext_block_args("convnext_block", x, *params)
+    x = _dev(x.detach(), "x")
+    params = [_dev(t.detach(), n) for n, t in zip(_CONVNEXT_PARAMS, params)]
+    out = torch.empty_like(x)
+    xhat = torch.empty((N, H, W, C), device=x.device, dtype=torch.float32)
+    rstd = torch.empty((N, H, W), device=x.device, dtype=torch.float32)
+    L.check(_timed("convnext_fwd", lambda: L.lib().nq_convnext_block_forward(
+        _p(x), *[_p(t) for t in params], _p(out), _p(xhat), _p(rstd), N, C, H, W, _stream())), "convnext_block_forward")
+    return out, xhat, rstd
+
+
+def convnext_block_backward_raw(dy, x, xhat, rstd, *params):
+    """One nq_convnext_block_backward call -> (dx, d dw_w, d dw_b, d ln_w, d ln_b, d w1, d b1, d w2, d b2, d gamma)"""
+    N, C, H, W = x.shape
+    dy = _dev(dy.detach(), "dy")
+    dw_w, dw_b, ln_w, ln_b, w1, b1, w2, b2, gamma = params
+    grads = [torch.empty_like(t) for t in (x,) + tuple(params)]
+    ws_bytes = _q("nq_convnext_block_ws_bytes", N, C, H, W)
+    ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32)
+    L.check(_timed("convnext_bwd", lambda: L.lib().nq_convnext_block_backward(
+        _p(dy), _p(x), _p(xhat), _p(rstd), _p(dw_w), _p(ln_w), _p(ln_b), _p(w1), _p(b1), _p(w2), _p(b2), _p(gamma),
+        *[_p(g) for g in grads], _p(ws), ws_bytes, N, C, H, W, _stream())), "convnext_block_backward")
+    return tuple(grads)
+
+
+class _ConvNeXtBlockFn(Function):
+    @staticmethod
+    def forward(ctx, x, *params):
+        out, xhat, rstd = convnext_block_raw(x, *params)
+        ctx.save_for_backward(_dev(x.detach(), "x"), xhat, rstd, *[_dev(t.detach(), "parameter") for t in params])
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        if torch.is_grad_enabled():    # a backward under create_graph=True
+            raise NotImplementedError("the second derivative of convnext_block is not built")
+        x, xhat, rstd, *params = ctx.saved_tensors
+        return convnext_block_backward_raw(dy, x, xhat, rstd, *params)
+
+
+def convnext_block(x, dw_w, dw_b, ln_w, ln_b, w1, b1, w2, b2, gamma):
+    """The ConvNeXt Block of the HNeRV encoder (models/_layers.py Block.forward with its layer scale; the definition is in
+    include/nq_hip.h: nq_convnext_block_forward) on the HIP kernels of csrc/convnext.hip, differentiable once in all ten
+    arguments.  x: (N, C, H, W) fp32, C a multiple of 8 up to 64; dw_w (C, 1, 7, 7), w1 (4C, C), w2 (C, 4C) as the module's
+    dwconv / pwconv1 / pwconv2 weights.  Bit-identical from call to call."""
+    return _ConvNeXtBlockFn.apply(x, dw_w, dw_b, ln_w, ln_b, w1, b1, w2, b2, gamma)
