@@ -905,6 +905,49 @@ NQ_API int nq_convnext_block_backward(const float* dy, const float* x, const flo
                                float* d_ln_b, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_gamma, void* ws,
                                int64_t ws_bytes, int N, int C, int H, int W, nq_stream_t stream);
 
+/* ---- HNeRV encoder stages: patchify convolution + channels-first LayerNorm, forward and backward (additive:
+ * nq_abi_version() stays 7) ----
+ * THE definition: reference models/_layers.py ConvNeXt.downsample_layers[i].  x (N, Cin, H, W) fp32 NCHW; everything in fp32.
+ *   LNcf(t)[n][c][h][w] = (t - mu) rstd ln_w[c] + ln_b[c],  mu = mean_c t[n][:][h][w],  var = mean_c (t - mu)^2 (biased),
+ *                         rstd = 1 / sqrt(var + 1e-6)
+ *   conv(t)[n][o][ho][wo] = conv_b[o] + sum_{c, i < s, j < s} conv_w[o][c][i][j] t[n][c][s ho + i][s wo + j]
+ *                         (F.conv2d(t, conv_w, conv_b, stride = s), conv_w (Cout, Cin, s, s), no padding): Ho = floor(H / s),
+ *                         Wo = floor(W / s); rows and columns of t past s Ho and s Wo are not read, their gradient is exactly 0
+ *   order NQ_PATCHIFY_POST (stage 0):   out = LNcf(conv(x)),  ln_w, ln_b of width Cout;  mu, rstd (N, Ho, Wo): of conv(x)
+ *   order NQ_PATCHIFY_PRE  (stages 1..): out = conv(LNcf(x)),  ln_w, ln_b of width Cin;   mu, rstd (N, H, W):   of x
+ * out (N, Cout, Ho, Wo).  Backward, for the upstream gradient dy of out's shape, with that = (t - mu) rstd of the normalised
+ * tensor t and the LayerNorm algebra of the Block (above):
+ *   LNcf:  d ln_w[c] = sum_pixels dv[c] that[c],  d ln_b[c] = sum_pixels dv[c],  dvh = dv ln_w,
+ *          dt[c] = rstd (dvh[c] - mean_c dvh - that[c] mean_c (dvh that))            for the gradient dv of LNcf's output
+ *   conv:  d conv_w[o][c][i][j] = sum_p g[o][p] t[c][s ho + i][s wo + j],  d conv_b[o] = sum_p g[o][p],
+ *          dt[c][s ho + i][s wo + j] = sum_o conv_w[o][c][i][j] g[o][p]              for the gradient g of conv's output
+ * Served: s in 2 .. 5; Cout a multiple of 8 in 8 .. 64; Cin 3 or a multiple of 8 in 8 .. 64 (PRE: the multiple of 8); N >= 1;
+ * H, W >= s; x and out below 2^31 elements.  Everything else is NQ_ERR_INVALID before anything is launched.
+ *
+ * All three products (forward, data gradient, weight gradient) run on the fp32 16x16x4 MFMA; the normalised tensor of PRE never
+ * reaches memory (normalised on the operand load, forward and backward), POST recomputes conv(x) in the backward from x, mu, rstd.
+ * nq_patchify_ln_forward: one launch (POST) or two (PRE: statistics, product); writes out, mu, rstd.
+ * nq_patchify_ln_backward: three launches (PRE; POST without dx) or four (POST with dx); writes dx (nullable: no data gradient
+ * is computed) and the four parameter gradients (overwritten); every parameter gradient is the sum, in double and in partial
+ * order, of per-workgroup (per-wave) partial sums in ws -- no atomics, bit-identical from call to call, nothing is allocated, no
+ * host read: capturable in a hipGraph.
+ *   ws: nq_patchify_ln_ws_bytes(N, Cin, H, W, Cout, s, order) = 4 (A + 2 G L + 4 S Cout (K + 1)) bytes with K = Cin s s,
+ *       P = N Ho Wo, T = ceil(P / 16) tiles;
+ *       POST: A = P Cout (dL/d conv(x)), L = Cout, G = min(T if T < 1024 and Cin >= 16 else ceil(T / 4), 256);
+ *       PRE:  A = 0, L = Cin, G = min(ceil(T s / 4), 256);
+ *       S = min(ceil(T / 4), 32, max(1, floor(2^19 / (Cout (K + 1))))).  0 for arguments the entries refuse.
+ * NQ_ERR_INVALID also for a null or not 16-byte aligned pointer (dx may be null) and ws_bytes below the query. */
+#define NQ_PATCHIFY_POST 0
+#define NQ_PATCHIFY_PRE 1
+NQ_API int64_t nq_patchify_ln_ws_bytes(int N, int Cin, int H, int W, int Cout, int s, int order);
+NQ_API int nq_patchify_ln_forward(const float* x, const float* conv_w, const float* conv_b, const float* ln_w, const float* ln_b,
+                           float* out, float* mu, float* rstd, int N, int Cin, int H, int W, int Cout, int s, int order,
+                           nq_stream_t stream);
+NQ_API int nq_patchify_ln_backward(const float* dy, const float* x, const float* mu, const float* rstd, const float* conv_w,
+                            const float* conv_b, const float* ln_w, const float* ln_b, float* dx /* nullable */, float* d_conv_w,
+                            float* d_conv_b, float* d_ln_w, float* d_ln_b, void* ws, int64_t ws_bytes, int N, int Cin, int H, int W,
+                            int Cout, int s, int order, nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,9 @@ def _load():
     sig("nq_convnext_block_ws_bytes", L, I, I, I, I)
     sig("nq_convnext_block_forward", I, *[P] * 13, I, I, I, I, P)
     sig("nq_convnext_block_backward", I, *[P] * 23, L, I, I, I, I, P)
+    sig("nq_patchify_ln_ws_bytes", L, I, I, I, I, I, I, I)
+    sig("nq_patchify_ln_forward", I, *[P] * 8, I, I, I, I, I, I, I, P)
+    sig("nq_patchify_ln_backward", I, *[P] * 14, L, I, I, I, I, I, I, I, P)
     return lib
 
 
@@ -249,6 +252,7 @@ EXPORTS = (
     "nq_level_rate_ws_words", "nq_level_rate",
     "nq_scale_init_ws_bytes", "nq_scale_init_search", "nq_scale_init_gaussian",
     "nq_convnext_block_ws_bytes", "nq_convnext_block_forward", "nq_convnext_block_backward",
+    "nq_patchify_ln_ws_bytes", "nq_patchify_ln_forward", "nq_patchify_ln_backward",
 )
 
 _lib = None

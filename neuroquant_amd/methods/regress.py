@@ -5,7 +5,8 @@ objective.TABLE: `l2`, `yuv420`, the reference's `ssim` / `Fusi
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
 from the GPU-resident cache; Adam and, by default, the ConvNeXt encoder stay in PyTorch (`--enc_kernels hip` runs the
-encoder's Blocks on csrc/convnext.hip).  Evaluations report PSNR and MS-SSIM
+encoder's Blocks on csrc/convnext.hip; `--enc_kernels hip_all` also its downsampling stages, patchify conv +
+channels-first LayerNorm, on csrc/patchify.hip).  Evaluations report PSNR and MS-SSIM
 (ops.ms_ssim); tensorboard is not produced.
 
     python -m neuroquant_amd.methods.regress --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny
@@ -43,8 +44,9 @@ def parse_args(argv):
     p.add_argument('--lr_type', type=str, default='cosine_0.1_1_0.1')
     p.add_argument('--weight', default='None', type=str)
     p.add_argument('--eval_only', action='store_true', default=False)
-    p.add_argument('--enc_kernels', choices=('torch', 'hip'), default='torch',
-                   help="what runs the HNeRV encoder's ConvNeXt blocks: PyTorch ops, or the HIP block of csrc/convnext.hip")
+    p.add_argument('--enc_kernels', choices=('torch', 'hip', 'hip_all'), default='torch',
+                   help="what runs the HNeRV encoder: PyTorch ops; 'hip': its ConvNeXt blocks on csrc/convnext.hip; 'hip_all': "
+                        "the blocks and the downsampling stages (csrc/patchify.hip)")
     return p.parse_args(argv)
 
 

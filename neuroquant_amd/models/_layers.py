@@ -3,7 +3,8 @@ reference's checkpoints load unchanged (e.g. `decoder.3.conv.0.weight`, `encoder
 
 The decoder block is the hot path: once wrapped by QuantModel it runs on the fused HIP conv+PixelShuffle+GELU
 kernel.  The ConvNeXt encoder is a one-time precompute for calibration and plain PyTorch by default (SURVEY.md §2 row 7);
-the trainer can put its Blocks on the HIP kernels of csrc/convnext.hip (`kernels='hip'`).
+the trainer can put its Blocks on the HIP kernels of csrc/convnext.hip (`kernels='hip'`) and, with
+`kernels='hip_all'`, its downsampling stages on those of csrc/patchify.hip as well.
 """
 from math import ceil, pi
 
@@ -143,25 +144,57 @@ class Block(nn.Module):
         return x + y.permute(0, 3, 1, 2)
 
 
+class Downsample(nn.Sequential):
+    """A downsampling stage of the encoder: the reference's nn.Sequential of a stride-s patchify conv and a channels-first
+    LayerNorm -- conv at index 0 and LayerNorm at index 1 (`order='post'`, stage 0) or the other way round (`order='pre'`) --
+    so parameter names and checkpoints are the reference's.  `kernels='hip'` forwards through ops.patchify_ln
+    (csrc/patchify.hip); a shape those kernels do not serve is refused here, there is no fallback."""
+
+    def __init__(self, in_channel, out_channel, stride, order, kernels='torch'):
+        if kernels not in BLOCK_KERNELS:
+            raise ValueError(f"Downsample kernels must be one of {BLOCK_KERNELS}, got {kernels!r}")
+        conv = nn.Conv2d(in_channel, out_channel, kernel_size=stride, stride=stride)
+        norm = LayerNorm(out_channel if order == 'post' else in_channel, eps=1e-6, data_format="channels_first")
+        super().__init__(*((conv, norm) if order == 'post' else (norm, conv)))
+        self.order, self.kernels = order, kernels
+        if kernels == 'hip':
+            from .. import ops
+            ops.patchify_ln_shape(f"Downsample({in_channel}, {out_channel}, stride={stride}, kernels='hip')", in_channel,
+                                  out_channel, stride, order)
+
+    def forward(self, x):
+        if self.kernels != 'hip':
+            return super().forward(x)
+        from .. import ops
+        conv, norm = (self[0], self[1]) if self.order == 'post' else (self[1], self[0])
+        return ops.patchify_ln(x, conv.weight, conv.bias, norm.weight, norm.bias, self.order)
+
+
+ENCODER_KERNELS = ('torch', 'hip', 'hip_all')   # PyTorch ops | Blocks in HIP | Blocks and downsampling stages in HIP
+
+
 class ConvNeXt(nn.Module):
-    """HNeRV frame encoder (reference _layers.py:134-193): per stage a strided patchify conv + `stage_blocks` Blocks."""
+    """HNeRV frame encoder (reference _layers.py:134-193): per stage a strided patchify conv + `stage_blocks` Blocks.
+    `kernels`: 'torch', 'hip' (the Blocks on csrc/convnext.hip) or 'hip_all' (and the stages on csrc/patchify.hip)."""
 
     def __init__(self, stage_blocks=0, strds=[2, 2, 2, 2], dims=[96, 192, 384, 768], in_chans=3, drop_path_rate=0.,
                  layer_scale_init_value=1e-6, kernels='torch'):
         super().__init__()
+        if kernels not in ENCODER_KERNELS:
+            raise ValueError(f"ConvNeXt kernels must be one of {ENCODER_KERNELS}, got {kernels!r}")
+        block_kernels = 'torch' if kernels == 'torch' else 'hip'
+        down_kernels = 'hip' if kernels == 'hip_all' else 'torch'
         self.downsample_layers = nn.ModuleList()
         self.stages = nn.ModuleList()
         self.stage_num = len(dims)
         for i in range(self.stage_num):
             if i > 0:
-                down = nn.Sequential(LayerNorm(dims[i - 1], eps=1e-6, data_format="channels_first"),
-                                     nn.Conv2d(dims[i - 1], dims[i], kernel_size=strds[i], stride=strds[i]))
+                down = Downsample(dims[i - 1], dims[i], strds[i], 'pre', kernels=down_kernels)
             else:
-                down = nn.Sequential(nn.Conv2d(in_chans, dims[0], kernel_size=strds[i], stride=strds[i]),
-                                     LayerNorm(dims[0], eps=1e-6, data_format="channels_first"))
+                down = Downsample(in_chans, dims[0], strds[i], 'post', kernels=down_kernels)
             self.downsample_layers.append(down)
-            self.stages.append(nn.Sequential(*[Block(dim=dims[i], layer_scale_init_value=layer_scale_init_value, kernels=kernels)
-                                               for _ in range(stage_blocks)]))
+            self.stages.append(nn.Sequential(*[Block(dim=dims[i], layer_scale_init_value=layer_scale_init_value,
+                                                     kernels=block_kernels) for _ in range(stage_blocks)]))
         self.apply(self._init_weights)
 
     @staticmethod

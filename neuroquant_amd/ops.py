@@ -2615,3 +2615,105 @@ def convnext_block(x, dw_w, dw_b, ln_w, ln_b, w1, b1, w2, b2, gamma):
     arguments.  x: (N, C, H, W) fp32, C a multiple of 8 up to 64; dw_w (C, 1, 7, 7), w1 (4C, C), w2 (C, 4C) as the module's
     dwconv / pwconv1 / pwconv2 weights.  Bit-identical from call to call."""
     return _ConvNeXtBlockFn.apply(x, dw_w, dw_b, ln_w, ln_b, w1, b1, w2, b2, gamma)
+
+
+# ------------------------------------------------------------------------------------------ encoder stages (DESIGN.md §28)
+PATCHIFY_STRIDES = (2, 3, 4, 5)             # the strides (= kernel sizes) csrc/patchify.hip is built for
+PATCHIFY_ORDERS = {"post": 0, "pre": 1}     # NQ_PATCHIFY_POST: LNcf(conv(x)), NQ_PATCHIFY_PRE: conv(LNcf(x))
+_PATCHIFY_PARAMS = ("conv_w", "conv_b", "ln_w", "ln_b")
+
+
+def patchify_ln_shape(what, Cin, Cout, s, order):
+    """ValueError naming `what` and the argument unless csrc/patchify.hip serves a stride-s patchify convolution Cin -> Cout
+    fused with the channels-first LayerNorm before ('pre') or after ('post') it; what a module checks at construction"""
+    if order not in PATCHIFY_ORDERS:
+        raise ValueError(f"{what}: order must be one of {tuple(PATCHIFY_ORDERS)}, got {order!r}")
+    if s not in PATCHIFY_STRIDES:
+        raise ValueError(f"{what}: conv_w has kernel size / stride s = {s}, the kernels serve {PATCHIFY_STRIDES}")
+    if Cout not in CONVNEXT_WIDTHS:
+        raise ValueError(f"{what}: conv_w has C_out = {Cout} channels, the kernels serve a multiple of 8 up to 64")
+    if Cin not in CONVNEXT_WIDTHS and not (Cin == 3 and order == "post"):
+        raise ValueError(f"{what}: x has C_in = {Cin} channels, the kernels serve a multiple of 8 up to 64"
+                         + (" and 3" if order == "post" else " ('pre' normalises over C_in)"))
+
+
+def patchify_ln_args(what, x, conv_w, conv_b, ln_w, ln_b, order):
+    """-> (N, Cin, H, W, Cout, s); ValueError naming `what` and the argument, before anything is launched and without a GPU,
+    unless x is an fp32 (N, Cin, H, W) tensor, conv_w an fp32 (Cout, Cin, s, s) one, the shape is served (patchify_ln_shape),
+    H, W >= s and conv_b (Cout), ln_w, ln_b (Cout for 'post', Cin for 'pre') are fp32 tensors of those shapes"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError(f"{what}: x must be an (N, C, H, W) tensor, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    N, Cin, H, W = x.shape
+    if not isinstance(conv_w, torch.Tensor) or conv_w.dim() != 4 or conv_w.shape[1] != Cin or conv_w.shape[2] != conv_w.shape[3]:
+        raise ValueError(f"{what}: conv_w must be (C_out, {Cin}, s, s) for x of {Cin} channels, got "
+                         f"{tuple(conv_w.shape) if isinstance(conv_w, torch.Tensor) else type(conv_w)}")
+    Cout, s = conv_w.shape[0], conv_w.shape[2]
+    patchify_ln_shape(what, Cin, Cout, s, order)
+    if H < s or W < s:
+        raise ValueError(f"{what}: x is {H} x {W}, smaller than one {s} x {s} patch")
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"{what}: x has {x.numel()} elements, the kernels index below 2^31")
+    Cl = Cout if order == "post" else Cin
+    shapes = dict(conv_w=(Cout, Cin, s, s), conv_b=(Cout,), ln_w=(Cl,), ln_b=(Cl,))
+    for name, t in zip(("x",) + _PATCHIFY_PARAMS, (x, conv_w, conv_b, ln_w, ln_b)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if name != "x" and tuple(t.shape) != shapes[name]:
+            raise ValueError(f"{what}: {name} must be {shapes[name]} for order {order!r}, got {tuple(t.shape)}")
+    return N, Cin, H, W, Cout, s
+
+
+def patchify_ln_raw(x, conv_w, conv_b, ln_w, ln_b, order):
+    """One nq_patchify_ln_forward call -> (out, mu, rstd): the LayerNorm statistics, per output pixel ('post': of conv(x)) or
+    per input pixel ('pre': of x), are what the backward reads next to x"""
+    N, Cin, H, W, Cout, s = patchify_ln_args("patchify_ln", x, conv_w, conv_b, ln_w, ln_b, order)
+    x = _dev(x.detach(), "x")
+    params = [_dev(t.detach(), n) for n, t in zip(_PATCHIFY_PARAMS, (conv_w, conv_b, ln_w, ln_b))]
+    out = torch.empty((N, Cout, H // s, W // s), device=x.device, dtype=torch.float32)
+    mu = torch.empty((N, H // s, W // s) if order == "post" else (N, H, W), device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mu)
+    L.check(_timed("patchify_fwd", lambda: L.lib().nq_patchify_ln_forward(
+        _p(x), *[_p(t) for t in params], _p(out), _p(mu), _p(rstd), N, Cin, H, W, Cout, s, PATCHIFY_ORDERS[order], _stream())),
+        "patchify_ln_forward")
+    return out, mu, rstd
+
+
+def patchify_ln_backward_raw(dy, x, mu, rstd, conv_w, conv_b, ln_w, ln_b, order, need_dx=True):
+    """One nq_patchify_ln_backward call -> (dx or None, d conv_w, d conv_b, d ln_w, d ln_b)"""
+    N, Cin, H, W = x.shape
+    Cout, s = conv_w.shape[0], conv_w.shape[2]
+    dy = _dev(dy.detach(), "dy")
+    dx = torch.empty_like(x) if need_dx else None
+    grads = [torch.empty_like(t) for t in (conv_w, conv_b, ln_w, ln_b)]
+    ws_bytes = _q("nq_patchify_ln_ws_bytes", N, Cin, H, W, Cout, s, PATCHIFY_ORDERS[order])
+    ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32)
+    L.check(_timed("patchify_bwd", lambda: L.lib().nq_patchify_ln_backward(
+        _p(dy), _p(x), _p(mu), _p(rstd), _p(conv_w), _p(conv_b), _p(ln_w), _p(ln_b), _p(dx), *[_p(g) for g in grads], _p(ws),
+        ws_bytes, N, Cin, H, W, Cout, s, PATCHIFY_ORDERS[order], _stream())), "patchify_ln_backward")
+    return (dx, *grads)
+
+
+class _PatchifyLnFn(Function):
+    @staticmethod
+    def forward(ctx, x, conv_w, conv_b, ln_w, ln_b, order):
+        out, mu, rstd = patchify_ln_raw(x, conv_w, conv_b, ln_w, ln_b, order)
+        ctx.order = order
+        ctx.save_for_backward(_dev(x.detach(), "x"), mu, rstd, *[_dev(t.detach(), "parameter") for t in (conv_w, conv_b, ln_w, ln_b)])
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        if torch.is_grad_enabled():    # a backward under create_graph=True
+            raise NotImplementedError("the second derivative of patchify_ln is not built")
+        x, mu, rstd, *params = ctx.saved_tensors
+        return (*patchify_ln_backward_raw(dy, x, mu, rstd, *params, ctx.order, need_dx=ctx.needs_input_grad[0]), None)
+
+
+def patchify_ln(x, conv_w, conv_b, ln_w, ln_b, order):
+    """A downsampling stage of the HNeRV encoder (models/_layers.py ConvNeXt.downsample_layers; the definition is in
+    include/nq_hip.h: nq_patchify_ln_forward) on the HIP kernels of csrc/patchify.hip, differentiable once in its five tensors:
+    order 'post' -> LNcf(conv(x)) (stage 0), 'pre' -> conv(LNcf(x)) (stages 1 ...), conv = F.conv2d(stride = kernel = s) and
+    LNcf the channels-first LayerNorm (eps 1e-6).  x: (N, Cin, H, W) fp32; conv_w (Cout, Cin, s, s), s in 2 .. 5, Cout a
+    multiple of 8 up to 64, Cin likewise or ('post') 3.  The data gradient is computed only if x requires one.  Bit-identical
+    from call to call."""
+    return _PatchifyLnFn.apply(x, conv_w, conv_b, ln_w, ln_b, order)
