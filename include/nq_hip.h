@@ -948,6 +948,47 @@ NQ_API int nq_patchify_ln_backward(const float* dy, const float* x, const float*
                             float* d_conv_b, float* d_ln_w, float* d_ln_b, void* ws, int64_t ws_bytes, int N, int Cin, int H, int W,
                             int Cout, int s, int order, nq_stream_t stream);
 
+/* ---- QAT baselines: QATQuantizer 'ffnerv' and 'hinerv' on all weight tensors of a decoder in one call (csrc/qat.hip, DESIGN.md
+ * §29; additive: nq_abi_version() stays 7) ----
+ * THE definition: reference quantization/quantizer.py:326-375 with qfn (:17-28) and _quantize_ste (:9-14), as autograd
+ * differentiates them.  w (Cout, Cin, k, k) fp32 is Cout rows of K = Cin k k columns (the reference reduces over axis 0: a column
+ * is all elements that share (ci, kh, kw)); b = bits in 2 .. 8; e = i K + c the flat index of element (i, c); g the gradient of
+ * the loss with respect to the output.  All fp32, uncontracted, IEEE division, round-half-even, unless marked double.
+ *   NQ_QAT_FFNERV:  t = tanh(w), n = 2^(b-1) - 1, y = (floor(|t| n) / n) sign(t);     dw = g (1 - t^2)   (qfn is straight-through)
+ *   NQ_QAT_HINERV:  R = 2^b - 1, s_c = (2 max_i |w_ic|) / R + 1e-6, a(c) = the LOWEST row i with |w_ic| = max_i |w_ic|,
+ *                   q_ic = clamp(rint(w_ic / s_c), -2^(b-1), 2^(b-1) - 1), wq_ic = q_ic s_c,
+ *                   noise != 0: y = w m + wq (1 - m), m_ic in {0, 1};   noise == 0: y = wq (m = 0 below)
+ *                   dw_ic = g_ic m_ic + [i = a(c)] (float)(sign(w_ic) (2 / R) S_c),  S_c = sum_j g_jc (1 - m_jc) q_jc  [double,
+ *                   rows ascending within a sixteenth (rounded up) of the rows, the sixteenths in order]: q is detached in the reference, so
+ *                   the quantised part reaches w through the scale only; a column whose maximum is 0 has sign 0, no scale gradient.
+ *   mask:           Philox-4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), counter
+ *                   {e >> 2, 0, index, *step}, key {seed & 0xffffffff, seed >> 32}; element e takes output word e & 3;
+ *                   m = 1 iff (float)(word >> 8) * 2^-24 > 0.9f.  A function of (seed, step, index, e) and of nothing else.
+ * Weights are finite (a NaN is never a maximum).  nq_qat_seg: one tensor -- w, out (forward: y; backward: dw; may alias nothing
+ * else) and, for the backward, g; 4-byte aligned (16-byte aligned tensors take 16-byte accesses); Cout K < 2^31; index >= 0.
+ * step: device int32 scalar, read by the kernels (a captured call replays with the value then in memory); needed only for
+ * NQ_QAT_HINERV with noise != 0.  ws: NQ_QAT_HINERV only, 16-byte aligned, nq_qat_ws_floats(segs, nseg, mode) = 4 (sum of K)
+ * floats (0 for NQ_QAT_FFNERV; NQ_ERR_INVALID for arguments the entries refuse); per column {s_c, a(c) [int32], S_c [double]},
+ * segment i behind the columns of the segments before it: s_c at ws[4 k0 ..], a(c) at ws[4 k0 + K ..], S_c at ws[4 k0 + 2 K ..].
+ * nq_qat_forward writes s_c and a(c); nq_qat_backward READS them (the same w, the same segment list and ws as the forward: nothing
+ * else is kept between the two; ffnerv recomputes tanh) and writes S_c.
+ * Launches: ffnerv 1 forward, 1 backward; hinerv 2 + 2 (column statistics / column sums, then elementwise), per 16 segments.  No
+ * atomics, bit-identical from call to call, nothing allocated, no host read: capturable in a hipGraph.  NQ_ERR_INVALID, before
+ * the device is touched: a null or misaligned pointer, bits outside 2 .. 8, a non-positive size, an unknown mode. */
+#define NQ_QAT_FFNERV 0
+#define NQ_QAT_HINERV 1
+typedef struct {
+  const float* w;
+  const float* g; /* backward only */
+  float* out;
+  int Cout, K, bits, index;
+} nq_qat_seg;
+NQ_API int64_t nq_qat_ws_floats(const nq_qat_seg* segs, int nseg, int mode);
+NQ_API int nq_qat_forward(const nq_qat_seg* segs, int nseg, int mode, int noise, uint64_t seed, const int* step, float* ws,
+                   nq_stream_t stream);
+NQ_API int nq_qat_backward(const nq_qat_seg* segs, int nseg, int mode, int noise, uint64_t seed, const int* step, float* ws,
+                    nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,11 @@ class AdamSeg(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64)]
 
 
+class QatSeg(Structure):
+    """nq_qat_seg (include/nq_hip.h): one weight tensor of a QAT quantiser call."""
+    _fields_ = [("w", c_void_p), ("g", c_void_p), ("out", c_void_p), ("Cout", c_int), ("K", c_int), ("bits", c_int), ("index", c_int)]
+
+
 class RateSeg(Structure):
     """nq_rate_seg (include/nq_hip.h): one weight tensor of a level-rate call."""
     _fields_ = [("x", c_void_p), ("alpha", c_void_p), ("delta", c_void_p), ("zp", c_void_p), ("dalpha", c_void_p),
@@ -224,6 +229,9 @@ def _load():
     sig("nq_patchify_ln_ws_bytes", L, I, I, I, I, I, I, I)
     sig("nq_patchify_ln_forward", I, *[P] * 8, I, I, I, I, I, I, I, P)
     sig("nq_patchify_ln_backward", I, *[P] * 14, L, I, I, I, I, I, I, I, P)
+    sig("nq_qat_ws_floats", L, POINTER(QatSeg), I, I)
+    sig("nq_qat_forward", I, POINTER(QatSeg), I, I, I, ctypes.c_uint64, P, P, P)
+    sig("nq_qat_backward", I, POINTER(QatSeg), I, I, I, ctypes.c_uint64, P, P, P)
     return lib
 
 
@@ -253,6 +261,7 @@ EXPORTS = (
     "nq_scale_init_ws_bytes", "nq_scale_init_search", "nq_scale_init_gaussian",
     "nq_convnext_block_ws_bytes", "nq_convnext_block_forward", "nq_convnext_block_backward",
     "nq_patchify_ln_ws_bytes", "nq_patchify_ln_forward", "nq_patchify_ln_backward",
+    "nq_qat_ws_floats", "nq_qat_forward", "nq_qat_backward",
 )
 
 _lib = None

@@ -7,7 +7,8 @@ HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tan
 from the GPU-resident cache; Adam and, by default, the ConvNeXt encoder stay in PyTorch (`--enc_kernels hip` runs the
 encoder's Blocks on csrc/convnext.hip; `--enc_kernels hip_all` also its downsampling stages, patchify conv +
 channels-first LayerNorm, on csrc/patchify.hip).  Evaluations report PSNR and MS-SSIM
-(ops.ms_ssim); tensorboard is not produced.
+(ops.ms_ssim); tensorboard is not produced.  `--qat ffnerv|hinerv --qat_bits B` trains the quantisation-aware baselines of the
+reference's QATQuantizer: every decoder weight passes through csrc/qat.hip in front of the decoder node.
 
     python -m neuroquant_amd.methods.regress --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny
 """
@@ -47,7 +48,44 @@ def parse_args(argv):
     p.add_argument('--enc_kernels', choices=('torch', 'hip', 'hip_all'), default='torch',
                    help="what runs the HNeRV encoder: PyTorch ops; 'hip': its ConvNeXt blocks on csrc/convnext.hip; 'hip_all': "
                         "the blocks and the downsampling stages (csrc/patchify.hip)")
+    p.add_argument('--qat', choices=('ffnerv', 'hinerv'), default=None,
+                   help="quantisation-aware training (the reference's QATQuantizer): every decoder weight, layer 0 and the head "
+                        "included, is quantised in front of the decoder; biases and the encoder stay fp32")
+    p.add_argument('--qat_bits', type=int, default=8, help='bit width of --qat, 2 .. 8')
+    p.add_argument('--qat_seed', type=int, default=0, help="seed of the 'hinerv' noise mask")
     return p.parse_args(argv)
+
+
+class WeightQAT:
+    """The `weight_qat` hook of models/_decode.run_decoder: the decoder's [(W, b)] -> [(QATQuantizer(W), b)] in ONE ops.qat_weight
+    call over all weights.  'hinerv' noise is on exactly while the model is in training mode, so evaluations decode with every
+    weight quantised; `step`, the device counter the noise mask reads, advances in front of every training forward.  Not a
+    module: checkpoints hold the latent fp32 weights under the model's own keys.  `last`: the weights of the latest decode."""
+
+    def __init__(self, model, mode, bits, seed=0):
+        ops.qat_args('--qat', None, bits, mode, seed)
+        self.model, self.mode, self.bits, self.seed = model, mode, bits, seed
+        self.step, self.last = None, None
+
+    def __call__(self, weights):
+        Ws = [W for W, _ in weights]
+        noise = self.mode == 'hinerv' and self.model.training
+        if noise:
+            if self.step is None:
+                self.step = torch.zeros(1, dtype=torch.int32, device=Ws[0].device)
+            self.step += 1
+        self.last = ops.qat_weight(Ws, self.bits, self.mode, noise, self.seed, self.step)
+        return [(Wq, b) for Wq, (_, b) in zip(self.last, weights)]
+
+
+def build_model(args, cfg, device):
+    """The model `train` optimises: HNeRV / NeRV of the config; with --qat its decoder reads quantised weights (WeightQAT)."""
+    if args.arch == 'hnerv':
+        cfg = dict(cfg, enc_kernels=getattr(args, 'enc_kernels', 'torch'))   # a flag, not a config line: the reference's YAML files stay usable
+    model = (HNeRV if args.arch == 'hnerv' else NeRV)(cfg).to(device)
+    mode = getattr(args, 'qat', None)
+    model.weight_qat = WeightQAT(model, mode, args.qat_bits, getattr(args, 'qat_seed', 0)) if mode is not None else None
+    return model
 
 
 def adjust_lr(optimizer, cur_epoch, args, eta_min=0.05):
@@ -104,6 +142,17 @@ def step_loss(img_out, img, yuv=None):
     return objective.of_params(yuv).step_loss(img_out, img)
 
 
+def train_step(model, optimizer, sample, args, obj):
+    """one optimiser step on one batch of the loader -> the decoded frames"""
+    img = sample['img']
+    img_out, _, _ = model(img if args.arch == 'hnerv' else sample['norm_idx'])
+    loss = step_loss(img_out, img, obj)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    optimizer.step()
+    return img_out
+
+
 def train(args, cfg):
     if not torch.cuda.is_available():
         raise RuntimeError('neuroquant_amd needs an AMD GPU')
@@ -113,9 +162,7 @@ def train(args, cfg):
     n = len(cache)
     train_ind, args.val_ind_list = data_split(list(range(n)), [int(x) for x in args.data_split.split('_')], False, 0)
     loader = CacheLoader(cache, train_ind, cfg['batch_size'], seed=args.seed)
-    if args.arch == 'hnerv':
-        cfg = dict(cfg, enc_kernels=getattr(args, 'enc_kernels', 'torch'))   # a flag, not a config line: the reference's YAML files stay usable
-    model = (HNeRV if args.arch == 'hnerv' else NeRV)(cfg).to(device)
+    model = build_model(args, cfg, device)
     os.makedirs(args.outf, exist_ok=True)
     setup_logger(os.path.join(args.outf, time.strftime('%Y%m%d_%H%M%S') + '.log'))
     if args.weight != 'None':
@@ -134,11 +181,7 @@ def train(args, cfg):
         for i, sample in enumerate(loader):
             lr = adjust_lr(optimizer, (epoch + float(i) / len(loader)) / cfg['epoch'], args)
             img = sample['img']
-            img_out, _, _ = model(img if args.arch == 'hnerv' else sample['norm_idx'])
-            loss = step_loss(img_out, img, obj)
-            optimizer.zero_grad(set_to_none=True)
-            loss.backward()
-            optimizer.step()
+            img_out = train_step(model, optimizer, sample, args, obj)
             psnrs.append(ops.frame_psnr(img_out, img))
             if i % args.print_freq == 0 or i == len(loader) - 1:
                 logging.info('[{}], Epoch[{}/{}], Step [{}/{}], lr:{:.2e} pred_PSNR: {}'.format(

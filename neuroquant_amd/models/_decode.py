@@ -60,15 +60,21 @@ def run_decoder(model, img_embed, embed_after_reshape: bool):
     With autograd enabled and a fully wrapped decoder the whole stack runs as ONE fused autograd node
     (ops.decoder_stack): activations are never materialised, so embed_list then only carries the input embedding.
     Without autograd (evaluation) every layer runs on its own fused kernel and embed_list is complete, as in the
-    reference.
+    reference.  A model with a `weight_qat` hook (methods/regress.py --qat) always takes the fused node, evaluation included:
+    the hook turns the providers' latent weights into the quantised ones the node reads.
     """
-    if torch.is_grad_enabled() and img_embed.is_cuda:
+    weight_qat = getattr(model, 'weight_qat', None)    # the trainer's --qat hook: [(W, b)] -> [(quantised W, b)], one list call
+    if (torch.is_grad_enabled() or weight_qat is not None) and img_embed.is_cuda:
         fused = _fused_stack(model)
         if fused is not None:
             from .. import ops
             spec, provs = fused
-            img_out = ops.decoder_stack(img_embed, spec, [p() for p in provs])
+            weights = [p() for p in provs]
+            img_out = ops.decoder_stack(img_embed, spec, weights if weight_qat is None else weight_qat(weights))
             return img_out, [img_embed]
+    if weight_qat is not None:
+        raise RuntimeError('weight_qat quantises the weights in front of the fused decoder node: this decoder is not of the shape '
+                           'that node runs, or its embedding is not on the GPU (no fallback exists)')
     embed_list = [img_embed]
     output = model.decoder[0](img_embed)
     if not embed_after_reshape:

@@ -2717,3 +2717,123 @@ def patchify_ln(x, conv_w, conv_b, ln_w, ln_b, order):
     multiple of 8 up to 64, Cin likewise or ('post') 3.  The data gradient is computed only if x requires one.  Bit-identical
     from call to call."""
     return _PatchifyLnFn.apply(x, conv_w, conv_b, ln_w, ln_b, order)
+
+
+# ------------------------------------------------------------------------------------------ QAT weight quantisers
+QAT_MODES = {"ffnerv": 0, "hinerv": 1}      # NQ_QAT_FFNERV, NQ_QAT_HINERV (include/nq_hip.h)
+_QAT_WS = {}                                 # list signature -> workspace
+
+
+def qat_args(what, weights, bits, mode, seed=0):
+    """The argument rules of the QAT quantiser entries, checked without a GPU -> (bits per tensor, mode number).  weights None:
+    the rules of mode, bits and seed alone."""
+    if mode not in QAT_MODES:
+        raise ValueError(f"{what}: mode must be one of {tuple(QAT_MODES)}, got {mode!r}")
+    if weights is not None and (not isinstance(weights, (list, tuple)) or not weights):
+        raise ValueError(f"{what}: weights is a non-empty list of tensors")
+    bits = [bits] * (1 if weights is None else len(weights)) if isinstance(bits, int) else list(bits)
+    if (weights is not None and len(bits) != len(weights)) or any(isinstance(b, bool) or not isinstance(b, int) or not 2 <= b <= 8
+                                                                  for b in bits):
+        raise ValueError(f"{what}: bits must be an int in [2, 8], or one per tensor, got {bits!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{what}: seed must be an int in [0, 2^64), got {seed!r}")
+    for w in weights or ():
+        if not isinstance(w, torch.Tensor) or w.dim() < 2 or w.numel() == 0 or w.numel() >= 2 ** 31:
+            raise ValueError(f"{what}: every weight is a non-empty (Cout, ...) tensor of at least two dimensions below 2^31 elements")
+    return bits, QAT_MODES[mode]
+
+
+def _qat_step(step, device):
+    """`step` as the device int32 scalar the kernels read: a tensor is taken as it is (a captured call replays with its value of
+    the moment), an int is copied to the device."""
+    if isinstance(step, torch.Tensor):
+        if step.dtype != torch.int32 or step.numel() != 1 or step.device != device:
+            raise ValueError("qat_weight: a step tensor is one int32 on the weights' device")
+        return step
+    return torch.tensor([int(step)], dtype=torch.int32, device=device)
+
+
+def _qat_call(bwd, weights, grads, bits, mode, noise, seed, step, ws=None, indices=None):
+    """One nq_qat_forward / nq_qat_backward call over the whole list -> (outputs, workspace).  indices: the tensors' words of the
+    noise generator's counter, by default their positions in the list."""
+    nbits, m = qat_args("qat_weight", weights, bits, mode, seed)
+    ws_in = [_dev(w.detach(), "weight") for w in weights]
+    gs = [_dev(g.detach(), "gradient") for g in grads] if bwd else [None] * len(ws_in)
+    outs = [torch.empty_like(w) for w in ws_in]
+    segs = (L.QatSeg * len(ws_in))()
+    for i, (w, g, o, b) in enumerate(zip(ws_in, gs, outs, nbits)):
+        segs[i] = L.QatSeg(w.data_ptr(), g.data_ptr() if bwd else None, o.data_ptr(), w.shape[0], w.numel() // w.shape[0], b,
+                           i if indices is None else indices[i])
+    dev = ws_in[0].device
+    if m == QAT_MODES["hinerv"]:
+        if ws is None:
+            if bwd:
+                raise ValueError("qat_weight: the hinerv backward reads the workspace its forward wrote")
+            key = (mode, dev, tuple((w.data_ptr(), tuple(w.shape), b) for w, b in zip(ws_in, nbits)))
+            ws = _QAT_WS.get(key)
+            if ws is None:
+                if len(_QAT_WS) >= 64:      # lists of other tensors (tests, tools): start over; a pending backward keeps its own
+                    _QAT_WS.clear()
+                ws = _QAT_WS[key] = torch.empty(L.lib().nq_qat_ws_floats(segs, len(ws_in), m), device=dev, dtype=torch.float32)
+        step = _qat_step(step, dev) if noise else None
+    else:
+        step = ws = None
+    entry = L.lib().nq_qat_backward if bwd else L.lib().nq_qat_forward
+    L.check(_timed("qat_bwd" if bwd else "qat_fwd", lambda: entry(segs, len(ws_in), m, int(bool(noise)), seed, _p(step), _p(ws),
+                                                                _stream())), "qat_backward" if bwd else "qat_forward")
+    return outs, ws
+
+
+def qat_weight_raw(weights, bits, mode, noise=False, seed=0, step=0, indices=None):
+    """The plain forward of qat_weight -> (outputs, workspace).  hinerv: qat_stats(workspace, weights) reads the column scales
+    and the rows of the column maxima out of the workspace; ffnerv has none.  indices: see _qat_call."""
+    return _qat_call(False, weights, None, bits, mode, noise, seed, step, None, indices)
+
+
+def qat_weight_backward_raw(weights, grads, bits, mode, noise=False, seed=0, step=0, ws=None, indices=None):
+    """The plain backward -> gradients with respect to `weights`; ws: what qat_weight_raw returned for the same list."""
+    return _qat_call(True, weights, grads, bits, mode, noise, seed, step, ws, indices)[0]
+
+
+def qat_stats(ws, weights):
+    """[(s_c (K,) float32, a(c) (K,) int32) per tensor] of a hinerv workspace (the layout of include/nq_hip.h)."""
+    out, k0 = [], 0
+    for w in weights:
+        K = w.numel() // w.shape[0]
+        out.append((ws[4 * k0:4 * k0 + K], ws[4 * k0 + K:4 * k0 + 2 * K].view(torch.int32)))
+        k0 += K
+    return out
+
+
+class _QATFn(Function):
+    @staticmethod
+    def forward(ctx, cfg, step, *weights):
+        bits, mode, noise, seed = cfg
+        outs, ws = _qat_call(False, weights, None, bits, mode, noise, seed, step)
+        ctx.cfg, ctx.ws, ctx.has_step = cfg, ws, step is not None
+        ctx.save_for_backward(*([step] if step is not None else []), *weights)   # a step or weight changed in place since: autograd refuses
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        saved = ctx.saved_tensors
+        step, weights = (saved[0], saved[1:]) if ctx.has_step else (None, saved)
+        bits, mode, noise, seed = ctx.cfg
+        gs = [torch.zeros_like(w) if g is None else g for g, w in zip(gs, weights)]
+        return (None, None, *_qat_call(True, weights, gs, bits, mode, noise, seed, step, ctx.ws)[0])
+
+
+def qat_weight(weights, bits, mode, noise=False, seed=0, step=0):
+    """QATQuantizer.forward (reference quantization/quantizer.py:351-371; the definition is in include/nq_hip.h: nq_qat_forward)
+    over a whole LIST of weight tensors: one forward call and one backward call of csrc/qat.hip, whatever the list's length.
+    mode 'ffnerv': tanh and a k-bit straight-through quantiser; 'hinerv': per-column scale, and with `noise` a tenth of the
+    elements left at full precision, chosen by a counter-based generator from (seed, step, position in the list, element).
+    bits: an int in 2 .. 8 or one per tensor.  step: an int, or an int32 device scalar that the kernels read (so a captured
+    step replays with the counter's value of the moment; it must not change between forward and backward).  The hinerv
+    workspace is allocated once per list of tensors.  -> list of quantised tensors, differentiable once."""
+    noise = bool(noise) and mode == "hinerv"
+    if noise:
+        step = _qat_step(step, weights[0].device) if isinstance(weights, (list, tuple)) and weights else step
+    else:
+        step = None
+    return list(_QATFn.apply((bits if isinstance(bits, int) else tuple(bits), mode, noise, seed), step, *weights))

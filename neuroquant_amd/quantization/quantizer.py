@@ -3,7 +3,8 @@
 Only what the network-wise calibration path reaches is implemented: UniformAffineQuantizer, asymmetric, with every
 scale_method the reference implements -- 'max', and 'mse' / 'l1' / 'gaussian' on the scale-init kernels (ops.scale_init,
 DESIGN.md §25; 'l2' is refused as the reference refuses it) -- and AdaRoundQuantizer with round_mode 'learned_hard_sigmoid'
-(SURVEY.md §2 row 5).
+(SURVEY.md §2 row 5).  QATQuantizer, the reference's quantisation-aware-training baselines 'ffnerv' and 'hinerv', runs on
+csrc/qat.hip.
 """
 import logging
 import time
@@ -114,3 +115,39 @@ class AdaRoundQuantizer(nn.Module):
 
     def extra_repr(self):
         return 'bit={}'.format(self.n_bits)
+
+
+class QATQuantizer(nn.Module):
+    """Quantisation-aware-training quantiser (reference quantizer.py:326-375): round_mode 'ffnerv' (tanh, then a k-bit
+    straight-through quantiser) or 'hinerv' (quant-noise: a per-column scale, and while `noise` is true a tenth of the
+    weights left at full precision in each forward).  Both run on csrc/qat.hip through ops.qat_weight.
+
+    Attributes kept from the reference: n_bits, sym, delta, zero_point, n_levels, round_mode, alpha, soft_targets, x_quant,
+    noise.  The noise mask is a function of (seed, step, element): `seed` is an attribute and `step` counts the noisy forwards.
+    """
+
+    def __init__(self, uaq: UniformAffineQuantizer, weight_tensor: torch.Tensor, round_mode='learned_round_sigmoid'):
+        super().__init__()
+        self.n_bits = uaq.n_bits
+        self.sym = uaq.sym
+        # delta / zero-point go through fp16 (quantizer.py:340-341); neither round mode reads them
+        self.delta = None if uaq.delta is None else uaq.delta.detach().half().float()
+        self.zero_point = None if uaq.zero_point is None else uaq.zero_point.half().float()
+        self.n_levels = uaq.n_levels
+        self.round_mode = round_mode
+        self.alpha = None
+        self.soft_targets = False
+        self.x_quant = None
+        self.noise = True
+        self.seed, self.step = 0, 0
+
+    def forward(self, x):
+        if self.round_mode not in ops.QAT_MODES:
+            raise ValueError('Wrong rounding mode')
+        noise = self.noise and self.round_mode == 'hinerv'
+        if noise:
+            self.step += 1
+        return ops.qat_weight([x], self.n_bits, self.round_mode, noise, self.seed, self.step)[0]
+
+    def extra_repr(self):
+        return 'bit={} mode={}'.format(self.n_bits, self.round_mode)
