@@ -989,6 +989,30 @@ NQ_API int nq_qat_forward(const nq_qat_seg* segs, int nseg, int mode, int noise,
 NQ_API int nq_qat_backward(const nq_qat_seg* segs, int nseg, int mode, int noise, uint64_t seed, const int* step, float* ws,
                     nq_stream_t stream);
 
+/* ---- QAT baselines to the bit stream: symbols of the two quantisers above and the weights a player rebuilds from them
+ * (csrc/qat_stream.hip; additive: nq_abi_version() stays 7).  Definitions: those above nq_qat_forward, noise == 0.
+ *   NQ_QAT_FFNERV:  symbol = q + n in [0, 2 n], q = sign(t) floor(|t| n) the integer the forward forms;  restore y = (float)q / (float)n
+ *   NQ_QAT_HINERV:  symbol = q_ic + 2^(b-1) in [0, 2^b - 1];  s_c is ALSO stored, fp32, K per tensor;  restore (float)q_ic s_c
+ * The restored weight equals nq_qat_forward's output value for value (a quantiser's -0, a negative w below the first step, comes
+ * back as +0).  form NQ_QAT_PACKED: `stored` is nq_packed_words(Cout K, bits) uint32 words in the bit order of nq_pack_levels (symbol
+ * i in bits [i b, (i + 1) b) of the stream, zero tail bits), written straight from w; NQ_QAT_SYMBOLS: Cout K bytes, one symbol
+ * each.  nq_qat_stream_seg: one tensor -- w (nq_qat_levels: read; nq_qat_restore: written), stored, scale (NQ_QAT_HINERV only:
+ * K floats, written by nq_qat_levels, read by nq_qat_restore); w, scale and packed words 4-byte aligned (a 16-byte aligned w takes
+ * 16-byte accesses); Cout K < 2^31.  ws: nq_qat_levels with NQ_QAT_HINERV only, 16-byte aligned, the nq_qat_ws_floats of the same
+ * tensors = 4 (sum of K) floats: the column statistics are the forward's own launch.  One launch per 16 segments (hinerv levels:
+ * two).  No atomics, bit-identical from call to call, nothing allocated on the device, no host read.  NQ_ERR_INVALID, before the
+ * device is touched: what nq_qat_forward refuses, and an unknown form. */
+#define NQ_QAT_PACKED 0
+#define NQ_QAT_SYMBOLS 1
+typedef struct {
+  float* w;
+  void* stored;
+  float* scale; /* NQ_QAT_HINERV only */
+  int Cout, K, bits;
+} nq_qat_stream_seg;
+NQ_API int nq_qat_levels(const nq_qat_stream_seg* segs, int nseg, int mode, int form, float* ws, nq_stream_t stream);
+NQ_API int nq_qat_restore(const nq_qat_stream_seg* segs, int nseg, int mode, int form, nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

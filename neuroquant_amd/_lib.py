@@ -88,6 +88,11 @@ class QatSeg(Structure):
     _fields_ = [("w", c_void_p), ("g", c_void_p), ("out", c_void_p), ("Cout", c_int), ("K", c_int), ("bits", c_int), ("index", c_int)]
 
 
+class QatStreamSeg(Structure):
+    """nq_qat_stream_seg (include/nq_hip.h): one weight tensor of a nq_qat_levels / nq_qat_restore call."""
+    _fields_ = [("w", c_void_p), ("stored", c_void_p), ("scale", c_void_p), ("Cout", c_int), ("K", c_int), ("bits", c_int)]
+
+
 class RateSeg(Structure):
     """nq_rate_seg (include/nq_hip.h): one weight tensor of a level-rate call."""
     _fields_ = [("x", c_void_p), ("alpha", c_void_p), ("delta", c_void_p), ("zp", c_void_p), ("dalpha", c_void_p),
@@ -232,6 +237,8 @@ def _load():
     sig("nq_qat_ws_floats", L, POINTER(QatSeg), I, I)
     sig("nq_qat_forward", I, POINTER(QatSeg), I, I, I, ctypes.c_uint64, P, P, P)
     sig("nq_qat_backward", I, POINTER(QatSeg), I, I, I, ctypes.c_uint64, P, P, P)
+    sig("nq_qat_levels", I, POINTER(QatStreamSeg), I, I, I, P, P)
+    sig("nq_qat_restore", I, POINTER(QatStreamSeg), I, I, I, P)
     return lib
 
 
@@ -261,7 +268,7 @@ EXPORTS = (
     "nq_scale_init_ws_bytes", "nq_scale_init_search", "nq_scale_init_gaussian",
     "nq_convnext_block_ws_bytes", "nq_convnext_block_forward", "nq_convnext_block_backward",
     "nq_patchify_ln_ws_bytes", "nq_patchify_ln_forward", "nq_patchify_ln_backward",
-    "nq_qat_ws_floats", "nq_qat_forward", "nq_qat_backward",
+    "nq_qat_ws_floats", "nq_qat_forward", "nq_qat_backward", "nq_qat_levels", "nq_qat_restore",
 )
 
 _lib = None

@@ -18,6 +18,10 @@ HNeRV's frame embeddings are fp32 by default.  `embedding_bits=` (DESIGN.md §17
 scale per embedding channel: packed, rANS coded, or rANS coded as frame-to-frame differences, whichever is smallest.  The
 player rebuilds them once at open (`ops.embed_restore`) and decodes as before.  `quantise_embeddings` gives the tensor such a
 file restores, so that a model can be calibrated and evaluated on what its file will hold.
+
+`write_qat_stream` writes a QAT-trained model (methods/regress.py --qat) into the same container: the weights as
+the symbols of the 'ffnerv' / 'hinerv' quantiser (`ops.qat_levels`), named by one more header field, `weight_quantiser`;
+`StreamDecoder` restores them at open (`ops.qat_restore`) and decodes as before, with arithmetic 'exact' only.
 """
 import collections
 import json
@@ -321,6 +325,14 @@ class _DeviceLevels:
         freq, states, offsets, words = self.dev
         return ops.rans_decode_dequant(words, states, offsets, freq, delta, zp, shape, st.n_bits, st.chunk, trusted=True)
 
+    def symbols(self):
+        """-> (tensor, form) as `ops.qat_restore` takes them: the packed words as uploaded, or the coded tensor's byte symbols"""
+        st = self.st
+        if st.coding == "packed":
+            return self.dev[0], "packed"
+        freq, states, offsets, words = self.dev
+        return ops.rans_decode(words, states, offsets, freq, st.n, st.n_bits, st.chunk, trusted=True), "symbols"
+
 
 # uint8 levels on the GPU -> the sections [(section name, tag, array)] that store them, one function per coding
 def _packed_section(name, levels_u8, n_bits):
@@ -452,11 +464,7 @@ def _layer_side(q, x, name, prefix, kind, coding, chunk, encoder="host"):
     else:
         hard = ops.uaq_forward(x, q.delta.data, q.zero_point, q.n_levels)
     levels = _levels(q, x)
-    chosen, secs = "packed", _packed_section(name, levels, q.n_bits)
-    if coding != "packed":
-        coded = _rans_sections(name, levels, q.n_bits, chunk, encoder)
-        if coding == "rans" or _section_bytes(coded) < _section_bytes(secs):
-            chosen, secs = "rans", coded
+    chosen, secs = _level_sections(name, levels, q.n_bits, coding, chunk, encoder)
     stored = _stored_levels(_as_stored(secs), name, x.numel(), int(q.n_bits), chosen, chunk, "write_stream")
     delta, zp = q.delta.detach().float().reshape(-1), q.zero_point.detach().float().reshape(-1)
     if not torch.equal(_DeviceLevels(stored, x.device).dequant(delta, zp, x.shape), hard):
@@ -476,6 +484,42 @@ def _check_decoder_shape(arch, cfg):
         raise ValueError(f"unknown arch {arch!r}")
     if cfg.get("out_bias") != "tanh" or cfg.get("dec_acts") != "gelu":
         raise ValueError("the player decodes the shipped decoder only: exact-GELU blocks and a tanh head")
+
+
+def _stream_embeddings(arch, embeddings, embedding_bits, frames):
+    """the embeddings= / embedding_bits= / frames= of a writer -> (fp32 embeddings the file's frames are decoded from or None,
+    their QuantisedEmbeddings or None, frame count)"""
+    emb = qemb = None
+    if embedding_bits is not None and arch != "hnerv":
+        raise ValueError("embedding_bits applies to HNeRV streams: a NeRV stream stores no embeddings")
+    if arch == "hnerv":
+        if embeddings is None:
+            raise ValueError("an HNeRV stream stores the frame embeddings: pass embeddings=")
+        if isinstance(embeddings, QuantisedEmbeddings):
+            if embedding_bits not in (None, embeddings.bits):
+                raise ValueError(f"embeddings were quantised to {embeddings.bits} bits, embedding_bits asks for {embedding_bits}")
+            qemb = embeddings
+        elif embedding_bits is not None:
+            qemb = quantise_embeddings(embeddings, embedding_bits)
+        emb = qemb.restored if qemb is not None else (
+            torch.cat(list(embeddings), 0) if isinstance(embeddings, (list, tuple)) else embeddings).detach().float()
+        frames = emb.shape[0] if frames is None else frames
+        if frames != emb.shape[0]:
+            raise ValueError(f"{frames} frames but {emb.shape[0]} embeddings")
+    elif frames is None:
+        raise ValueError("a NeRV stream needs the frame count: pass frames=")
+    return emb, qemb, frames
+
+
+def _level_sections(name, levels_u8, n_bits, coding, chunk, encoder, packed=None):
+    """uint8 levels -> (coding chosen, sections): 'packed', 'rans', or under 'auto' the coded form where it is smaller.
+    packed: the packed sections where the caller already holds them."""
+    chosen, secs = "packed", packed if packed is not None else _packed_section(name, levels_u8, n_bits)
+    if coding != "packed":
+        coded = _rans_sections(name, levels_u8, n_bits, chunk, encoder)
+        if coding == "rans" or _section_bytes(coded) < _section_bytes(secs):
+            chosen, secs = "rans", coded
+    return chosen, secs
 
 
 @torch.no_grad()
@@ -506,25 +550,7 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
     if coding != "packed":
         _check_chunk(chunk, "write_stream")
     _check_decoder_shape(arch, cfg)
-    emb = qemb = None
-    if embedding_bits is not None and arch != "hnerv":
-        raise ValueError("embedding_bits applies to HNeRV streams: a NeRV stream stores no embeddings")
-    if arch == "hnerv":
-        if embeddings is None:
-            raise ValueError("an HNeRV stream stores the frame embeddings: pass embeddings=")
-        if isinstance(embeddings, QuantisedEmbeddings):
-            if embedding_bits not in (None, embeddings.bits):
-                raise ValueError(f"embeddings were quantised to {embeddings.bits} bits, embedding_bits asks for {embedding_bits}")
-            qemb = embeddings
-        elif embedding_bits is not None:
-            qemb = quantise_embeddings(embeddings, embedding_bits)
-        emb = qemb.restored if qemb is not None else (
-            torch.cat(list(embeddings), 0) if isinstance(embeddings, (list, tuple)) else embeddings).detach().float()
-        frames = emb.shape[0] if frames is None else frames
-        if frames != emb.shape[0]:
-            raise ValueError(f"{frames} frames but {emb.shape[0]} embeddings")
-    elif frames is None:
-        raise ValueError("a NeRV stream needs the frame count: pass frames=")
+    emb, qemb, frames = _stream_embeddings(arch, embeddings, embedding_bits, frames)
     mods = [m for m in qnn.model.modules() if isinstance(m, QuantModule)]
     layers, sections, nominal_bits, entropy_bits = [], [], 0, 0.0   # sections: [(kind in the size summary, (name, tag, array))]
     for i, m in enumerate(mods):
@@ -579,6 +605,131 @@ def write_stream(qnn, path, arch, cfg, embeddings=None, frames=None, bias="soft"
     return summary
 
 
+# ------------------------------------------------------------------------------------------ QAT-trained models
+QAT_FIELD = "weight_quantiser"   # header: {"mode": 'ffnerv' | 'hinerv', "bits": [per layer]}; absent in a calibrated model's file
+
+
+def qat_entry(header, what="stream"):
+    """The weight quantiser a parsed header names -> None (a calibrated model's file) or (mode, [bits per layer]), checked on
+    the host: a file whose weights are QAT symbols (`write_qat_stream`) and not levels under a step and a zero point.
+    ValueError for a mode this reader does not know, widths that are not the layers' own, or a Hadamard / hard-bias file."""
+    entry = header.get(QAT_FIELD)
+    if entry is None:
+        return None
+    layers = header.get("layers", [])
+    mode, bits = (entry.get("mode"), entry.get("bits")) if isinstance(entry, dict) else (None, None)
+    if mode not in ops.QAT_MODES:
+        raise ValueError(f"{what}: weights stored under an unknown quantiser {entry!r}; this reader serves {tuple(ops.QAT_MODES)}")
+    if not isinstance(bits, list) or len(bits) != len(layers):
+        raise ValueError(f"{what}: {QAT_FIELD} must give one bit width per layer, got {bits!r} for {len(layers)} layers")
+    for i, (b, lay) in enumerate(zip(bits, layers)):
+        _check_bits(b, 2, 8, f"{what}: {QAT_FIELD} bits of layer {i}")
+        if lay.get("n_bits") != b or lay.get("c_in_stored") != lay["shape"][1]:
+            raise ValueError(f"{what}: layer {i} stores {lay.get('n_bits')!r}-bit levels of {lay.get('c_in_stored')!r} input "
+                             f"channels, its quantiser says {b} bits of {lay['shape'][1]}")
+    if header.get("hadamard") or header.get("bias") != "soft":
+        raise ValueError(f"{what}: a {mode} file stores plain-domain weights and fp32 biases")
+    return mode, bits
+
+
+def restore_qat_weights(header, sec, stored, device, what="stream"):
+    """The decoder weights of a QAT file, layer order: every stored tensor (`stored_tensors`' result, so host-checked) to the
+    GPU, rANS-coded ones decoded to byte symbols, then `ops.qat_restore`: one call for the packed tensors, one for the coded."""
+    mode, bits = qat_entry(header, what)
+    shapes = [tuple(lay["shape"]) for lay in header["layers"]]
+    held, scales = [], []
+    for i, shape in enumerate(shapes):
+        held.append(_DeviceLevels(stored[f"w{i}"], device).symbols())
+        sc = sec.get(f"w{i}.scale")
+        if mode == "hinerv":
+            K = int(np.prod(shape[1:]))
+            if sc is None or sc.dtype != np.dtype(_DTYPES["f32"]) or len(sc) != K:
+                raise ValueError(f"{what}: w{i}.scale must hold {K} f32 column scales")
+            sc = _upload(sc, device)
+        scales.append(sc)
+    out = [None] * len(shapes)
+    for form in ops.QAT_FORMS:
+        idx = [i for i, (_, f) in enumerate(held) if f == form]
+        if idx:
+            ws = ops.qat_restore([held[i][0] for i in idx], [shapes[i] for i in idx], [bits[i] for i in idx], mode,
+                                 [scales[i] for i in idx], form)
+            for i, w in zip(idx, ws):
+                out[i] = w
+    return out
+
+
+@torch.no_grad()
+def write_qat_stream(model, path, arch, cfg, mode, bits, embeddings=None, frames=None, coding="packed", chunk=DEFAULT_CHUNK,
+                     encoder="host"):
+    """Write a QAT-trained `model` (methods/regress.py --qat: HNeRV / NeRV with latent fp32 decoder weights) to `path`: the
+    container of `write_stream` with one more header field, `weight_quantiser`.  Every decoder weight is stored as the b-bit
+    symbols of its quantiser (`ops.qat_levels`: packed words straight from the latent weights; for coding 'rans' / 'auto' byte
+    symbols through the rANS coders of `write_stream`), 'hinerv' adds its fp32 column scales (`w{i}.scale`); biases are fp32, as
+    QAT leaves them.  mode, bits: as `ops.qat_weight` takes them (an int or one per layer).  embeddings: HNeRV's, a tensor, a
+    list or a `QuantisedEmbeddings`, stored as `write_stream` stores them; NeRV needs `frames`.  Before anything is written the
+    player's own functions restore the weights from the sections and `ops.qat_weight(..., noise=False)`, what the model's
+    evaluation decodes with, must come out.  -> summary: file size, bytes per kind of section, the nominal size (bits x
+    parameters + scales + biases + embeddings + header) and the gap to it, bpp when the frame size is known."""
+    from .models._decode import _fused_stack
+    if coding not in CODINGS:
+        raise ValueError(f"coding must be one of {CODINGS}, got {coding!r}")
+    _check_encoder(encoder, "write_qat_stream")
+    if coding != "packed":
+        _check_chunk(chunk, "write_qat_stream")
+    _check_decoder_shape(arch, cfg)
+    fused = _fused_stack(model)
+    if fused is None:
+        raise ValueError("write_qat_stream: the decoder is not the shipped shape (stride-1 'same' convolutions, exact-GELU blocks, "
+                         "a tanh head)")
+    params = [p() for p in fused[1]]
+    Ws = [W.detach() for W, _ in params]
+    nbits, _ = ops.qat_args("write_qat_stream", Ws, bits, mode)
+    emb, qemb, frames = _stream_embeddings(arch, embeddings, None, frames)
+    want = ops.qat_weight_raw(Ws, nbits, mode, False)[0]
+    packed = ops.qat_levels(Ws, nbits, mode, "packed")
+    symbols = ops.qat_levels(Ws, nbits, mode, "symbols") if coding != "packed" else [(None, None)] * len(Ws)
+    layers, sections, nominal_bits = [], [], 0   # sections: [(kind in the size summary, (name, tag, array))]
+    for i, (W, (_, b), n_bits) in enumerate(zip(Ws, params, nbits)):
+        words = [(f"w{i}.levels", "u32", packed[i][0].cpu().numpy().view(np.uint32))]
+        chosen, secs = _level_sections(f"w{i}", symbols[i][0], n_bits, coding, chunk, encoder, packed=words)
+        lay = dict(shape=list(W.shape), c_in_stored=int(W.shape[1]), n_bits=n_bits)
+        if chosen == "rans":
+            lay.update(levels_coding="rans", rans_chunk=chunk)
+        sections += [(f"weight_{k}", s) for (k, _), s in zip(_LEVEL_PARTS[chosen], secs)]
+        if mode == "hinerv":
+            sections.append(("weight_scale", (f"w{i}.scale", "f32", packed[i][1].cpu().numpy())))
+        sections.append(("bias_soft", (f"b{i}.soft", "f32", b.detach().float().cpu().numpy())))
+        layers.append(lay)
+        nominal_bits += n_bits * W.numel()
+    header = dict(arch=arch, cfg=cfg, frames=int(frames), hadamard=False, bias="soft", layers=layers, embedding_shape=None,
+                  **{QAT_FIELD: dict(mode=mode, bits=nbits)})
+    held = _as_stored([s for _, s in sections])
+    got = restore_qat_weights(header, held, stored_tensors(header, held, "write_qat_stream"), Ws[0].device, "write_qat_stream")
+    if not all(torch.equal(g, w) for g, w in zip(got, want)):
+        raise RuntimeError("write_qat_stream: the stored symbols do not reproduce the quantiser's output")
+    if emb is not None:
+        header["embedding_shape"] = list(emb.shape)
+        if qemb is None:
+            sections.append(("embeddings", ("embeddings", "f32", emb.cpu().numpy())))
+        else:
+            header["embedding"], secs, _ = _embedding_stream_sections(qemb, chunk, int(frames), emb.device, encoder)
+            sections += zip(_EMBED_KINDS, secs)
+    header, size = _write_container(path, header, [s for _, s in sections])
+    kinds = {}
+    for (kind, _), s in zip(sections, header["sections"]):
+        kinds[kind] = kinds.get(kind, 0) + _align4(s["bytes"])
+    side = sum(v for k, v in kinds.items() if k in ("weight_scale", "bias_soft") or k.startswith("embedding"))
+    header_bytes = size - sum(kinds.values())
+    nominal = math.ceil(nominal_bits / 8) + side + header_bytes
+    summary = dict(path=path, file_bytes=size, header_bytes=header_bytes, section_bytes=kinds, total_bytes_nominal=nominal,
+                   gap_to_nominal_bytes=size - nominal, frames=int(frames), coding=coding, mode=mode, bits=nbits,
+                   coded_tensors=sum("levels_coding" in l for l in layers))
+    h, w = cfg.get("crop_h"), cfg.get("crop_w")
+    if frames and h and w:
+        summary["bpp"] = size * 8 / (frames * h * w)
+    return summary
+
+
 # ------------------------------------------------------------------------------------------ player
 class StreamDecoder:
     """Decode frames from a `.nqv` file alone.  Weights, biases and embeddings are rebuilt once at open; each layer's
@@ -595,7 +746,10 @@ class StreamDecoder:
     y = delta[co] * conv(f16(x), level - zero_point) + bias: the activations rounded once to IEEE half, one F16 MFMA per
     product.  An approximation, about ten times outside the bounds the other two keep and two orders of magnitude below one
     8-bit output step.  A finite activation beyond +-65504 is clamped and raises the decoder's one sticky flag word: `decode`
-    never synchronises for it, `saturated()` reads it (one synchronise) and returns a bool."""
+    never synchronises for it, `saturated()` reads it (one synchronise) and returns a bool.
+
+    A QAT-trained model's file (`write_qat_stream`; `qat` is then (mode, bits per layer), else None) decodes with 'exact' only:
+    'levels' / 'half' raise ValueError at open."""
 
     ARITHMETICS = ("exact", "levels", "half")
 
@@ -624,6 +778,10 @@ class StreamDecoder:
         if self._lv_dtype is not None and header.get("hadamard"):
             raise ValueError(f"{path}: a Hadamard-domain file stores the levels of the TRANSFORMED weights, not the convolution's: "
                              f"arithmetic={arithmetic!r} does not apply")
+        self.qat = qat_entry(header, path)   # (mode, bits) of a QAT-trained model's file (§30), None for a calibrated model's
+        if self.qat is not None and self._lv_dtype is not None:
+            raise ValueError(f"{path}: weights stored as {self.qat[0]} symbols decode with arithmetic='exact' only: 'levels' / "
+                             f"'half' factor ONE step per output channel out of the product, which no such weight has")
         self.arithmetic, self.levels_used = arithmetic, {}
         self.levels_ineligible = {}    # 'levels' / 'half': layer -> why it can never take the path (whatever the batch size)
         self.header, self.device = header, torch.device(device)
@@ -657,6 +815,10 @@ class StreamDecoder:
         # the level tensors this file stores and the bytes of their sections (unpadded), per coding
         self.level_tensors = {c: sum(st.coding == c for st in stored.values()) for c in ("packed", "rans")}
         self.level_bytes = {c: sum(st.nbytes for st in stored.values() if st.coding == c) for c in ("packed", "rans")}
+        if self.qat is not None:   # symbols of a QAT quantiser: one restore call, fp32 biases
+            self.weights = [w.contiguous() for w in restore_qat_weights(header, sec, stored, self.device, path)]
+            self.biases = [_upload(sec[f"b{i}.soft"], self.device).float().contiguous() for i in range(len(self.weights))]
+            return
         for i, lay in enumerate(header["layers"]):
             co, ci, k, k2 = lay["shape"]
             w, n, delta = self._dequant(sec, stored[f"w{i}"], (co, lay["c_in_stored"], k, k2), integers=on_levels)

@@ -19,6 +19,7 @@
 //
 // The noise mask is Philox-4x32-10 (Salmon et al., SC'11) on counter {e >> 2 low, e >> 2 high, tensor index, step} and key
 // {seed low, seed high}; element e takes output word e & 3, so a thread's four elements cost one generator call.
+#include "qat_elem.h"
 #include "seg_table.h"
 
 #include <cmath>
@@ -88,11 +89,9 @@ __device__ __forceinline__ float mask1(unsigned e, unsigned index, const Rng& rn
   return mask_of(k == 0 ? r[0] : k == 1 ? r[1] : k == 2 ? r[2] : r[3]);
 }
 
-__device__ __forceinline__ float level_of(float w, float s, int bits) {
-  const float hi = (float)((1 << (bits - 1)) - 1), lo = -(float)(1 << (bits - 1));
-  return fminf(fmaxf(rintf(w / s), lo), hi);
-}
-__device__ __forceinline__ float sign_of(float v) { return (float)((v > 0.f) - (v < 0.f)); }
+// the element arithmetic shared with qat_stream.hip (qat_elem.h)
+__device__ __forceinline__ float level_of(float w, float s, int bits) { return nq_qat_level(w, s, bits); }
+__device__ __forceinline__ float sign_of(float v) { return nq_qat_sign(v); }
 
 // ------------------------------------------------------------------------------------------------------ column kernels
 // workgroup `local` of a segment: columns [64 local, 64 local + 64); wave v: rows [v chunk, (v + 1) chunk)
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(TPB) void qat_elem_kernel(Table t, Rng rng) {
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
       const float th = tanhf(w[i]);
-      y[i] = (floorf(fabsf(th) * nl) / nl) * sign_of(th);
+      y[i] = (nq_qat_ff_floor(th, nl) / nl) * sign_of(th);
     }
   } else if (PASS == FF_BWD) {
 #pragma unroll
@@ -260,7 +259,8 @@ inline bool segs_ok(const nq_qat_seg* segs, int nseg, int mode, bool bwd, int64_
   return true;
 }
 
-int run(const nq_qat_seg* segs, int nseg, int mode, int noise, uint64_t seed, const int* step, float* ws, bool bwd, hipStream_t st) {
+int run(const nq_qat_seg* segs, int nseg, int mode, int noise, uint64_t seed, const int* step, float* ws, bool bwd, hipStream_t st,
+        bool columns_only = false) {
   int64_t columns;
   if (!segs_ok(segs, nseg, mode, bwd, &columns)) return NQ_ERR_INVALID;
   const bool hi = mode == NQ_QAT_HINERV;
@@ -293,7 +293,7 @@ int run(const nq_qat_seg* segs, int nseg, int mode, int noise, uint64_t seed, co
           else
             hipLaunchKernelGGL(qat_colmax_kernel, dim3(blocks), dim3(CTPB), 0, st, t);
         });
-    if (rc) return rc;
+    if (rc || columns_only) return rc;
   }
   return Table::launch_all(
       segs, nseg,
@@ -311,6 +311,10 @@ int run(const nq_qat_seg* segs, int nseg, int mode, int noise, uint64_t seed, co
 }
 
 }  // namespace
+
+int nq_qat_column_stats(const nq_qat_seg* segs, int nseg, float* ws, hipStream_t st) {
+  return run(segs, nseg, NQ_QAT_HINERV, 0, 0, nullptr, ws, false, st, true);
+}
 
 extern "C" {
 

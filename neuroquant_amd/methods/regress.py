@@ -8,7 +8,10 @@ from the GPU-resident cache; Adam and, by default, the ConvNeXt encoder stay in 
 encoder's Blocks on csrc/convnext.hip; `--enc_kernels hip_all` also its downsampling stages, patchify conv +
 channels-first LayerNorm, on csrc/patchify.hip).  Evaluations report PSNR and MS-SSIM
 (ops.ms_ssim); tensorboard is not produced.  `--qat ffnerv|hinerv --qat_bits B` trains the quantisation-aware baselines of the
-reference's QATQuantizer: every decoder weight passes through csrc/qat.hip in front of the decoder node.
+reference's QATQuantizer: every decoder weight passes through csrc/qat.hip in front of the decoder node (DESIGN.md §29);
+with `--export_stream FILE.nqv [--stream_coding packed|rans|auto] [--stream_encoder host|gpu]` the trained model (or, with
+`--eval_only --weight ckpt`, a checkpoint) is also written as a bit stream that `python -m neuroquant_amd.methods.decode_stream`
+plays back to the frames of the evaluation.
 
     python -m neuroquant_amd.methods.regress --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny
 """
@@ -53,6 +56,12 @@ def parse_args(argv):
                         "included, is quantised in front of the decoder; biases and the encoder stay fp32")
     p.add_argument('--qat_bits', type=int, default=8, help='bit width of --qat, 2 .. 8')
     p.add_argument('--qat_seed', type=int, default=0, help="seed of the 'hinerv' noise mask")
+    p.add_argument('--export_stream', type=str, default=None,
+                   help='--qat: write the trained model as a bit stream (.nqv, bitstream.write_qat_stream) to this path')
+    p.add_argument('--stream_coding', type=str, default='packed', choices=['packed', 'rans', 'auto'],
+                   help='symbols of --export_stream: packed at their bit-width, rANS coded, or whichever is smaller per tensor')
+    p.add_argument('--stream_encoder', type=str, default='host', choices=['host', 'gpu'],
+                   help='who runs the rANS encoder of --export_stream: numpy on the host, or the HIP encoder on the device')
     return p.parse_args(argv)
 
 
@@ -86,6 +95,18 @@ def build_model(args, cfg, device):
     mode = getattr(args, 'qat', None)
     model.weight_qat = WeightQAT(model, mode, args.qat_bits, getattr(args, 'qat_seed', 0)) if mode is not None else None
     return model
+
+
+def export_stream(model, args, cfg, embeddings, frames):
+    """--export_stream: the QAT-trained model as a .nqv file; embeddings: what the evaluation decoded the frames from"""
+    from ..bitstream import write_qat_stream
+    s = write_qat_stream(model, args.export_stream, args.arch, cfg, args.qat, args.qat_bits, frames=frames,
+                         embeddings=embeddings if args.arch == 'hnerv' else None, coding=args.stream_coding,
+                         encoder=args.stream_encoder)
+    logging.info('bit stream: {} ({} bytes, {} bpp; nominal {} bytes; {} at {} bits, coding {})'.format(
+        args.export_stream, s['file_bytes'], round(s.get('bpp', float('nan')), 5), s['total_bytes_nominal'], s['mode'],
+        args.qat_bits, s['coding']))
+    return s
 
 
 def adjust_lr(optimizer, cur_epoch, args, eta_min=0.05):
@@ -163,14 +184,19 @@ def train(args, cfg):
     train_ind, args.val_ind_list = data_split(list(range(n)), [int(x) for x in args.data_split.split('_')], False, 0)
     loader = CacheLoader(cache, train_ind, cfg['batch_size'], seed=args.seed)
     model = build_model(args, cfg, device)
+    want_stream = getattr(args, 'export_stream', None)
+    if want_stream and model.weight_qat is None:
+        raise ValueError('--export_stream writes a --qat model; a calibrated model is written by calibrate_network --export_stream')
     os.makedirs(args.outf, exist_ok=True)
     setup_logger(os.path.join(args.outf, time.strftime('%Y%m%d_%H%M%S') + '.log'))
     if args.weight != 'None':
         model.load_state_dict(torch.load(args.weight, map_location='cpu'), strict=False)
     msssim = obj.params if obj.name == MSSSIM_LOSS else None   # evaluations then log the objective's line
     if args.eval_only:
-        res, _ = evaluate(model, cache, args, cfg, msssim=msssim)
+        res, embeds = evaluate(model, cache, args, cfg, msssim=msssim)
         logging.info(report_line('', args))
+        if want_stream:
+            export_stream(model, args, cfg, embeds, n)
         return res
     optimizer = torch.optim.Adam(model.parameters(), weight_decay=0.)
     args.lr = cfg['learning_rate']
@@ -195,6 +221,8 @@ def train(args, cfg):
         if (epoch + 1) % cfg['epoch'] == 0:
             torch.save(model.state_dict(), f'{args.outf}/epoch{epoch + 1}.pth')
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
+    if want_stream:
+        export_stream(model, args, cfg, evaluate(model, cache, args, cfg, msssim=msssim)[1], n)
     return model
 
 

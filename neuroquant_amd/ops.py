@@ -2837,3 +2837,76 @@ def qat_weight(weights, bits, mode, noise=False, seed=0, step=0):
     else:
         step = None
     return list(_QATFn.apply((bits if isinstance(bits, int) else tuple(bits), mode, noise, seed), step, *weights))
+
+
+# ------------------------------------------------------------------------------------------ QAT weights <-> stored symbols
+QAT_FORMS = {"packed": 0, "symbols": 1}     # NQ_QAT_PACKED, NQ_QAT_SYMBOLS (include/nq_hip.h)
+
+
+def _qat_form(what, form):
+    if form not in QAT_FORMS:
+        raise ValueError(f"{what}: form must be one of {tuple(QAT_FORMS)}, got {form!r}")
+    return QAT_FORMS[form]
+
+
+def _qat_stream_segs(ws, stored, scales, nbits):
+    segs = (L.QatStreamSeg * len(ws))()
+    for i, (w, st, sc, b) in enumerate(zip(ws, stored, scales, nbits)):
+        segs[i] = L.QatStreamSeg(w.data_ptr(), st.data_ptr(), None if sc is None else sc.data_ptr(), w.shape[0],
+                                 w.numel() // w.shape[0], b)
+    return segs
+
+
+def qat_levels(weights, bits, mode, form="packed"):
+    """Latent weights -> what a stream stores of them (symbols: include/nq_hip.h above nq_qat_levels), ONE call
+    of csrc/qat_stream.hip over the whole list.  form 'packed': int32 words of the packed layout (ops.pack_levels' bit order),
+    written straight from the weights; 'symbols': uint8, one per element.  -> [(words or symbols, scales)] per tensor, scales
+    the K = numel / shape[0] fp32 column scales of 'hinerv', None for 'ffnerv'."""
+    nbits, m = qat_args("qat_levels", weights, bits, mode)
+    f = _qat_form("qat_levels", form)
+    ws = [_dev(w.detach(), "weight") for w in weights]
+    dev, hi = ws[0].device, m == QAT_MODES["hinerv"]
+    stored = [torch.empty(packed_words(w.numel(), b), device=dev, dtype=torch.int32) if form == "packed" else
+              torch.empty(w.numel(), device=dev, dtype=torch.uint8) for w, b in zip(ws, nbits)]
+    scales = [torch.empty(w.numel() // w.shape[0], device=dev, dtype=torch.float32) if hi else None for w in ws]
+    work = None
+    if hi:   # the forward's own column launch writes the forward's workspace
+        fwd = (L.QatSeg * len(ws))(*[L.QatSeg(w.data_ptr(), None, w.data_ptr(), w.shape[0], w.numel() // w.shape[0], b, i)
+                                     for i, (w, b) in enumerate(zip(ws, nbits))])
+        work = torch.empty(L.lib().nq_qat_ws_floats(fwd, len(ws), m), device=dev, dtype=torch.float32)
+    segs = _qat_stream_segs(ws, stored, scales, nbits)
+    L.check(_timed("qat_levels", lambda: L.lib().nq_qat_levels(segs, len(ws), m, f, _p(work), _stream())), "qat_levels")
+    return list(zip(stored, scales))
+
+
+def qat_restore(stored, shapes, bits, mode, scales=None, form="packed"):
+    """What `qat_levels` gave (or a file holds) -> the fp32 weights of `shapes`, equal to `qat_weight(..., noise=False)` of the
+    latent weights; ONE call over the whole list.  stored: int32 words ('packed') or uint8 symbols per tensor; scales: the
+    fp32 column scales per tensor ('hinerv'; ignored for 'ffnerv')."""
+    if not isinstance(stored, (list, tuple)) or not stored or not isinstance(shapes, (list, tuple)) or len(shapes) != len(stored):
+        raise ValueError("qat_restore: stored and shapes are non-empty lists of one length")
+    nbits, m = qat_args("qat_restore", None, bits if isinstance(bits, int) else list(bits), mode)
+    nbits = nbits * len(stored) if isinstance(bits, int) else nbits
+    f = _qat_form("qat_restore", form)
+    hi = m == QAT_MODES["hinerv"]
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    if len(nbits) != len(stored) or any(len(s) < 2 or min(s) <= 0 or math.prod(s) >= 2 ** 31 for s in shapes):
+        raise ValueError("qat_restore: one bit width per tensor, and every shape (Cout, ...) of at least two positive sizes below "
+                         "2^31 elements")
+    if hi and (not isinstance(scales, (list, tuple)) or len(scales) != len(stored)):
+        raise ValueError("qat_restore: 'hinerv' needs the column scales of every tensor")
+    sts, scs = [], []
+    for i, (st, s, b) in enumerate(zip(stored, shapes, nbits)):
+        n = math.prod(s)
+        st = _dev_as(st, torch.int32 if form == "packed" else torch.uint8, "stored").reshape(-1)
+        if st.numel() != (packed_words(n, b) if form == "packed" else n):
+            raise ValueError(f"qat_restore: tensor {i} of shape {s} at {b} bits is not {st.numel()} {'words' if form == 'packed' else 'symbols'}")
+        sc = _dev(scales[i], "scales").reshape(-1) if hi else None
+        if hi and sc.numel() != n // s[0]:
+            raise ValueError(f"qat_restore: tensor {i} has {n // s[0]} columns, got {sc.numel()} scales")
+        sts.append(st)
+        scs.append(sc)
+    outs = [torch.empty(s, device=sts[0].device, dtype=torch.float32) for s in shapes]
+    segs = _qat_stream_segs(outs, sts, scs, nbits)
+    L.check(_timed("qat_restore", lambda: L.lib().nq_qat_restore(segs, len(outs), m, f, _stream())), "qat_restore")
+    return outs
