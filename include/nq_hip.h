@@ -1013,6 +1013,43 @@ typedef struct {
 NQ_API int nq_qat_levels(const nq_qat_stream_seg* segs, int nseg, int mode, int form, float* ws, nq_stream_t stream);
 NQ_API int nq_qat_restore(const nq_qat_stream_seg* segs, int nseg, int mode, int form, nq_stream_t stream);
 
+/* ---- Magnitude pruning baseline: exact global threshold select, keep-mask and masked write over a LIST of tensors
+ * (csrc/prune.hip; additive: nq_abi_version() stays 7) ----
+ * THE definition.  m(w) = bits(w) & 0x7fffffff as an unsigned 32-bit integer: monotone in |w| for finite w, -0 = +0, subnormals
+ * ordered, the infinities behind every finite value and a NaN behind those.  Over the segments {w, n} of a call (N elements in
+ * all) the RANK of an element is its position in the stable order by (m, segment index, flat index).  For a given k, clamped to
+ * [0, N], the pruned set is the elements of rank < k -- except that a NaN is never pruned, whatever its rank.
+ *   T     = m of the element of rank min(k, N - 1)
+ *   below = the number of elements with m < T
+ *   r     = k - below: how many of the elements with m == T are pruned, the first r of them in the order (segment, index);
+ *           0 <= r <= the number of such elements, so k = 0 prunes nothing and k = N everything
+ * nq_prune_seg: w fp32, 4-byte aligned (a 16-byte aligned tensor takes 16-byte accesses), n >= 1; at most 16 segments (more:
+ * NQ_ERR_UNSUPPORTED), each taken as starting on a 64-element boundary of the call's index space, which holds at most 2^31
+ * elements.  c: nq_prune_apply only, up to three companions of w's size (gradient, Adam moments), each nullable.
+ * nq_magnitude_select: k_dev a DEVICE int64 scalar; sel 4 device int64, written {T, r, below, k clamped}; eight launches: per
+ *   8-bit digit, most significant first, every workgroup counts the digit of the elements under the prefix found so far in its
+ *   fixed run of nq_prune_run() consecutive elements into one 256-bin row of ws, and one workgroup adds the rows, scans the bins
+ *   and writes the new prefix and the remaining rank to sel, where the next pass reads them.
+ * nq_prune_mask: sel as written above; mask: one bit per element, 1 = keep, bit i & 63 of 64-bit word i / 64 of the segment's
+ *   words, a segment of n elements owning ceil(n / 64) consecutive words behind those of the segments before it, the bits behind
+ *   its last element 0.  Three launches: ties (m == T) per run, their exclusive scan by one workgroup, the keep bits.
+ * nq_prune_apply: w and every companion given := +0.0f exactly where the mask bit is 0; one launch.
+ * ws: nq_prune_ws_bytes(segs, nseg) = 1028 ceil(S / nq_prune_run()) bytes, S = 64 (words of all segments); 0 for a list the
+ *   entries refuse.  nq_magnitude_select and nq_prune_mask may share it; neither reads what the other left there.
+ * No launch argument depends on device data; no global atomics, nothing allocated, no host read, integers throughout:
+ * bit-identical from call to call and capturable in a hipGraph.  NQ_ERR_INVALID, before the device is touched: a null or
+ * misaligned pointer (k_dev, sel, mask: 8 bytes), a non-positive n or count, more than 2^31 elements. */
+typedef struct {
+  float* w;
+  int64_t n;
+  float* c[3]; /* nq_prune_apply only */
+} nq_prune_seg;
+NQ_API int nq_prune_run(void);
+NQ_API int64_t nq_prune_ws_bytes(const nq_prune_seg* segs, int nseg);
+NQ_API int nq_magnitude_select(const nq_prune_seg* segs, int nseg, const int64_t* k_dev, int64_t* sel, void* ws, nq_stream_t stream);
+NQ_API int nq_prune_mask(const nq_prune_seg* segs, int nseg, const int64_t* sel, uint64_t* mask, void* ws, nq_stream_t stream);
+NQ_API int nq_prune_apply(const nq_prune_seg* segs, int nseg, const uint64_t* mask, nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

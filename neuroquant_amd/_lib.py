@@ -100,6 +100,11 @@ class RateSeg(Structure):
                 ("per_row", c_int), ("n_levels", c_int)]
 
 
+class PruneSeg(Structure):
+    """nq_prune_seg (include/nq_hip.h): one tensor of a magnitude-pruning call, with its companions for nq_prune_apply."""
+    _fields_ = [("w", c_void_p), ("n", c_int64), ("c", c_void_p * 3)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise NQLibraryError(
@@ -239,6 +244,11 @@ def _load():
     sig("nq_qat_backward", I, POINTER(QatSeg), I, I, I, ctypes.c_uint64, P, P, P)
     sig("nq_qat_levels", I, POINTER(QatStreamSeg), I, I, I, P, P)
     sig("nq_qat_restore", I, POINTER(QatStreamSeg), I, I, I, P)
+    sig("nq_prune_run", I)
+    sig("nq_prune_ws_bytes", L, POINTER(PruneSeg), I)
+    sig("nq_magnitude_select", I, POINTER(PruneSeg), I, P, P, P, P)
+    sig("nq_prune_mask", I, POINTER(PruneSeg), I, P, P, P, P)
+    sig("nq_prune_apply", I, POINTER(PruneSeg), I, P, P)
     return lib
 
 
@@ -269,6 +279,7 @@ EXPORTS = (
     "nq_convnext_block_ws_bytes", "nq_convnext_block_forward", "nq_convnext_block_backward",
     "nq_patchify_ln_ws_bytes", "nq_patchify_ln_forward", "nq_patchify_ln_backward",
     "nq_qat_ws_floats", "nq_qat_forward", "nq_qat_backward", "nq_qat_levels", "nq_qat_restore",
+    "nq_prune_run", "nq_prune_ws_bytes", "nq_magnitude_select", "nq_prune_mask", "nq_prune_apply",
 )
 
 _lib = None

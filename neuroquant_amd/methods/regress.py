@@ -11,7 +11,9 @@ channels-first LayerNorm, on csrc/patchify.hip).  Evaluations re
 reference's QATQuantizer: every decoder weight passes through csrc/qat.hip in front of the decoder node (DESIGN.md §29);
 with `--export_stream FILE.nqv [--stream_coding packed|rans|auto] [--stream_encoder host|gpu]` the trained model (or, with
 `--eval_only --weight ckpt`, a checkpoint) is also written as a bit stream that `python -m neuroquant_amd.methods.decode_stream`
-plays back to the frames of the evaluation.
+plays back to the frames of the evaluation.  `--prune_ratio R` is the papers' other baseline, global unstructured
+magnitude pruning: the R smallest part of the decoder's convolution weights, by magnitude over all of them at once, is set to zero
+once the model and `--weight` are loaded (csrc/prune.hip) and held there through every optimiser step.
 
     python -m neuroquant_amd.methods.regress --arch hnerv --config cfg.yaml --data_path bunny/ --vid Bunny
 """
@@ -62,7 +64,58 @@ def parse_args(argv):
                    help='symbols of --export_stream: packed at their bit-width, rANS coded, or whichever is smaller per tensor')
     p.add_argument('--stream_encoder', type=str, default='host', choices=['host', 'gpu'],
                    help='who runs the rANS encoder of --export_stream: numpy on the host, or the HIP encoder on the device')
+    p.add_argument('--prune_ratio', type=float, default=None,
+                   help='global unstructured magnitude pruning: this part, in [0, 1], of the decoder convolution weights is zeroed '
+                        'after the model and --weight are loaded and kept at zero while training; not with --qat')
+    p.add_argument('--prune_scope', choices=('decoder',), default='decoder',
+                   help="what --prune_ratio prunes: 'decoder', its convolution weights (biases, encoder and embeddings stay)")
     return p.parse_args(argv)
+
+
+def prune_check(args):
+    """--prune_ratio's rules, before anything runs"""
+    ratio = getattr(args, 'prune_ratio', None)
+    if ratio is None:
+        return
+    if getattr(args, 'qat', None) is not None:
+        raise ValueError('--prune_ratio with --qat: mixing the two baselines is not defined here')
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError(f'--prune_ratio must lie in [0, 1], got {ratio}')
+
+
+class WeightPruner:
+    """--prune_ratio: the decoder's convolution weights (every 4-D parameter outside the encoder) pruned ONCE, globally by
+    magnitude (ops.magnitude_prune_), and the mask of that moment; `hold` writes the zeros back into weights, gradients and both
+    Adam moments in one launch after an optimiser step, so checkpoints keep their keys and hold the pruned weights as zeros."""
+
+    def __init__(self, model, ratio):
+        self.names, self.params = zip(*[(n, p) for n, p in model.named_parameters() if not n.startswith('encoder') and p.dim() == 4])
+        self.tensors = [p.data for p in self.params]
+        self.mask, self.sel = ops.magnitude_prune_(self.tensors, ratio)
+        self.pruned = ops.prune_counts(self.tensors, self.mask)
+
+    def hold(self, optimizer):
+        state = [optimizer.state.get(p, {}) for p in self.params]
+        ops.prune_apply_(self.tensors, self.mask, [p.grad for p in self.params], [s.get('exp_avg') for s in state],
+                         [s.get('exp_avg_sq') for s in state])
+
+    def sparsity(self):
+        """{name: pruned part of the tensor, ..., 'total': of all of them}, from the mask"""
+        out = {n: k / t.numel() for n, k, t in zip(self.names, self.pruned, self.tensors)}
+        out['total'] = sum(self.pruned) / sum(t.numel() for t in self.tensors)
+        return out
+
+    def log(self):
+        sp = self.sparsity()
+        logging.info('sparsity: total {:.4f} ({} of {}) | '.format(sp['total'], sum(self.pruned), sum(t.numel() for t in self.tensors))
+                     + ' '.join('{}: {:.4f}'.format(n, sp[n]) for n in self.names))
+
+
+def prune_model(model, args):
+    """-> the WeightPruner of --prune_ratio (the model is pruned when this returns), or None without the flag"""
+    prune_check(args)
+    ratio = getattr(args, 'prune_ratio', None)
+    return None if ratio is None else WeightPruner(model, ratio)
 
 
 class WeightQAT:
@@ -163,18 +216,21 @@ def step_loss(img_out, img, yuv=None):
     return objective.of_params(yuv).step_loss(img_out, img)
 
 
-def train_step(model, optimizer, sample, args, obj):
-    """one optimiser step on one batch of the loader -> the decoded frames"""
+def train_step(model, optimizer, sample, args, obj, pruner=None):
+    """one optimiser step on one batch of the loader -> the decoded frames; pruner: --prune_ratio's mask, held through the step"""
     img = sample['img']
     img_out, _, _ = model(img if args.arch == 'hnerv' else sample['norm_idx'])
     loss = step_loss(img_out, img, obj)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     optimizer.step()
+    if pruner is not None:
+        pruner.hold(optimizer)
     return img_out
 
 
 def train(args, cfg):
+    prune_check(args)
     if not torch.cuda.is_available():
         raise RuntimeError('neuroquant_amd needs an AMD GPU')
     obj = objective.of_params(loss_params(args, cfg))
@@ -191,10 +247,13 @@ def train(args, cfg):
     setup_logger(os.path.join(args.outf, time.strftime('%Y%m%d_%H%M%S') + '.log'))
     if args.weight != 'None':
         model.load_state_dict(torch.load(args.weight, map_location='cpu'), strict=False)
+    pruner = prune_model(model, args)
     msssim = obj.params if obj.name == MSSSIM_LOSS else None   # evaluations then log the objective's line
     if args.eval_only:
         res, embeds = evaluate(model, cache, args, cfg, msssim=msssim)
         logging.info(report_line('', args))
+        if pruner is not None:
+            pruner.log()
         if want_stream:
             export_stream(model, args, cfg, embeds, n)
         return res
@@ -207,7 +266,7 @@ def train(args, cfg):
         for i, sample in enumerate(loader):
             lr = adjust_lr(optimizer, (epoch + float(i) / len(loader)) / cfg['epoch'], args)
             img = sample['img']
-            img_out = train_step(model, optimizer, sample, args, obj)
+            img_out = train_step(model, optimizer, sample, args, obj, pruner)
             psnrs.append(ops.frame_psnr(img_out, img))
             if i % args.print_freq == 0 or i == len(loader) - 1:
                 logging.info('[{}], Epoch[{}/{}], Step [{}/{}], lr:{:.2e} pred_PSNR: {}'.format(
@@ -217,6 +276,8 @@ def train(args, cfg):
             res, _ = evaluate(model, cache, args, cfg, msssim=msssim)
             logging.info(f'Eval at epoch {epoch + 1}: pred_seen_psnr: {RoundTensor(res[0], 2)} | pred_seen_ssim: '
                          f'{RoundTensor(args.eval_metrics["pred_seen_ssim"], 4)}')
+            if pruner is not None:
+                pruner.log()
         torch.save(model.state_dict(), '{}/model_latest.pth'.format(args.outf))
         if (epoch + 1) % cfg['epoch'] == 0:
             torch.save(model.state_dict(), f'{args.outf}/epoch{epoch + 1}.pth')

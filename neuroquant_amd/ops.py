@@ -2910,3 +2910,131 @@ def qat_restore(stored, shapes, bits, mode, scales=None, form="packed"):
     segs = _qat_stream_segs(outs, sts, scs, nbits)
     L.check(_timed("qat_restore", lambda: L.lib().nq_qat_restore(segs, len(outs), m, f, _stream())), "qat_restore")
     return outs
+
+
+# ------------------------------------------------------------------------------------------ magnitude pruning
+PRUNE_MAX_TENSORS = 16      # segments of one table (include/nq_hip.h: nq_prune_seg)
+
+
+def prune_args(what, tensors, ratio=None, companions=()):
+    """The argument rules of the pruning entries, checked without a GPU -> N, the elements of the list.  Every refusal is a
+    ValueError: an empty list, a tensor that is not contiguous fp32, more than 16 tensors or 2^31 elements, a ratio outside
+    [0, 1], companions that do not match their tensors."""
+    if not isinstance(tensors, (list, tuple)) or not tensors:
+        raise ValueError(f"{what}: tensors is a non-empty list of tensors")
+    if len(tensors) > PRUNE_MAX_TENSORS:
+        raise ValueError(f"{what}: at most {PRUNE_MAX_TENSORS} tensors per call, got {len(tensors)}")
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0:
+            raise ValueError(f"{what}: every tensor is a non-empty contiguous float32 tensor")
+    if prune_mask_words(tensors) * 64 > 2 ** 31:
+        raise ValueError(f"{what}: at most 2^31 elements per call")
+    if ratio is not None and (isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 <= ratio <= 1.0):
+        raise ValueError(f"{what}: ratio must be a number in [0, 1], got {ratio!r}")
+    for comp in companions:
+        if comp is None:
+            continue
+        if not isinstance(comp, (list, tuple)) or len(comp) != len(tensors):
+            raise ValueError(f"{what}: a companion list has one entry (a tensor or None) per tensor")
+        for c, t in zip(comp, tensors):
+            if c is not None and (not isinstance(c, torch.Tensor) or c.dtype != torch.float32 or not c.is_contiguous()
+                                  or c.shape != t.shape or c.device != t.device):
+                raise ValueError(f"{what}: a companion is a contiguous float32 tensor of its tensor's shape and device")
+    return sum(t.numel() for t in tensors)
+
+
+def prune_mask_words(tensors):
+    """64-bit words of the keep-mask of a list: every tensor starts on a word boundary"""
+    return sum((t.numel() + 63) // 64 for t in tensors)
+
+
+def _prune_segs(tensors, companions=()):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("neuroquant_amd: tensors to prune must live on the GPU (no CPU fallback exists)")
+    segs = (L.PruneSeg * len(tensors))()
+    for i, t in enumerate(tensors):
+        segs[i].w, segs[i].n = t.data_ptr(), t.numel()
+        for j, comp in enumerate(companions):
+            if comp is not None and comp[i] is not None:
+                segs[i].c[j] = comp[i].data_ptr()
+    return segs
+
+
+def _prune_ws(segs, n, device):
+    return torch.empty(L.lib().nq_prune_ws_bytes(segs, n) // 4, device=device, dtype=torch.int32)
+
+
+def magnitude_select(tensors, k):
+    """Exact global selection over a LIST of tensors (csrc/prune.hip; the definition is in include/nq_hip.h above
+    nq_magnitude_select): -> sel, 4 int64 on the device {T, r, below, k clamped to [0, N]} -- T the magnitude pattern
+    bits(w) & 0x7fffffff of the element of rank min(k, N - 1) in the stable order (magnitude, tensor, index), `below` the
+    elements under T, r = k - below the ties at T that the first k elements take.  k: an int, or an int64 device scalar that
+    the kernels read (no host read: the call can be captured).  The tensors are only read."""
+    prune_args("magnitude_select", tensors)
+    dev = tensors[0].device
+    if isinstance(k, torch.Tensor):
+        if k.dtype != torch.int64 or k.numel() != 1 or k.device != dev:
+            raise ValueError("magnitude_select: a k tensor is one int64 on the tensors' device")
+    elif isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"magnitude_select: k is an int or an int64 device scalar, got {k!r}")
+    segs = _prune_segs(tensors)
+    k_dev = k if isinstance(k, torch.Tensor) else torch.tensor([k], dtype=torch.int64, device=dev)
+    sel = torch.empty(4, dtype=torch.int64, device=dev)
+    ws = _prune_ws(segs, len(tensors), dev)
+    L.check(_timed("prune_select", lambda: L.lib().nq_magnitude_select(segs, len(tensors), _p(k_dev), _p(sel), _p(ws), _stream())),
+            "magnitude_select")
+    return sel
+
+
+def prune_mask(tensors, sel):
+    """The keep-mask of a selection: prune_mask_words(tensors) int64 words on the device, bit i & 63 of word i // 64 of a tensor's
+    own words = 1 where element i stays.  Pruned: the magnitudes below T and the first r of the ties at T in the order (tensor,
+    index); a NaN is never pruned."""
+    prune_args("prune_mask", tensors)
+    if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int64 or sel.numel() != 4 or not sel.is_contiguous():
+        raise ValueError("prune_mask: sel is what magnitude_select returned, 4 int64")
+    segs = _prune_segs(tensors)
+    dev = tensors[0].device
+    if sel.device != dev:
+        raise ValueError("prune_mask: sel lives on the tensors' device")
+    mask = torch.empty(prune_mask_words(tensors), dtype=torch.int64, device=dev)
+    ws = _prune_ws(segs, len(tensors), dev)
+    L.check(_timed("prune_mask", lambda: L.lib().nq_prune_mask(segs, len(tensors), _p(sel), _p(mask), _p(ws), _stream())), "prune_mask")
+    return mask
+
+
+def prune_apply_(tensors, mask, grads=None, exp_avg=None, exp_avg_sq=None):
+    """In place: +0.0 wherever the mask bit is 0, in every tensor and in the companions given (each a list with a tensor or None
+    per tensor: gradients and both Adam moments), all in ONE launch -- so a pruned weight stays pruned under Adam."""
+    companions = (grads, exp_avg, exp_avg_sq)
+    prune_args("prune_apply_", tensors, companions=companions)
+    if (not isinstance(mask, torch.Tensor) or mask.dtype != torch.int64 or not mask.is_contiguous()
+            or mask.numel() != prune_mask_words(tensors)):
+        raise ValueError("prune_apply_: mask is the int64 words prune_mask returned for these tensors")
+    segs = _prune_segs(tensors, companions)
+    if mask.device != tensors[0].device:
+        raise ValueError("prune_apply_: mask lives on the tensors' device")
+    L.check(_timed("prune_apply", lambda: L.lib().nq_prune_apply(segs, len(tensors), _p(mask), _stream())), "prune_apply")
+    return tensors
+
+
+def magnitude_prune_(tensors, ratio):
+    """Global unstructured magnitude pruning of a list of tensors, in place: the k = floor(ratio N) smallest magnitudes of the
+    whole list become +0.0 (k from the shapes alone: nothing is read back) -> (mask, sel) of prune_mask / magnitude_select."""
+    n = prune_args("magnitude_prune_", tensors, ratio)
+    sel = magnitude_select(tensors, min(n, int(math.floor(ratio * n))))
+    mask = prune_mask(tensors, sel)
+    prune_apply_(tensors, mask)
+    return mask, sel
+
+
+def prune_counts(tensors, mask):
+    """pruned elements per tensor according to the mask (a host list: one read-back, for the logs)"""
+    bits = ((mask.view(torch.uint8)[:, None] >> torch.arange(8, device=mask.device, dtype=torch.uint8)) & 1).sum(1).view(-1, 8).sum(1)
+    out, w0 = [], 0
+    for t in tensors:
+        nw = (t.numel() + 63) // 64
+        out.append(t.numel() - int(bits[w0:w0 + nw].sum()))
+        w0 += nw
+    return out
