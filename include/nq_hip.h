@@ -726,6 +726,42 @@ NQ_API int64_t nq_msssim_loss_ws_floats(int B, int C, int H, int W);
 NQ_API int nq_msssim_loss(const float* pred, const float* tgt, float* loss3, float* grad, float* ws, int B, int C, int H, int W,
                    float w_mse, float w_ms, float grad_scale, nq_stream_t stream);
 
+/* ---- absolute-error objectives: w_abs mean |d|^p + w_mse mean d^2 with its gradient (additive:
+ * nq_abi_version() stays 7) ----
+ * The reference's `l1`, `Fusion7`, `Fusion8` losses (utils.py:117-136), lp_loss(p) of its calibration (--norm_p), and, in
+ * accumulate mode behind nq_ssim_loss / nq_ssim_loss_head / nq_msssim_loss, the L1 term of `Fusion2/4/6/9/10/11/12`.
+ * pred (B, C, H, W) fp32; the target is exactly one of `tgt` (B, C, H, W) fp32 and `cache_u8` (N, C, H, W) + idx[B] on the
+ * device: tgt = cache[idx[b]] / 255 in the arithmetic of nq_gather_frames_u8, converted on load (no float copy is written;
+ * the VALUES of idx are the caller's responsibility, as for nq_ssim_loss_head).  With d = pred - tgt and n = B C H W:
+ *   A = sum |d|^p / n,  M = sum d^2 / n,  L = w_abs A + w_mse M
+ *   dL/dpred = (w_abs p |d|^(p-1) sign(d) + w_mse 2 d) / n,  sign(0) = 0: an element with pred == tgt exactly gets exactly 0
+ *   (what autograd gives for abs().pow(p)).
+ *   accumulate == 0: loss3[3] = {scale L (the float L times scale, one more rounding), A, M}.  A term whose weight is 0 is not
+ *   computed and its entry of loss3 is 0 -- except p == 2, where the absolute term IS the squared error: one sum, A = M.
+ *   grad == NULL: forward only.
+ *   db == NULL: grad (B, C, H, W) = scale dL/dpred.
+ *   db != NULL (pred = tanh(conv) * 0.5 + 0.5; grad must be given): grad = that value * 0.5 * (1 - (2 pred - 1)^2), the gradient
+ *   at the head conv's output, bit-identical to nq_tanh_out_backward of the db == NULL result; db[C] = its sums over frames and
+ *   pixels (per workgroup in double, stored as one float; the finishing launch adds those per channel, frame by frame, in double).
+ *   accumulate != 0: loss3[0], every element of grad and every db[c] get the value above ADDED in place (one more rounding
+ *   each; grad is read once more); loss3[1] and loss3[2] are left alone.  On the stream behind nq_ssim_loss,
+ *   nq_ssim_loss_head or nq_msssim_loss this adds the L1 term of a fusion loss with no host read; in head mode that is exact
+ *   up to the rounding, because the head backward is linear in the image gradient.
+ * p == 1 evaluates no transcendental; general p evaluates the accurate powf once per element, |d|^(p-1), and gets |d|^p by one
+ * multiply.  Two launches: a streaming one (a workgroup owns 4096 consecutive elements of one (frame, channel) plane -- any H, W:
+ * a chunk's unaligned head and tail run on scalar lanes -- and leaves one float partial sum per term) and a finishing one that
+ * adds the partial sums in index order in double (1 + C workgroups with db).  No atomics, nothing allocated, no host read:
+ * bit-identical from call to call, capturable in a hipGraph.
+ *   ws: nq_lp_loss_ws_floats(B, C, H, W) floats = 3 B C ceil(H W / 4096) (0 for sizes the entry refuses).
+ * NQ_ERR_INVALID, before the device is touched, for null pred / loss3 / ws, both or neither target, a cache without idx, db
+ * without grad (accumulate mode included), non-positive sizes, p < 1 or non-finite (below 1 the gradient is singular at d = 0),
+ * a negative or non-finite weight, both weights zero, a non-finite scale and an element count past int64; NQ_ERR_UNSUPPORTED for
+ * more than 2^31 - 1 chunks. */
+NQ_API int64_t nq_lp_loss_ws_floats(int B, int C, int H, int W);
+NQ_API int nq_lp_loss(const float* pred, const float* tgt, const uint8_t* cache_u8, const int64_t* idx, float* loss3, float* grad,
+               float* db, float* ws, int B, int C, int H, int W, float p, float w_abs, float w_mse, float scale, int accumulate,
+               nq_stream_t stream);
+
 /* Entropy-coded levels: 64-lane interleaved rANS, one frequency table per tensor (probabilities in units of
  * 1 / 4096), 32-bit states >= 2^16, 16-bit words.  The n levels (flat, C order) are cut into chunks of `chunk` symbols (a
  * multiple of 64, the last may be short); lane l of a chunk owns its symbols l, l + 64, ...  One wavefront decodes one chunk.

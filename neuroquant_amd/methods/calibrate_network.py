@@ -16,7 +16,9 @@ the definition of pytorch_msssim.ms_ssim; last-bit parity with that pip package 
     --loss_domain yuv420 (--yuv_weights WY WU WV, default 6 1 1; matrix and range from --yuv_matrix / --yuv_range: §19),
     --rec_loss ssim | Fusion1 | Fusion3 | Fusion5 or --rec_weights W_MSE W_SSIM (the reference's MSE + (1 - SSIM) losses: §21),
     --rec_loss msssim or --rec_ms_weights W_MSE W_MS (1 - MS-SSIM; frames whose smaller side exceeds 160: §22); every evaluation
-    then also logs the figure that objective is after;
+    then also logs the figure that objective is after; --norm_p P (the reference's flag; default 2, the squared error) with
+    P >= 1, P != 2 calibrates on lp_loss(P) = (pred - tgt).abs().pow(P).sum(1).mean() in both phases (csrc/lp_loss.hip: §32), on
+    its own: not beside --rec_loss / --rec_weights / --rec_ms_weights / --loss_domain yuv420, and P < 1 is refused;
     --export_stream FILE.nqv also writes the calibrated model as a bit stream that
     `python -m neuroquant_amd.methods.decode_stream` plays back; --stream_coding packed | rans | auto chooses between levels
     packed at their bit-width and entropy-coded levels, --stream_encoder host | gpu who encodes them (numpy, or the HIP encoder
@@ -75,7 +77,8 @@ def parse_args(argv):
     p.add_argument('--warmup', default=0.2, type=float)
     p.add_argument('--input_prob', default=1.0, type=float)
     p.add_argument('--lr', default=0.0015, type=float)
-    p.add_argument('--norm_p', default=2.0, type=float)
+    p.add_argument('--norm_p', default=2.0, type=float,
+                   help='p of the reconstruction loss lp_loss(p): 2 = squared error; any other p >= 1 runs on csrc/lp_loss.hip (DESIGN.md §32)')
     p.add_argument('--init', default='max', type=str, choices=['max', 'mse', 'gaussian', 'l1', 'l2'])
     p.add_argument('--opt_mode', default='mse', type=str, choices=['mse', 'fisher_diag', 'fisher_full', 'lp_norm'])
     p.add_argument('--ckpt', default='None', type=str)
@@ -196,6 +199,13 @@ def objective_of(args):
     elif name != 'l2':
         raise ValueError(f"rec_loss must be one of {['l2'] + list(SSIM_LOSSES)}, got {name!r}")
     yuv420 = getattr(args, 'loss_domain', 'rgb') == 'yuv420'
+    norm_p = getattr(args, 'norm_p', 2.0)
+    if norm_p != 2.0:   # the reference's lp_loss(p): the 'lp' objective; p < 1 stops in its check, with the reason
+        lp = objective.resolve('lp', dict(p=norm_p), '--norm_p')
+        if name != 'l2' or yuv420:
+            raise ValueError(f'--norm_p {norm_p} asks for lp_loss(p) on RGB frames: it does not combine with --rec_loss, --rec_weights, '
+                             '--rec_ms_weights or --loss_domain yuv420 (--norm_p 2 does)')
+        return lp
     if name == 'l2':
         return objective.resolve('yuv420', yuv_loss_params(args), '--loss_domain yuv420') if yuv420 else objective.resolve('l2')
     keys = tuple(objective.TABLE[name]['defaults'])

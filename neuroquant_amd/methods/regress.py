@@ -1,7 +1,8 @@
 """FP32 INR trainer (counterpart of the reference's methods/regress.py:151-322; SURVEY §8f-4, a "next" row).
 
 Same flags and schedule (Adam, weight_decay 0, `--lr_type cosine_0.1_1_0.1` / hybrid, a config's `loss:` = one objective of
-objective.TABLE: `l2`, `yuv420`, the reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5`, or `msssim`, per-epoch
+objective.TABLE: `l2`, `yuv420`, the reference's `ssim` / `Fusion1` / `Fusion3` / `Fusion5`, `msssim`, or `lp`
+(`loss_p: P`, `loss_weights: [W_ABS, W_MSE]`: the absolute-error losses on csrc/lp_loss.hip), per-epoch
 `model_latest.pth`, final `epoch{N}.pth` state_dicts that `calibrate_network` loads).  The decoder runs as the fused
 HIP stack (`ops.decoder_stack`: implicit-GEMM convs, fused PixelShuffle/GELU/tanh, data/weight gradients), frames come
 from the GPU-resident cache; Adam and, by default, the ConvNeXt encoder stay in PyTorch (`--enc_kernels hip` runs the
@@ -191,10 +192,18 @@ def loss_params(args, cfg):
     """cfg['loss'] -> None for 'l2', the keywords of ops.yuv420_loss for 'yuv420' (the weighted plane MSEs of the 8-bit YUV
     4:2:0 codes; --yuv_matrix, --yuv_range, --yuv_weights; evaluations then also report PSNR-Y / U / V), the keywords of
     ops.ssim_loss for 'ssim' / 'Fusion1' / 'Fusion3' / 'Fusion5' (DESIGN.md §20), dict(w_mse, w_ms) of ops.ms_ssim_loss for
-    'msssim' (weights (0, 1), or the config's `loss_weights: [W_MSE, W_MS]`); anything else raises."""
+    'msssim' (weights (0, 1), or the config's `loss_weights: [W_MSE, W_MS]`), dict(p, w_abs, w_mse) of ops.lp_loss
+    for 'lp' (the config's `loss_p: P`, default 1, and `loss_weights: [W_ABS, W_MSE]`, default (1, 0): w_abs * mean |d|^p + w_mse *
+    MSE, i.e. the reference's `l1` = (1, [1, 0]), `Fusion7` = (1, [0.3, 0.7]), `Fusion8` = (1, [0.5, 0.5])); anything
+    else raises."""
     loss_name = cfg.get('loss', 'l2')
     if loss_name == 'l2':
         return None
+    if loss_name == 'lp':
+        w = cfg.get('loss_weights', (1.0, 0.0))
+        if not isinstance(w, (list, tuple)) or len(w) != 2:
+            raise ValueError(f'loss_weights takes [W_ABS, W_MSE], got {w!r}')
+        return objective.resolve('lp', dict(p=cfg.get('loss_p', 1.0), w_abs=w[0], w_mse=w[1]), 'loss_p / loss_weights').params
     if loss_name == MSSSIM_LOSS:
         w = cfg.get('loss_weights', MSSSIM_WEIGHTS)
         if not isinstance(w, (list, tuple)) or len(w) != 2:

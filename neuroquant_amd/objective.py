@@ -71,11 +71,28 @@ TABLE = {
 }
 
 
+def _lp_check(what, p):   # the ops validator on the smallest legal probe shape (any shape is legal: one element)
+    return dict(zip(p, ops.lp_loss_args(what, (1, 1, 1, 1), (1, 1, 1, 1), *p.values())))
+
+
+# The p-norm form of the squared-error objective: C * (w_abs * mean |d|^p + w_mse * MSE), the reference's
+# lp_loss(p) for (p, 1, 0).  It has the shape of a TABLE entry and resolves by the name 'lp', but it is chosen by
+# model_reconstruction(p=) / --norm_p (and `loss: lp` of a trainer config), not by one of the engine's keyword dicts, so it
+# stands beside the table of the keyword-selected objectives.
+LP = dict(defaults=dict(p=1.0, w_abs=1.0, w_mse=0.0), exact=True, check=_lp_check, excludes=('yuv420', 'ssim', 'msssim'),
+          title='absolute error', head_grad=ops.lp_loss_head_grad, rec=0, loss=ops.lp_loss, lp_mul=lambda C: C, step_div=None,
+          fused_head=False, log='reconstruction loss: C * (w_abs * mean |d|^p + w_mse * MSE), {}', frame=None, report=None)
+
+
+def _entry(name):
+    return LP if name == 'lp' else TABLE[name]
+
+
 class Objective:
     """One resolved objective: `name`, validated `params`, and what the loops call."""
 
     def __init__(self, name, params):
-        e = TABLE[name]
+        e = _entry(name)
         self.name, self.params, self.entry = name, params, e
         self._head_grad = functools.partial(e['head_grad'], **params)
         self._loss = functools.partial(e['loss'], **params)
@@ -108,9 +125,10 @@ class Objective:
         return loss if div is None else loss / div(tgt.shape[1])
 
     def engine_kwargs(self):
-        """the keywords of model_reconstruction that ask for this objective (from_kwargs reads them back)"""
+        """the keywords of model_reconstruction that ask for this objective (from_kwargs reads them back); 'lp' is asked for by
+        the engine's own p= (the driver's --norm_p), which is not among them"""
         kw = dict(loss_domain='yuv420' if self.name == 'yuv420' else 'rgb', yuv=None, ssim=None, msssim=None)
-        if self.name != 'l2':
+        if self.name not in ('l2', 'lp'):
             kw['yuv' if self.name == 'yuv420' else self.name] = dict(self.params)
         return kw
 
@@ -126,31 +144,38 @@ class Objective:
 
 def resolve(name, params=None, what='model_reconstruction'):
     """-> Objective `name` with `params` over its defaults; ValueError for an unknown name, unknown keys or bad values"""
-    if name not in TABLE:
-        raise ValueError(f'objective must be one of {list(TABLE)}, got {name!r}')
-    e = TABLE[name]
+    if name not in TABLE and name != 'lp':
+        raise ValueError(f"objective must be one of {list(TABLE) + ['lp']}, got {name!r}")
+    e = _entry(name)
     params = dict(params or {})
     if set(params) - set(e['defaults']):
         raise ValueError(f"{name} takes {', '.join(e['defaults']) or 'no parameters'}, got {sorted(params)}")
     return Objective(name, e['check'](what, dict(e['defaults'], **params)))
 
 
-def from_kwargs(loss_domain='rgb', yuv=None, ssim=None, msssim=None, what='model_reconstruction'):
-    """The objective model_reconstruction's keywords ask for; bad keys, bad values and what does not combine stop here."""
+def from_kwargs(loss_domain='rgb', yuv=None, ssim=None, msssim=None, what='model_reconstruction', p=2.0):
+    """The objective model_reconstruction's keywords ask for; bad keys, bad values and what does not combine stop here.
+    p != 2 (the engine's p=, --norm_p) asks for 'lp' with (p, 1, 0), the reference's lp_loss(p): p < 1 is refused, and so is p != 2
+    beside any other objective."""
     if loss_domain not in ('rgb', 'yuv420'):
         raise ValueError(f"loss_domain must be 'rgb' or 'yuv420', got {loss_domain!r}")
     yuv = dict(yuv or {})
     if set(yuv) - set(TABLE['yuv420']['defaults']):
         raise ValueError(f"yuv takes matrix, full_range and weights, got {sorted(yuv)}")
-    asked = {n: p for n, p in (('yuv420', yuv if loss_domain == 'yuv420' else None), ('ssim', ssim), ('msssim', msssim)) if p is not None}
-    for n, p in asked.items():
+    asked = {n: q for n, q in (('yuv420', yuv if loss_domain == 'yuv420' else None), ('ssim', ssim), ('msssim', msssim)) if q is not None}
+    for n, q in asked.items():
         e = TABLE[n]
-        if e['exact'] and (not isinstance(p, dict) or set(p) != set(e['defaults'])):
-            raise ValueError(f"{n} takes dict({', '.join(e['defaults'])}), got {sorted(p) if isinstance(p, dict) else p!r}")
+        if e['exact'] and (not isinstance(q, dict) or set(q) != set(e['defaults'])):
+            raise ValueError(f"{n} takes dict({', '.join(e['defaults'])}), got {sorted(q) if isinstance(q, dict) else q!r}")
         for other in e['excludes']:
             if other in asked:
                 raise ValueError(f"the {e['title']} objective is defined on RGB frames: it does not combine with loss_domain 'yuv420'"
                                  if other == 'yuv420' else f"{n} and {other} are two objectives: give one")
+    if p != 2.0:
+        lp = resolve('lp', dict(p=p), what + '(p=)')   # p < 1 or not a finite number stops here, with the reason
+        if asked:
+            raise ValueError(f"p = {p!r} asks for the {LP['title']} objective: it does not combine with {', '.join(asked)} (p = 2 does)")
+        return lp
     name = next(reversed(asked), 'l2')
     return resolve(name, asked.get(name), what)
 
@@ -162,7 +187,7 @@ def of_params(params, what='loss'):
         return params
     if params is None:
         return resolve('l2', None, what)
-    for name, e in TABLE.items():
+    for name, e in list(TABLE.items()) + [('lp', LP)]:
         if e['defaults'] and set(params) == set(e['defaults']):
             return resolve(name, params, what)
     raise ValueError(f'no objective takes the parameters {sorted(params)}')

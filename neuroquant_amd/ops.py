@@ -2075,12 +2075,16 @@ def ssim_loss_raw(pred, tgt, w_mse, w_ssim, want_grad=True):
     return loss3, grad
 
 
-def ssim_loss(pred, tgt, w_mse=0.0, w_ssim=1.0):
-    """Differentiable L of ssim_loss_raw (w.r.t. `pred`): the reference's per-frame loss followed by .mean()."""
-    w_mse, w_ssim = float(w_mse), float(w_ssim)
+def ssim_loss(pred, tgt, w_mse=0.0, w_ssim=1.0, w_l1=0.0):
+    """Differentiable L of ssim_loss_raw (w.r.t. `pred`): the reference's per-frame loss followed by .mean().  w_l1 > 0 adds
+    w_l1 * mean |pred - tgt| (the reference's Fusion2 / 4 / 6 / 9): one accumulate-mode nq_lp_loss behind the SSIM launches;
+    w_l1 = 0 launches what it always launched."""
+    w_mse, w_ssim, w_l1 = float(w_mse), float(w_ssim), _l1_weight("ssim_loss", w_l1)
 
     def launch(pred, tgt, want_grad):
         loss3, grad = ssim_loss_raw(pred, tgt, w_mse, w_ssim)
+        if w_l1 > 0.0:
+            lp_loss_raw(pred, tgt=tgt, w_abs=w_l1, into=(loss3, grad, None))
         return loss3[0].clone(), grad
     return _ScalarLossFn.apply(pred, tgt, launch)
 
@@ -2114,13 +2118,17 @@ def ssim_loss_head_raw(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ssi
     return loss3, grad, db
 
 
-def ssim_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ssim=1.0, node=None):
+def ssim_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, w_mse=0.0, w_ssim=1.0, node=None, w_l1=0.0):
     """l2_loss_head_grad for the MSE + SSIM objective: -> (loss3, g) where `pred.backward(g)` (or decoder_backward_steps(node,
     g)) continues the backward pass.  When `pred` carries the hand-over slot of a tanh-headed decoder node, g is the
     gradient at the head conv's OUTPUT and the head's bias gradient is handed over with it; otherwise g = C * dL/dpred and the
-    ordinary backward runs.  Never None: the kernel has no tiling restriction."""
+    ordinary backward runs.  Never None: the kernel has no tiling restriction.  w_l1 > 0 adds C * w_l1 * mean |pred - tgt| to
+    loss3[0], its gradient to g and to the bias gradient: one accumulate-mode nq_lp_loss behind the SSIM launches."""
+    w_l1 = _l1_weight("ssim_loss_head_grad", w_l1)
     head = _handoff(pred, node)
     loss3, g, db = ssim_loss_head_raw(pred, tgt, cache_u8, idx, w_mse, w_ssim, head=head is not None)
+    if w_l1 > 0.0:
+        lp_loss_raw(pred, tgt, cache_u8, idx, w_abs=w_l1, scale=float(pred.shape[1]), into=(loss3, g, db))
     return loss3, (g if head is None else _hand_over(head, g, db))
 
 
@@ -2145,26 +2153,31 @@ def ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=True):
     return loss3, grad
 
 
-def ms_ssim_loss(pred, tgt, w_mse=0.0, w_ms=1.0):
+def ms_ssim_loss(pred, tgt, w_mse=0.0, w_ms=1.0, w_l1=0.0):
     """Differentiable L of ms_ssim_loss_raw (w.r.t. `pred`).  Where `pred` needs no gradient (torch.no_grad, a detached image) the
-    call is forward only: six launches, no derivative maps, the same loss bits."""
-    w_mse, w_ms = float(w_mse), float(w_ms)
+    call is forward only: six launches, no derivative maps, the same loss bits.  w_l1 > 0 adds w_l1 * mean |pred - tgt| (the
+    reference's Fusion10 / 11 / 12): one accumulate-mode nq_lp_loss behind the MS-SSIM launches."""
+    w_mse, w_ms, w_l1 = float(w_mse), float(w_ms), _l1_weight("ms_ssim_loss", w_l1)
 
     def launch(pred, tgt, want_grad):
         loss3, grad = ms_ssim_loss_raw(pred, tgt, w_mse, w_ms, want_grad=want_grad)
+        if w_l1 > 0.0:
+            lp_loss_raw(pred, tgt=tgt, w_abs=w_l1, into=(loss3, grad, None))
         return loss3[0].clone(), grad
     return _ScalarLossFn.apply(pred, tgt, launch)
 
 
-def msssim_loss_head_grad(img_out, tgt=None, cache_u8=None, idx=None, node=None, w_mse=0.0, w_ms=1.0):
+def msssim_loss_head_grad(img_out, tgt=None, cache_u8=None, idx=None, node=None, w_mse=0.0, w_ms=1.0, w_l1=0.0):
     """ssim_loss_head_grad for the MSE + MS-SSIM objective: -> (loss3, dimg) with loss3 = (C * L, mean MSE, mean MS-SSIM) (the
     factor C puts weights (1, 0) on the scale of lp_loss(p = 2)) and `img_out.backward(dimg)` (or decoder_backward_steps(node,
     dimg)) continuing the backward pass.  The target is `tgt` or the frames `cache_u8[idx] / 255`, gathered by
     nq_gather_frames_u8.  With the hand-over slot of a tanh-headed decoder node, dimg is the gradient at the head conv's OUTPUT
     (nq_tanh_out_backward of C * dL/dimg) and the head's bias gradient (nq_channel_sum of it) is handed over with it; otherwise
     dimg = C * dL/dimg.  There is no fused head variant of this kernel.  Everything stays on the stream, nothing is read by the
-    host.  ValueError for a bad shape, target or weights before any launch."""
+    host.  ValueError for a bad shape, target or weights before any launch.  w_l1 > 0 adds C * w_l1 * mean |img_out - tgt|:
+    one accumulate-mode nq_lp_loss on loss3[0] and on the image gradient, in front of the tanh backward."""
     global msssim_loss_head_launches
+    w_l1 = _l1_weight("msssim_loss_head_grad", w_l1)
     if not isinstance(img_out, torch.Tensor):
         raise ValueError(f"msssim_loss_head_grad takes (B, C, H, W) images, got {type(img_out)}")
     w = ms_ssim_loss_args("msssim_loss_head_grad", img_out.shape, img_out.shape, w_mse, w_ms)
@@ -2177,6 +2190,8 @@ def msssim_loss_head_grad(img_out, tgt=None, cache_u8=None, idx=None, node=None,
     msssim_loss_head_launches += 1
     loss3, g, _ = _mse_plus_launch("msssim_loss", "msssim_loss_head_grad", img_out, tgt, w[0], w[1], True, grad_scale=float(C))
     loss3[:1].mul_(float(C))       # the float L times C, one more rounding, on the stream
+    if w_l1 > 0.0:
+        lp_loss_raw(img_out, tgt=tgt, w_abs=w_l1, scale=float(C), into=(loss3, g, None))
     head = _handoff(img_out, node)
     if head is None:
         return loss3, g
@@ -2184,6 +2199,99 @@ def msssim_loss_head_grad(img_out, tgt=None, cache_u8=None, idx=None, node=None,
     dconv = torch.empty_like(g)
     L.check(L.lib().nq_tanh_out_backward(_p(g), _p(img_d), _p(dconv), g.numel(), _stream()), "tanh_backward")
     return loss3, _hand_over(head, dconv, channel_sum(dconv))
+
+
+# ---- absolute-error objectives: w_abs * mean |d|^p + w_mse * mean d^2 (include/nq_hip.h: nq_lp_loss) ----
+LP_LOSS_CHUNK = 4096      # consecutive elements of one (frame, channel) plane a workgroup of csrc/lp_loss.hip owns: the tests' edge shapes
+lp_loss_launches = 0      # nq_lp_loss calls issued (or captured) by this process: the default paths issue none
+
+
+def _l1_weight(what, w_l1):
+    """-> the weight of an L1 term behind an SSIM / MS-SSIM loss as a float; ValueError naming `what`"""
+    try:
+        w = float(w_l1)
+    except (TypeError, ValueError):
+        w = math.nan
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"{what}: w_l1 must be a finite number >= 0, got {w_l1!r}")
+    return w
+
+
+def lp_loss_args(what, pred_shape, tgt_shape, p, w_abs, w_mse):
+    """-> (p, w_abs, w_mse) as floats; ValueError naming `what` before anything is launched"""
+    if len(pred_shape) != 4 or min(pred_shape) <= 0:
+        raise ValueError(f"{what} takes non-empty (B, C, H, W) images, got {tuple(pred_shape)}")
+    if tuple(tgt_shape) != tuple(pred_shape):
+        raise ValueError(f"{what}: pred {tuple(pred_shape)} and tgt {tuple(tgt_shape)} differ")
+    try:
+        pf = float(p)
+    except (TypeError, ValueError):
+        pf = math.nan
+    if not (math.isfinite(pf) and pf >= 1.0):
+        raise ValueError(f"{what}: p must be a finite number >= 1 (below 1 the gradient of |d|^p is singular at d = 0: the reference "
+                         f"gives NaN where pred == tgt), got {p!r}")
+    return (pf,) + _loss_weights(what, (w_abs, w_mse), 2)
+
+
+def lp_loss_raw(pred, tgt=None, cache_u8=None, idx=None, p=1.0, w_abs=1.0, w_mse=0.0, scale=1.0, want_grad=True, head=False,
+                into=None):
+    """One nq_lp_loss call on images `pred` (B, C, H, W), any H, W -> (loss3, grad, db): loss3 = (scale * L, A, M) with A = mean
+    |pred - tgt|^p, M = mean (pred - tgt)^2 over all elements and L = w_abs * A + w_mse * M (a term of weight 0 is not computed and
+    reads 0; p = 2: A = M); the target is `tgt` or frames `cache_u8[idx] / 255` read straight from the uint8 cache.  head=False:
+    grad = scale * dL/dpred (None with want_grad=False), db = None; an element with pred == tgt has a gradient of exactly 0.
+    head=True (`pred` = tanh(conv) * 0.5 + 0.5): grad = the gradient at the conv OUTPUT and db its per-channel sums, as
+    ssim_loss_head_raw.  into=(loss3, grad or None, db or None), the results of an earlier loss launch on the same images: the
+    values are ADDED to loss3[0], grad and db in place (loss3[1:] stay) and `into` is returned; head mode is db is not None.
+    Bit-identical from call to call.  ValueError for a bad shape, target, p or weights before any launch; the VALUES of idx stay on
+    the device, unchecked, as for ssim_loss_head_raw."""
+    global lp_loss_launches
+    if not isinstance(pred, torch.Tensor):
+        raise ValueError(f"lp_loss takes (B, C, H, W) images, got {type(pred)}")
+    pf, wa, wm = lp_loss_args("lp_loss", pred.shape, pred.shape, p, w_abs, w_mse)
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"lp_loss: scale must be finite, got {scale!r}")
+    tgt, cache_u8, idx = _loss_target("lp_loss", pred, tgt, cache_u8, idx, typed=True)
+    pred_d = _dev(pred.detach(), "pred")
+    B, C, H, W = pred_d.shape
+    if into is None:
+        loss3 = torch.empty(3, device=pred_d.device, dtype=torch.float32)
+        grad = torch.empty_like(pred_d) if (want_grad or head) else None
+        db = torch.empty(C, device=pred_d.device, dtype=torch.float32) if head else None
+    else:
+        loss3, grad, db = into
+        ok = loss3.is_contiguous() and (grad is None or (grad.is_contiguous() and grad.shape == pred_d.shape)) and \
+            (db is None or (grad is not None and db.is_contiguous() and db.numel() == C))
+        if not ok or any(t is not None and (not t.is_cuda or t.dtype != torch.float32) for t in into):
+            raise ValueError("lp_loss: into takes (loss3, grad or None, db or None): contiguous float32 GPU tensors of the image's shape")
+    ws = torch.empty(_q("nq_lp_loss_ws_floats", B, C, H, W), device=pred_d.device, dtype=torch.float32)
+    lp_loss_launches += 1
+    L.check(_timed("lp_loss", lambda: L.lib().nq_lp_loss(
+        _p(pred_d), _p(tgt), _p(cache_u8), _p(idx), _p(loss3), _p(grad), _p(db), _p(ws), B, C, H, W, pf, wa, wm, scale,
+        int(into is not None), _stream())), "lp_loss")
+    return loss3, grad, db
+
+
+def lp_loss(pred, tgt, p=1.0, w_abs=1.0, w_mse=0.0):
+    """Differentiable L of lp_loss_raw (w.r.t. `pred`): w_abs * mean |pred - tgt|^p + w_mse * mean (pred - tgt)^2, the reference's
+    `l1` (1, 1, 0), `Fusion7` (1, 0.3, 0.7) and `Fusion8` (1, 0.5, 0.5); times C it is the reference's lp_loss(p) for (p, 1, 0)."""
+    p, w_abs, w_mse = lp_loss_args("lp_loss", pred.shape, tgt.shape, p, w_abs, w_mse)
+
+    def launch(pred, tgt, want_grad):
+        loss3, grad, _ = lp_loss_raw(pred, tgt=tgt, p=p, w_abs=w_abs, w_mse=w_mse, want_grad=want_grad)
+        return loss3[0].clone(), grad
+    return _ScalarLossFn.apply(pred, tgt, launch)
+
+
+def lp_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, node=None, p=1.0, w_abs=1.0, w_mse=0.0):
+    """ssim_loss_head_grad for the absolute-error objective: -> (loss3, g) with loss3 = (C * L, A, M) (the factor C puts (p, 1, 0) on
+    the scale of the reference's lp_loss(p)) and `pred.backward(g)` (or decoder_backward_steps(node, g)) continuing the backward
+    pass.  With the hand-over slot of a tanh-headed decoder node, g is the gradient at the head conv's OUTPUT and the head's bias
+    gradient is handed over with it; otherwise g = C * dL/dpred.  Never None: the kernel takes every shape."""
+    head = _handoff(pred, node)
+    C = pred.shape[1] if isinstance(pred, torch.Tensor) and pred.dim() == 4 else 1
+    loss3, g, db = lp_loss_raw(pred, tgt, cache_u8, idx, p, w_abs, w_mse, scale=float(C), head=head is not None)
+    return loss3, (g if head is None else _hand_over(head, g, db))
 
 
 def ssim(out, gt):

@@ -197,13 +197,17 @@ def model_reconstruction(model: QuantModel, cali_data: torch.Tensor, gt, arch: s
     rate=None, and rate=None launches nothing new.  The term is gated like the regulariser (off during the warm-up), is local to
     a rank (not reduced: replicas stay identical) and combines with every objective above.  A second log line follows the
     'Total loss' line: 'rate: lambda*bpp .., soft .. bits, hard .. bytes'.
+    p (the reference's --norm_p): 2 is lp_loss(p=2), the squared error, and launches what it always launched; any other p >= 1
+    takes the 'lp' objective, lp_loss(p) = (pred - tgt).abs().pow(p).sum(1).mean() with its gradient on csrc/lp_loss.hip, in both
+    phases.  p < 1 is a ValueError (the gradient is singular where pred == tgt), and p != 2 combines with none of
+    loss_domain "yuv420", ssim and msssim.
     """
     if arch not in ('hnerv', 'nerv'):
         raise ValueError
-    if opt_mode != 'mse' or p != 2.0:
-        raise NotImplementedError('only opt_mode="mse", p=2 is on the calibration path')
-    # bad keys, bad weights and what does not combine stop here, before the first iteration
-    obj = objective.from_kwargs(loss_domain, yuv, ssim, msssim)
+    if opt_mode != 'mse':
+        raise NotImplementedError('only opt_mode="mse" is on the calibration path')
+    # bad keys, bad weights, p < 1 and what does not combine stop here, before the first iteration
+    obj = objective.from_kwargs(loss_domain, yuv, ssim, msssim, p=p)
     rate = objective.rate_kwarg(rate)
     model.set_quant_state(True)
     device = next(model.parameters()).device

@@ -24,9 +24,12 @@ class StraightThrough(nn.Module):
 
 
 def lp_loss(pred, tgt, p=2.0, reduction='none'):
-    """reference quantizer.py:66-73.  p=2 / reduction='none' (the calibration loss) runs in one HIP kernel."""
+    """reference quantizer.py:66-73.  reduction='none' (the calibration loss) runs in one HIP kernel on the GPU: p=2 on nq_l2_loss,
+    any other p >= 1 on nq_lp_loss (4-d images)."""
     if reduction == 'none' and p == 2.0 and pred.is_cuda:
         return ops.l2_loss(pred, tgt)
+    if reduction == 'none' and pred.is_cuda and pred.dim() == 4 and p >= 1.0:
+        return ops.lp_loss(pred, tgt, p=p) * pred.shape[1]
     if reduction == 'none':
         return (pred - tgt).abs().pow(p).sum(1).mean()
     return (pred - tgt).abs().pow(p).mean()
