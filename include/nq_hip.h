@@ -1086,6 +1086,53 @@ NQ_API int nq_magnitude_select(const nq_prune_seg* segs, int nseg, const int64_t
 NQ_API int nq_prune_mask(const nq_prune_seg* segs, int nseg, const int64_t* sel, uint64_t* mask, void* ws, nq_stream_t stream);
 NQ_API int nq_prune_apply(const nq_prune_seg* segs, int nseg, const uint64_t* mask, nq_stream_t stream);
 
+/* ---- Unit-wise reconstruction: the loss of one layer / block on its output activation, with the gradient at the unit's
+ * convolution output, and the QDrop input mix (csrc/unit_rec.hip; additive: nq_abi_version() stays 7) ----
+ * The reference's layer-wise and block-wise calibration (quantization/calib_layer.py, calib_block.py: LossFunction).
+ * pred (B, C, H r, W r) fp32: the unit's output; H, W are the sizes of the unit's CONVOLUTION output, r its PixelShuffle factor
+ * (1 .. 5; 1: none).  tgt: the FP output, read as tgt[idx[b]] from a cache (N, C, H r, W r) of fp32 entries when idx (device
+ * int64[B]) is given, as a plain (B, C, H r, W r) tensor when idx == NULL; the VALUES of idx are the caller's responsibility, as
+ * for nq_lp_loss.  fisher: the Fisher weights g (the reference stores |grad| + 1), same shape and the SAME idx convention; needed
+ * by the two fisher modes, ignored by NQ_UNIT_LP.  z (B, C, H r, W r) or NULL: the derivative a NQ_EPI_PS_GELU forward saved; NULL:
+ * no activation (with r == 1 a bare layer).  z is taken with ANY r, r == 1 included (a GELU block without PixelShuffle): no
+ * combination of z and r is refused.  With d = pred - tgt, count = B H r W r, n = C count:
+ *   NQ_UNIT_LP           L = sum |d|^p / count              (lp_loss: sum over channels, mean over the rest; p >= 1)
+ *                        dL/dpred = p |d|^(p-1) sign(d) / count, sign(0) = 0: pred == tgt gives exactly 0.  p == 2 and p == 1
+ *                        evaluate no transcendental; p == 2 forms the float k d with k = (float)(C p / n), the float that
+ *                        nq_lp_loss (image mode, scale C) stores.
+ *   NQ_UNIT_FISHER_DIAG  L = sum d^2 g^2 / count,           dL/dpred = (k d) g^2, k = (float)(2 / count)
+ *   NQ_UNIT_FISHER_FULL  a = |d|, s_b = sum_{c,h,w} a |g|,  L = sum_b s_b^2 / (100 n)   (= mean(s_b a |g|) / 100)
+ *                        dL/dpred = (float)(2 s_b / (100 n)) |g| sign(d)
+ *   loss[0] = L;  dconv (B, C r^2, H, W) = PixelUnshuffle_r(dL/dpred * z): dconv[b, c r^2 + i r + j, y, x] = (dL/dpred z)[b, c,
+ *   y r + i, x r + j], the output gradient of the unit's convolution as nq_conv_wgrad reads it; for NQ_UNIT_LP, p == 2 bit-identical
+ *   to nq_ps_gelu_backward of nq_lp_loss's image-mode gradient.
+ * Launches: the streaming one (a workgroup owns the r rows of one (b, c) plane behind one output row; r == 1: a run of whole
+ * rows, about 4096 floats) and a finishing one that adds the one double per workgroup in index order; NQ_UNIT_FISHER_FULL: the
+ * per-sample dots first (at most 256 workgroups per sample, fixed chunk order), then the streaming one, which adds them in index
+ * order and writes the loss.  16-byte accesses where W r % 4 == 0 (loads), W % 4 == 0 (stores) and the tensors are 16-byte
+ * aligned, one float per lane otherwise: any H, W >= 1.  No atomics, nothing allocated, no host read: bit-identical from call to
+ * call, capturable in a hipGraph.
+ *   ws: nq_unit_rec_loss_ws_floats(B, C, H, W, r) floats, 8-byte aligned (0 for sizes the entry refuses).
+ * NQ_ERR_INVALID, before the device is touched: a null pred / tgt / loss / dconv / ws, fisher missing in a fisher mode, a
+ * non-positive size, r outside 1 .. 5, an unknown mode, NQ_UNIT_LP with p < 1 or non-finite, a misaligned ws, dconv aliasing an
+ * input, an element count past int64; NQ_ERR_UNSUPPORTED for more than 2^31 - 1 workgroups.
+ *
+ * nq_qdrop_mix (QDrop, calib_block.py:161-164): x (B, n) [b, i] = u_bi < prob ? xq_cache[idx[b], i] : xfp_cache[idx[b], i]; the
+ * caches are (N, n) fp32, idx device int64[B].  u_bi = (float)(word >> 8) * 2^-24 with word = output i & 3 of Philox-4x32-10 on
+ * counter {(i >> 2) & 0xffffffff, i >> 34, b, *step}, key {seed & 0xffffffff, seed >> 32} (the generator of nq_qat_forward);
+ * step: device int32 scalar read by the kernel.  prob >= 1: x = xq_cache[idx] and no random number is evaluated (xfp_cache and
+ * step may be NULL).  One launch.  NQ_ERR_INVALID: a null pointer that is needed, B or n <= 0, prob negative or NaN;
+ * NQ_ERR_UNSUPPORTED: B > 65535. */
+#define NQ_UNIT_LP 0
+#define NQ_UNIT_FISHER_DIAG 1
+#define NQ_UNIT_FISHER_FULL 2
+NQ_API int64_t nq_unit_rec_loss_ws_floats(int B, int C, int H, int W, int r);
+NQ_API int nq_unit_rec_loss(const float* pred, const float* tgt, const float* fisher, const int64_t* idx, const float* z,
+                            float* loss, float* dconv, float* ws, int B, int C, int H, int W, int r, int mode, float p,
+                            nq_stream_t stream);
+NQ_API int nq_qdrop_mix(const float* xq_cache, const float* xfp_cache, const int64_t* idx, float* x, int B, int64_t n, float prob,
+                        uint64_t seed, const int* step, nq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("NQ_LIB") or os.path.join(_HERE, "libnqhip.so")
 NQ_OK = 0
 ABI_VERSION = 7   # nq_abi_version() of the library this binding was written against (include/nq_hip.h)
 EPI_PLAIN, EPI_PS_GELU, EPI_TANH, EPI_PS, EPI_DGRAD_GELU = 0, 1, 2, 3, 4
+UNIT_LP, UNIT_FISHER_DIAG, UNIT_FISHER_FULL = 0, 1, 2   # NQ_UNIT_*: the modes of nq_unit_rec_loss
 
 
 class NQLibraryError(RuntimeError):
@@ -251,6 +252,9 @@ def _load():
     sig("nq_magnitude_select", I, POINTER(PruneSeg), I, P, P, P, P)
     sig("nq_prune_mask", I, POINTER(PruneSeg), I, P, P, P, P)
     sig("nq_prune_apply", I, POINTER(PruneSeg), I, P, P)
+    sig("nq_unit_rec_loss_ws_floats", L, I, I, I, I, I)
+    sig("nq_unit_rec_loss", I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P)
+    sig("nq_qdrop_mix", I, P, P, P, P, I, L, F, ctypes.c_uint64, P, P)
     return lib
 
 
@@ -283,6 +287,7 @@ EXPORTS = (
     "nq_patchify_ln_ws_bytes", "nq_patchify_ln_forward", "nq_patchify_ln_backward",
     "nq_qat_ws_floats", "nq_qat_forward", "nq_qat_backward", "nq_qat_levels", "nq_qat_restore",
     "nq_prune_run", "nq_prune_ws_bytes", "nq_magnitude_select", "nq_prune_mask", "nq_prune_apply",
+    "nq_unit_rec_loss_ws_floats", "nq_unit_rec_loss", "nq_qdrop_mix",
 )
 
 _lib = None

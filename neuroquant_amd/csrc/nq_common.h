@@ -121,6 +121,27 @@ static inline int64_t nq_wl_fill(const nq_wl_seg* segs, int i, NqWLSeg& d) {
   return ((int64_t)krows * ld + 255) / 256;
 }
 
+// Philox-4x32-10 (Salmon et al., SC'11): counter {c0, c1, c2, c3}, key {k0, k1} -> four 32-bit words.  The generator of the QAT
+// noise mask (qat.hip) and of the QDrop input mix (unit_rec.hip); integer arithmetic only, the same bits wherever it is compiled.
+__device__ __forceinline__ void nq_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned (&r)[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  r[0] = c0;
+  r[1] = c1;
+  r[2] = c2;
+  r[3] = c3;
+}
+
 // ---- wave / block reductions (wave = 64 lanes) ----
 __device__ __forceinline__ float nq_wave_sum(float v) {
 #pragma unroll

@@ -53,38 +53,19 @@ struct Rng {
   int noise;
 };
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&r)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  r[0] = c0;
-  r[1] = c1;
-  r[2] = c2;
-  r[3] = c3;
-}
-
 // m = 1 iff the top 24 bits of the word, as a fraction of 2^24, exceed 0.9f (torch.rand_like(x) > 0.9, quantizer.py:362)
 __device__ __forceinline__ float mask_of(unsigned word) { return ((float)(word >> 8) * 5.9604644775390625e-8f > 0.9f) ? 1.f : 0.f; }
 
 // the four masks of elements 4 e4 .. 4 e4 + 3 of tensor `index`
 __device__ __forceinline__ void mask4(unsigned e4, unsigned index, const Rng& rng, unsigned step, float (&m)[4]) {
   unsigned r[4];
-  philox4x32_10(e4, 0u, index, step, rng.k0, rng.k1, r);
+  nq_philox4x32_10(e4, 0u, index, step, rng.k0, rng.k1, r);
 #pragma unroll
   for (int i = 0; i < 4; ++i) m[i] = mask_of(r[i]);
 }
 __device__ __forceinline__ float mask1(unsigned e, unsigned index, const Rng& rng, unsigned step) {
   unsigned r[4];
-  philox4x32_10(e >> 2, 0u, index, step, rng.k0, rng.k1, r);
+  nq_philox4x32_10(e >> 2, 0u, index, step, rng.k0, rng.k1, r);
   const unsigned k = e & 3u;
   return mask_of(k == 0 ? r[0] : k == 1 ? r[1] : k == 2 ? r[2] : r[3]);
 }

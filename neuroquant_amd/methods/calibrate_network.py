@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from ..models import HNeRV, NeRV
-from ..quantization import QuantModel, model_reconstruction
+from ..quantization import QuantModel, block_reconstruction, layer_reconstruction, model_reconstruction
 from ..utils import (CacheLoader, FrameCache, RoundTensor, data_split, get_config, setup_logger, synthetic_frames)
 from .. import objective, ops
 from ..objective import SSIM_METRIC_NAME, YUV_METRIC_NAMES   # added to the metrics by the SSIM / the YUV 4:2:0 objective
@@ -81,6 +81,10 @@ def parse_args(argv):
                    help='p of the reconstruction loss lp_loss(p): 2 = squared error; any other p >= 1 runs on csrc/lp_loss.hip (DESIGN.md §32)')
     p.add_argument('--init', default='max', type=str, choices=['max', 'mse', 'gaussian', 'l1', 'l2'])
     p.add_argument('--opt_mode', default='mse', type=str, choices=['mse', 'fisher_diag', 'fisher_full', 'lp_norm'])
+    p.add_argument('--granularity', default='network', type=str, choices=['network', 'block', 'layer'],
+                   help='reconstruction unit: the whole decoder (the paper), or the BRECQ / QDrop and AdaRound baselines that '
+                        'calibrate block by block / layer by layer in decoder order (DESIGN.md §33)')
+    p.add_argument('--asym', action='store_true', help='unit-wise calibration: cache the unit input of the QUANTISED model')
     p.add_argument('--ckpt', default='None', type=str)
     p.add_argument('--dump_vis', action='store_true', default=False)
     p.add_argument('--export_stream', type=str, default=None,
@@ -98,6 +102,7 @@ def parse_args(argv):
                         'per-tensor model of the hard levels (DESIGN.md §23); 0 = off')
     args = p.parse_args(argv)
     rate_params(args, 1)   # a negative or non-finite --rate_lambda stops here
+    unit_wise_args(args)
     if args.precision_file is not None:
         args.precision = read_precision_file(args.precision_file)
     elif args.precision is None:
@@ -229,6 +234,33 @@ def rec_msssim_params(args):
     model_reconstruction(msssim=...); objective_of's refusals."""
     obj = objective_of(args)
     return dict(obj.params) if obj.name == MSSSIM_LOSS else None
+
+
+def unit_wise_args(args):
+    """ValueError, before anything is launched, for what --granularity block / layer does not combine with, and for --opt_mode
+    lp_norm, which the reference's unit loops refuse too; --granularity network checks nothing here."""
+    if getattr(args, 'granularity', 'network') == 'network':
+        return
+    g = f'--granularity {args.granularity}'
+    bad = [flag for flag, on in (('--hadamard', args.hadamard), ('--rec_loss', getattr(args, 'rec_loss', None) not in (None, 'l2')),
+                                 ('--rec_weights', getattr(args, 'rec_weights', None) is not None),
+                                 ('--rec_ms_weights', getattr(args, 'rec_ms_weights', None) is not None),
+                                 ('--loss_domain yuv420', args.loss_domain == 'yuv420'), ('--rate_lambda', args.rate_lambda != 0.0)) if on]
+    if bad:
+        raise ValueError(f'{g} reconstructs activations of one unit: it does not combine with {", ".join(bad)}')
+    if args.opt_mode == 'lp_norm':
+        raise ValueError(f'{g}: --opt_mode lp_norm is not a reconstruction loss (mse, fisher_diag, fisher_full are)')
+    if args.opt_mode != 'mse' and args.norm_p != 2.0:
+        raise ValueError(f'{g}: --norm_p {args.norm_p} applies to --opt_mode mse; {args.opt_mode} has no exponent')
+    ops.lp_loss_args('--norm_p', (1, 1, 1, 1), (1, 1, 1, 1), args.norm_p, 1.0, 0.0)
+
+
+def calibration_units(qnn, granularity):
+    """the units of --granularity block / layer in decoder order: block -- decoder[0], every block, the head; layer -- every
+    QuantModule"""
+    net = qnn.model
+    stages = list(net.decoder) + [net.head_layer]
+    return stages if granularity == 'block' else [getattr(st, 'conv', st) for st in stages]
 
 
 def rate_params(args, pixels):
@@ -458,10 +490,21 @@ def calibrate(args, cfg):
         logging.info('rate term: lambda * bits per pixel of the weight levels, {}'.format(rate_obj))
     start = datetime.now()
     qnn.set_quant_state(weight_quant=True)
-    model_reconstruction(qnn, cali_data=cali_data, gt=train_loader, arch=args.arch, batch_size=args.batch_size,
-                         iters=args.iters_w, weight=args.weight, opt_mode='mse', hadamard=args.hadamard,
-                         b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr,
-                         **obj.engine_kwargs(), **(dict(rate=rate_obj) if rate_obj is not None else {}))
+    granularity = getattr(args, 'granularity', 'network')
+    if granularity == 'network':
+        model_reconstruction(qnn, cali_data=cali_data, gt=train_loader, arch=args.arch, batch_size=args.batch_size,
+                             iters=args.iters_w, weight=args.weight, opt_mode=args.opt_mode, hadamard=args.hadamard,
+                             b_range=(args.b_start, args.b_end), warmup=args.warmup, p=args.norm_p, lr=args.lr,
+                             **obj.engine_kwargs(), **(dict(rate=rate_obj) if rate_obj is not None else {}))
+    else:
+        unit_wise_args(args)
+        units = calibration_units(qnn, granularity)
+        for i, unit in enumerate(units):     # in decoder order, each left quantised
+            logging.info('Reconstruction for {} {} of {}'.format(granularity, i + 1, len(units)))
+            (block_reconstruction if granularity == 'block' else layer_reconstruction)(
+                qnn, unit, cali_data, batch_size=args.batch_size, iters=args.iters_w, weight=args.weight, opt_mode=args.opt_mode,
+                asym=getattr(args, 'asym', False), b_range=(args.b_start, args.b_end), warmup=args.warmup,
+                input_prob=args.input_prob, p=args.norm_p, lr=args.lr)
     torch.cuda.synchronize()
     logging.info(f"Training complete in: {str(datetime.now() - start)}")
 

@@ -2294,6 +2294,93 @@ def lp_loss_head_grad(pred, tgt=None, cache_u8=None, idx=None, node=None, p=1.0,
     return loss3, (g if head is None else _hand_over(head, g, db))
 
 
+# ---- unit-wise reconstruction: the tail of a layer's / block's iteration and the QDrop mix (nq_unit_rec_loss) ----
+UNIT_REC_MODES = {"lp": L.UNIT_LP, "mse": L.UNIT_LP, "fisher_diag": L.UNIT_FISHER_DIAG, "fisher_full": L.UNIT_FISHER_FULL}
+
+
+def unit_rec_args(what, pred, tgt, mode, p, fisher, z, r, idx):
+    """-> (mode number, p as a float); ValueError naming `what` before anything is launched"""
+    for name, t in (("pred", pred), ("tgt", tgt), ("fisher", fisher), ("z", z)):
+        if t is None and name in ("fisher", "z"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.numel() == 0:
+            raise ValueError(f"{what}: {name} must be a non-empty float32 (B, C, H, W) tensor")
+    if mode not in UNIT_REC_MODES:
+        raise ValueError(f"{what}: mode must be one of {tuple(UNIT_REC_MODES)}, got {mode!r}")
+    if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= 5 or pred.shape[2] % r or pred.shape[3] % r:
+        raise ValueError(f"{what}: r must be an int in [1, 5] that divides the sides of pred {tuple(pred.shape)}, got {r!r}")
+    if idx is None:
+        if tgt.shape != pred.shape:
+            raise ValueError(f"{what}: pred {tuple(pred.shape)} and tgt {tuple(tgt.shape)} differ")
+    elif not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.shape != pred.shape[:1] or tgt.shape[1:] != pred.shape[1:]:
+        raise ValueError(f"{what}: with idx, tgt is a cache (N,) + {tuple(pred.shape[1:])} and idx one int64 per sample")
+    pf = 2.0
+    if UNIT_REC_MODES[mode] == L.UNIT_LP:
+        pf = lp_loss_args(what, pred.shape, pred.shape, p, 1.0, 0.0)[0]
+    elif fisher is None or fisher.shape != tgt.shape:
+        raise ValueError(f"{what}: mode {mode!r} takes fisher weights of tgt's shape {tuple(tgt.shape)}")
+    if z is not None and z.shape != pred.shape:
+        raise ValueError(f"{what}: pred {tuple(pred.shape)} and z {tuple(z.shape)} differ")
+    if not all(t is None or t.is_cuda for t in (pred, tgt, fisher, z, idx)):
+        raise ValueError(f"{what}: every tensor must live on the GPU (no CPU fallback exists)")
+    return UNIT_REC_MODES[mode], pf
+
+
+def unit_rec_loss_raw(pred, tgt, mode, p, fisher, z, r, idx, loss=None, dconv=None):
+    """One nq_unit_rec_loss call on checked, contiguous arguments (mode: the number) -> (loss (1,), dconv (B, C r^2, H / r, W / r))"""
+    B, C, Hr, Wr = pred.shape
+    H, W = Hr // r, Wr // r
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32) if loss is None else loss
+    dconv = torch.empty((B, C * r * r, H, W), device=pred.device, dtype=torch.float32) if dconv is None else dconv
+    ws = torch.empty(_q("nq_unit_rec_loss_ws_floats", B, C, H, W, r) // 2, device=pred.device, dtype=torch.float64)
+    L.check(_timed("unit_rec_loss", lambda: L.lib().nq_unit_rec_loss(
+        _p(pred), _p(tgt), _p(fisher), _p(idx), _p(z), _p(loss), _p(dconv), _p(ws), B, C, H, W, r, mode, p, _stream())),
+        "unit_rec_loss")
+    return loss, dconv
+
+
+def unit_rec_loss(pred, tgt, mode="lp", p=2.0, fisher=None, z=None, r=1, idx=None):
+    """The reconstruction tail of one unit (reference calib_block.LossFunction, round_loss aside): the loss of the unit's output
+    `pred` (B, C, H r, W r) against its FP output and the gradient at the unit's CONVOLUTION output -> (loss (1,), dconv (B, C r^2,
+    H, W)) with dconv = pixel_unshuffle(dL/dpred * z, r), what conv_wgrad_raw reads.  mode 'lp' ('mse'): sum_c |d|^p averaged over
+    the rest; 'fisher_diag': (d^2 g^2).sum(1).mean(); 'fisher_full': mean(s_b |d| g) / 100, s_b the sample's sum of |d| g; g =
+    `fisher`.  tgt (and fisher): plain tensors of pred's shape, or with idx (int64 (B,) on the GPU) caches (N, C, H r, W r) read as
+    cache[idx[b]] on the device.  z: the derivative an EPI_PS_GELU forward saved, None for a unit without activation.  One pass
+    over the tensors, bit-identical from call to call.  ValueError for a bad argument before any launch."""
+    m, pf = unit_rec_args("unit_rec_loss", pred, tgt, mode, p, fisher, z, r, idx)
+    c = lambda t: None if t is None else t.detach().contiguous()
+    return unit_rec_loss_raw(c(pred), c(tgt), m, pf, c(fisher) if m != L.UNIT_LP else None, c(z), r, c(idx))
+
+
+def qdrop_mix(xq_cache, xfp_cache, idx, prob, seed=0, step=0):
+    """QDrop's input of one iteration (reference calib_block.py:161-164) in one launch: x[b] = where(u < prob, xq_cache[idx[b]],
+    xfp_cache[idx[b]]) per element, u from Philox-4x32-10 of (seed, step, sample, element) -- `step` an int or an int32 device
+    scalar the kernel reads.  prob >= 1: the gather of xq_cache alone, no random number (xfp_cache may be None)."""
+    try:
+        pr = float(prob)
+    except (TypeError, ValueError):
+        pr = math.nan
+    if not pr >= 0.0:
+        raise ValueError(f"qdrop_mix: prob must be a number >= 0, got {prob!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"qdrop_mix: seed must be an int in [0, 2^64), got {seed!r}")
+    mix = pr < 1.0
+    for name, t in (("xq_cache", xq_cache),) + ((("xfp_cache", xfp_cache),) if mix else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() < 2 or t.numel() == 0:
+            raise ValueError(f"qdrop_mix: {name} must be a non-empty float32 (N, ...) cache on the GPU (no CPU fallback exists)")
+    if mix and xfp_cache.shape != xq_cache.shape:
+        raise ValueError(f"qdrop_mix: the caches differ: {tuple(xq_cache.shape)} and {tuple(xfp_cache.shape)}")
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() == 0:
+        raise ValueError("qdrop_mix: idx is a non-empty 1-d int64 tensor on the GPU")
+    xq = xq_cache.detach().contiguous()
+    xf = xfp_cache.detach().contiguous() if mix else None
+    stp = _qat_step(step, xq.device, "qdrop_mix") if mix else None
+    x = torch.empty((idx.numel(),) + tuple(xq.shape[1:]), device=xq.device, dtype=torch.float32)
+    L.check(_timed("qdrop_mix", lambda: L.lib().nq_qdrop_mix(_p(xq), _p(xf), _p(idx.contiguous()), _p(x), idx.numel(),
+                                                             xq[0].numel(), pr, seed, _p(stp), _stream())), "qdrop_mix")
+    return x
+
+
 def ssim(out, gt):
     """per-frame single-scale SSIM of (F, C, H, W) images -> (F,) fp32 (pytorch_msssim.ssim(out, gt, data_range=1,
     size_average=False)); a frame's value depends on that frame's bytes only.  Forward only (inputs are detached)."""
@@ -2851,12 +2938,12 @@ def qat_args(what, weights, bits, mode, seed=0):
     return bits, QAT_MODES[mode]
 
 
-def _qat_step(step, device):
+def _qat_step(step, device, what="qat_weight"):
     """`step` as the device int32 scalar the kernels read: a tensor is taken as it is (a captured call replays with its value of
     the moment), an int is copied to the device."""
     if isinstance(step, torch.Tensor):
         if step.dtype != torch.int32 or step.numel() != 1 or step.device != device:
-            raise ValueError("qat_weight: a step tensor is one int32 on the weights' device")
+            raise ValueError(f"{what}: a step tensor is one int32 on the weights' device")
         return step
     return torch.tensor([int(step)], dtype=torch.int32, device=device)
 
